@@ -9,7 +9,10 @@ workload: 3D idealized 4-axon mesh, refinement r (default 2: 995 328 tets, 11 94
 Launch  : python bench.py --gpus 1 ...        or, for N > 1,
           python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P
                  bench.py --gpus N ...
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and reports them (headline + `config`);
+--full adds what takes work of its own: the `roofline` block (two further steps with per-apply events, back-to-back apply
+launches, the committed PMC traffic records) and, on one GPU, the `cpu_baseline` (unless --no-cpu-baseline).
+--dump-outputs DIR writes the fields of the last timed step as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import json
@@ -290,6 +293,117 @@ def _cpu_baseline_one_core(resolution):
                          t_setup, t_ode, os.cpu_count() or 0)}
 
 
+DUMP_CELL_BYTES = 48 << 20                 # --dump-outputs: cell fields + facet field stay under 64 MB in all
+DUMP_FACET_BYTES = 8 << 20
+
+
+def dump_outputs(S, path):
+    """What a caller of the timed path holds after its last step, as float64 arrays: phi [cells, nd], the solved concentrations
+    c [species, cells, nd], the eliminated species c_elim [cells, nd] and the membrane potential phi_M [facets].  When the fields
+    exceed the budget, the same fixed, seeded sample of cells (and of facets), in ascending order, is taken from every field:
+    identical for every run with the same arguments."""
+    fields = {"phi": S.phi.array(), "c": S.c.array(), "c_elim": S.ion_list[-1]["c"].array()}
+    phi_M = S.phi_M_prev_PDE.array()
+    nc, nd = fields["phi"].shape
+    n_cells = min(nc, DUMP_CELL_BYTES // (8 * nd * (S.N_ions + 2)))
+    n_facets = min(phi_M.size, DUMP_FACET_BYTES // 8)
+    cells = np.sort(np.random.default_rng(0).choice(nc, n_cells, replace=False)) if n_cells < nc else slice(None)
+    facets = np.sort(np.random.default_rng(1).choice(phi_M.size, n_facets, replace=False)) if n_facets < phi_M.size else slice(None)
+    os.makedirs(path, exist_ok=True)
+    for name, a in fields.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a[..., cells, :], dtype=np.float64))
+    np.save(os.path.join(path, "phi_M.npy"), np.ascontiguousarray(phi_M[facets], dtype=np.float64))
+
+
+def measure_roofline(S, A, degree, k, t):
+    """--full: the `roofline` block of the bench line, measured after the timed steps (`k`: index of the next step)."""
+    # --- roofline of the dominant kernels (operator applies), HIP events on the context's stream.
+    # (1) in-solver: every apply launched by the solves of two further steps is bracketed by an event pair (knp_apply_timing);
+    # (2) back-to-back: 200 launches rotating three vector pairs (knp_bench_apply) -- the figure `roofline.achieved` uses is
+    #     the SLOWER, in-solver one.
+    nc_local = S.dev.nc_owned
+    S.dev.apply_timing(True)
+    for _ in range(2):
+        S.step_membrane_models(k); S.solve_for_time_step(k, t); k += 1
+    emi_solver_ms, emi_n = S.dev.apply_timing_read(0)
+    knp_solver_ms, knp_n = S.dev.apply_timing_read(1)
+    S.dev.apply_timing(False)
+    rng = np.random.default_rng(0)
+    S.dev.upload(A.F_X, rng.uniform(-1, 1, size=S.dev.size(A.F_X)))
+    S.dev.update_kappa(); S.dev.update_dnphi()
+    emi_b2b_ms = S.dev.bench_apply(0, 200)
+    knp_b2b_ms = S.dev.bench_apply(1, 200)
+    emi_ms = max(emi_solver_ms, emi_b2b_ms) if emi_n else emi_b2b_ms
+    knp_ms = max(knp_solver_ms, knp_b2b_ms) if knp_n else knp_b2b_ms
+    # algorithmic bytes per cell (SURVEY.md section 8d): P1 137 / 217, P2 281 / 457
+    emi_bpc = EMI_BYTES_PER_CELL if degree == 1 else 281.0
+    knp_bpc = KNP_BYTES_PER_CELL if degree == 1 else 457.0
+    emi_gbs = emi_bpc * nc_local / (emi_ms * 1e-3) / 1e9
+    knp_gbs = knp_bpc * nc_local / (knp_ms * 1e-3) / 1e9
+
+    # HBM-side traffic of the same kernel on the same workload, from the committed rocprofv3 --pmc passes
+    # (counters cannot be read from inside this process); null when the workload differs
+    cls = bool(S.dev.n_geometry_classes)
+    if degree == 1:
+        emi_name = {3: "k_emi_apply_ring", 1: "k_emi_apply_cls_staged<3,256>", 10: "k_emi_apply_ring_u"}.get(S.dev.apply_variant(0), "k_emi_apply<3,3>")
+        kv = S.dev.apply_variant(1)
+        knp_name = {7: "k_knp_apply_ring<2>", 2: "k_knp_apply_halo<2,false>", 6: "k_knp_apply_halo<2,true>",
+                    1: "k_knp_apply_cls_staged<3,2,256>", 10: "k_knp_apply_ring_u<2>"}.get(kv, "k_knp_apply<3,2>")
+    else:
+        emi_name = "k_emi_apply_p2<3,256,%s>" % ("true" if cls else "false")
+        knp_name = "k_knp_apply_p2<3,256,%s>" % ("true" if cls else "false")
+    # FP64 vector instructions per cell of the two apply kernels (static counts from the gfx950 ISA, loops fully unrolled: DESIGN.md
+    # sections 4.0 / 4b) against the chip's FP64 issue peak, 256 CUs x 4 SIMDs x 16 lanes per cycle at 2.4 GHz: the second roofline
+    # of these kernels (the P2 applies are bound by it, the P1 ring-staged applies sit between it and the HBM one)
+    # (tools/count_fp64.py prints them from the current sources; the DG-P2 KNP kernel runs one species per pass: 2 x 2304)
+    fp64_per_cell = {"k_emi_apply_ring": 542, "k_knp_apply_ring<2>": 435, "k_emi_apply_p2<3,256,true>": 2035,
+                     "k_knp_apply_p2<3,256,true>": 2 * 2304, "k_emi_apply_ring_u": 636, "k_knp_apply_ring_u<2>": 684,
+                     "k_emi_apply_p2<3,256,false>": 2264, "k_knp_apply_p2<3,256,false>": 2 * 2533}
+    FP64_PEAK_TINST = 256 * 4 * 16 * 2.4e9 / 1e12
+
+    def fp64_issue(name, ms):
+        n = fp64_per_cell.get(name)
+        if n is None:
+            return None
+        ach = n * nc_local / (ms * 1e-3) / 1e12
+        return {"fp64_instructions_per_cell": n, "achieved": ach, "peak": FP64_PEAK_TINST, "unit": "T lane-instructions/s",
+                "frac": ach / FP64_PEAK_TINST}
+    # A record counts only for the code it was measured on: it carries the sha256 (first 16 hex digits) of the kernel's source file at the
+    # time of the counter pass (tools/pmc_traffic_update.py), and a kernel edited since then reports null until a new pass is committed.
+    traffic = traffic_emi = None
+    try:
+        import hashlib
+        pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
+        sha = {}
+
+        def current(src):
+            if src not in sha:
+                with open(os.path.join(ROOT, "knp-emi-dg_amd", "csrc", src), "rb") as fh:
+                    sha[src] = hashlib.sha256(fh.read()).hexdigest()[:16]
+            return sha[src]
+        for key, rec in pmc.items():
+            if isinstance(rec, dict) and rec.get("cells_per_launch") == nc_local and rec.get("source") and rec.get("source_sha16") == current(rec["source"]):
+                if key.split(":")[0] == emi_name:
+                    traffic_emi = rec["traffic_bytes"]
+                if key.split(":")[0] == knp_name:
+                    traffic = rec["traffic_bytes"]
+    except (OSError, ValueError, KeyError):
+        pass
+
+    # dominant kernel of a step = the KNP operator apply (all solved species in one launch; ~30 % of the kernel time
+    # of the profiled run, profiles/): the EMI apply, same design, is reported next to it
+    return {"bound": "hbm", "kernel": knp_name, "achieved": knp_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": knp_gbs / HBM_PEAK_GBS, "traffic": traffic, "avg_kernel_us": knp_ms * 1e3,
+            "algorithmic_bytes_per_cell": knp_bpc, "cells_per_launch": nc_local,
+            "in_solver_us": knp_solver_ms * 1e3, "in_solver_launches": knp_n, "back_to_back_us": knp_b2b_ms * 1e3,
+            "fp64_issue": fp64_issue(knp_name, knp_ms),
+            "emi_apply": {"kernel": emi_name, "achieved": emi_gbs, "frac": emi_gbs / HBM_PEAK_GBS, "traffic": traffic_emi,
+                          "avg_kernel_us": emi_ms * 1e3, "algorithmic_bytes_per_cell": emi_bpc,
+                          "in_solver_us": emi_solver_ms * 1e3, "in_solver_launches": emi_n,
+                          "fp64_issue": fp64_issue(emi_name, emi_ms),
+                          "back_to_back_us": emi_b2b_ms * 1e3}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -301,8 +415,13 @@ def main():
                     help="idealized = the headline 4-axon BoxMesh (default); emix = BASELINE configs[4], the reference's bundled tissue "
                          "reconstruction (121 617 unstructured tets, coordinate-path kernels, cm / ms / mV)")
     ap.add_argument("--refine", type=int, default=0, help="--workload emix: regular refinements of the tissue mesh (1: 972 936 tets)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the apply-kernel roofline and, on one GPU, the CPU baseline (work of their own, not in the headline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the fields of the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -311,6 +430,8 @@ def main():
     if args.gpus != world:
         if world == 1 and args.gpus > 1:
             raise SystemExit("launch with torch.distributed.run for --gpus > 1")
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs writes the fields of one rank: run it with one process")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: no GPU visible (there is no CPU fallback)")
     shm_ranks = bool(os.environ.get("KNP_COMM_SHM"))      # validation only: several ranks on ONE GPU over the shared-memory communicator
@@ -412,79 +533,9 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     ms_per_step = 1e3 * elapsed / args.steps
-
-    # --- roofline of the dominant kernels (operator applies), HIP events on the context's stream.
-    # (1) in-solver: every apply launched by the solves of two further steps is bracketed by an event pair (knp_apply_timing);
-    # (2) back-to-back: 200 launches rotating three vector pairs (knp_bench_apply) -- the figure `roofline.achieved` uses is
-    #     the SLOWER, in-solver one.
-    nc_local = S.dev.nc_owned
-    S.dev.apply_timing(True)
-    for _ in range(2):
-        S.step_membrane_models(k); S.solve_for_time_step(k, t); k += 1
-    emi_solver_ms, emi_n = S.dev.apply_timing_read(0)
-    knp_solver_ms, knp_n = S.dev.apply_timing_read(1)
-    S.dev.apply_timing(False)
-    rng = np.random.default_rng(0)
-    S.dev.upload(A.F_X, rng.uniform(-1, 1, size=S.dev.size(A.F_X)))
-    S.dev.update_kappa(); S.dev.update_dnphi()
-    emi_b2b_ms = S.dev.bench_apply(0, 200)
-    knp_b2b_ms = S.dev.bench_apply(1, 200)
-    emi_ms = max(emi_solver_ms, emi_b2b_ms) if emi_n else emi_b2b_ms
-    knp_ms = max(knp_solver_ms, knp_b2b_ms) if knp_n else knp_b2b_ms
-    # algorithmic bytes per cell: P1 137 / 217, P2 281 / 457
-    emi_bpc = EMI_BYTES_PER_CELL if args.degree == 1 else 281.0
-    knp_bpc = KNP_BYTES_PER_CELL if args.degree == 1 else 457.0
-    emi_gbs = emi_bpc * nc_local / (emi_ms * 1e-3) / 1e9
-    knp_gbs = knp_bpc * nc_local / (knp_ms * 1e-3) / 1e9
-
-    # HBM-side traffic of the same kernel on the same workload, from the committed rocprofv3 --pmc passes
-    # (counters cannot be read from inside this process); null when the workload differs
-    cls = bool(S.dev.n_geometry_classes)
-    if args.degree == 1:
-        emi_name = {3: "k_emi_apply_ring", 1: "k_emi_apply_cls_staged<3,256>", 10: "k_emi_apply_ring_u"}.get(S.dev.apply_variant(0), "k_emi_apply<3,3>")
-        kv = S.dev.apply_variant(1)
-        knp_name = {7: "k_knp_apply_ring<2>", 2: "k_knp_apply_halo<2,false>", 6: "k_knp_apply_halo<2,true>",
-                    1: "k_knp_apply_cls_staged<3,2,256>", 10: "k_knp_apply_ring_u<2>"}.get(kv, "k_knp_apply<3,2>")
-    else:
-        emi_name = "k_emi_apply_p2<3,256,%s>" % ("true" if cls else "false")
-        knp_name = "k_knp_apply_p2<3,256,%s>" % ("true" if cls else "false")
-    # FP64 vector instructions per cell of the two apply kernels (static counts from the gfx950 ISA, loops fully unrolled: DESIGN.md
-    # sections 4.0 / 4b) against the chip's FP64 issue peak, 256 CUs x 4 SIMDs x 16 lanes per cycle at 2.4 GHz: the second roofline
-    # of these kernels (the P2 applies are bound by it, the P1 ring-staged applies sit between it and the HBM one)
-    # (tools/count_fp64.py prints them from the current sources; the DG-P2 KNP kernel runs one species per pass: 2 x 2304)
-    fp64_per_cell = {"k_emi_apply_ring": 542, "k_knp_apply_ring<2>": 435, "k_emi_apply_p2<3,256,true>": 2035,
-                     "k_knp_apply_p2<3,256,true>": 2 * 2304, "k_emi_apply_ring_u": 636, "k_knp_apply_ring_u<2>": 684,
-                     "k_emi_apply_p2<3,256,false>": 2264, "k_knp_apply_p2<3,256,false>": 2 * 2533}
-    FP64_PEAK_TINST = 256 * 4 * 16 * 2.4e9 / 1e12
-
-    def fp64_issue(name, ms):
-        n = fp64_per_cell.get(name)
-        if n is None:
-            return None
-        ach = n * nc_local / (ms * 1e-3) / 1e12
-        return {"fp64_instructions_per_cell": n, "achieved": ach, "peak": FP64_PEAK_TINST, "unit": "T lane-instructions/s",
-                "frac": ach / FP64_PEAK_TINST}
-    # A record counts only for the code it was measured on: it carries the sha256 (first 16 hex digits) of the kernel's source file at the
-    # time of the counter pass (tools/pmc_traffic_update.py), and a kernel edited since then reports null until a new pass is committed.
-    traffic = traffic_emi = None
-    try:
-        import hashlib
-        pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
-        sha = {}
-
-        def current(src):
-            if src not in sha:
-                with open(os.path.join(ROOT, "knp-emi-dg_amd", "csrc", src), "rb") as fh:
-                    sha[src] = hashlib.sha256(fh.read()).hexdigest()[:16]
-            return sha[src]
-        for key, rec in pmc.items():
-            if isinstance(rec, dict) and rec.get("cells_per_launch") == nc_local and rec.get("source") and rec.get("source_sha16") == current(rec["source"]):
-                if key.split(":")[0] == emi_name:
-                    traffic_emi = rec["traffic_bytes"]
-                if key.split(":")[0] == knp_name:
-                    traffic = rec["traffic_bytes"]
-    except (OSError, ValueError, KeyError):
-        pass
+    if args.dump_outputs:
+        dump_outputs(S, args.dump_outputs)
+    roofline = measure_roofline(S, A, args.degree, k, t) if args.full else None
 
     progress("timed region: %.2f ms/step; a %d-step run of examples/idealized-geometries/run_3D.py:60-62 at this rate + the %.1f s of setup "
              "above = %.1f s end to end" % (ms_per_step, 200, t_ready, t_ready + 0.2 * ms_per_step))
@@ -499,9 +550,6 @@ def main():
                                    ("3D idealized 4-axon mesh r=%d (%d tets, %d P%d-DG DoFs: phi + K,Cl solved, Na eliminated), "
                                     "HH membranes + stimulus, full splitting step" % (r, nc_global, dofs, args.degree)),
                        "parallelism": ("rcb%d" if emix else "slab%d") % world,
-                       "cpu_baseline_workload": "the same mesh family at r=1 (124 416 tets, 1 492 992 DoFs), ONE step on cpu_baseline.cores host "
-                                                "cores -- NOT the GPU line's r=%d mesh: one oracle step at r=2 is ~70 s of assembly + solves "
-                                                "on one core, beyond the bounded sample the default run may spend" % r,
                        "preconditioner": ("cell-block-Jacobi + conforming-P%d auxiliary space, smoothed-aggregation AMG V-cycle; block inverses, level "
                                           "matrices and coarse inverse stored in fp32, vectors / operator applies / stopping tests in fp64"
                                           % args.degree) if S.use_amg
@@ -512,21 +560,15 @@ def main():
                        "setup_s_before_first_step": t_first_step,
                        # DG-level smoother of the EMI preconditioner as measured by the run itself on its solves 1-4 (knpemidg/solver.py)
                        "emi_dg_smoother": getattr(S, "emi_dg_chebyshev_measured", None)},
-            # dominant kernel of a step = the KNP operator apply (all solved species in one launch; ~30 % of the kernel time
-            # of the profiled run, profiles/): the EMI apply, same design, is reported next to it
-            "roofline": {"bound": "hbm", "kernel": knp_name, "achieved": knp_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": knp_gbs / HBM_PEAK_GBS, "traffic": traffic, "avg_kernel_us": knp_ms * 1e3,
-                         "algorithmic_bytes_per_cell": knp_bpc, "cells_per_launch": nc_local,
-                         "in_solver_us": knp_solver_ms * 1e3, "in_solver_launches": knp_n, "back_to_back_us": knp_b2b_ms * 1e3,
-                         "fp64_issue": fp64_issue(knp_name, knp_ms),
-                         "emi_apply": {"kernel": emi_name, "achieved": emi_gbs, "frac": emi_gbs / HBM_PEAK_GBS, "traffic": traffic_emi,
-                                       "avg_kernel_us": emi_ms * 1e3, "algorithmic_bytes_per_cell": emi_bpc,
-                                       "in_solver_us": emi_solver_ms * 1e3, "in_solver_launches": emi_n,
-                                       "fp64_issue": fp64_issue(emi_name, emi_ms),
-                                       "back_to_back_us": emi_b2b_ms * 1e3}},
         }
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline()
+        if args.full:
+            out["roofline"] = roofline
+            out["config"]["cpu_baseline_workload"] = (
+                "the same mesh family at r=1 (124 416 tets, 1 492 992 DoFs), ONE step on cpu_baseline.cores host cores -- NOT the GPU "
+                "line's r=%d mesh: one oracle step at r=2 is ~70 s of assembly + solves on one core, beyond the bounded sample a --full "
+                "run may spend" % r)
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

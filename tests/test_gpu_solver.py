@@ -500,6 +500,30 @@ def test_rccl_code_path_with_one_rank(hip_lib):
     assert a["config"]["knp_iters_per_step"] == b["config"]["knp_iters_per_step"]
 
 
+def test_bench_plain_run_and_dump_outputs(hip_lib, tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps, prints the headline fields without the roofline / CPU-baseline
+    work, and --dump-outputs writes the fields of the last timed step: float64 .npy files of the solver's shapes, finite, < 64 MB."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    res = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--resolution", "0", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(out)], cwd=root, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f64"
+    assert d["metric"] == "DoF-updates/sec per PDE timestep" and d["unit"] == "DoF/s" and d["higher_is_better"] is True
+    assert "roofline" not in d and "cpu_baseline" not in d
+    f = {n: np.load(str(out / (n + ".npy"))) for n in ("phi", "c", "c_elim", "phi_M")}
+    assert sorted(p.name for p in out.iterdir()) == ["c.npy", "c_elim.npy", "phi.npy", "phi_M.npy"]
+    nc, nd = f["phi"].shape
+    assert nc > 0 and nd == 4 and f["c"].shape == (2, nc, nd) and f["c_elim"].shape == (nc, nd) and f["phi_M"].ndim == 1
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in f.values())
+    assert sum(a.nbytes for a in f.values()) <= 64 << 20
+
+
 @pytest.mark.parametrize("which", ["hh_emix", "glial"])
 def test_emix_device_ode_models_match_host(hip_lib, which):
     """Device implementations of the EMIx membrane models (cm / ms / mV; reference: examples/emix-simulations/mm_hh.py,

@@ -711,3 +711,39 @@ def test_cancelled_helpers_leave_nothing_in_dev_shm():
     res = W.collect(h)
     assert res is not None and len(res["levels"]) >= 1
     assert set(glob.glob("/dev/shm/knp_setup_*")) == before
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """bench.dump_outputs on fields of the r=2 P1 bench workload's shapes (995 328 cells, 2 solved species, 2 M facets): float64,
+    under 64 MB in all, the same cells in every field and the same seeded sample on every call; small fields are written whole."""
+    import types
+    import bench
+
+    class F:
+        def __init__(self, a):
+            self.a = a
+
+        def array(self):
+            return self.a
+
+    def fields(nc, nd, nf):
+        x = np.arange(nc, dtype=np.float64)[:, None] + np.arange(nd) / 10.0        # value encodes (cell, node)
+        return types.SimpleNamespace(N_ions=2, phi=F(x), c=F(np.stack([x + 1e7, x + 2e7])), ion_list=[{}, {}, {"c": F(x + 3e7)}],
+                                     phi_M_prev_PDE=F(np.arange(nf, dtype=np.float64)))
+
+    S = fields(995328, 4, 2000000)
+    got = []
+    for run in ("a", "b"):
+        bench.dump_outputs(S, str(tmp_path / run))
+        got.append({n: np.load(str(tmp_path / run / (n + ".npy"))) for n in ("phi", "c", "c_elim", "phi_M")})
+    a, b = got
+    assert all(a[n].dtype == np.float64 and np.array_equal(a[n], b[n]) for n in a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    cells = a["phi"][:, 0]
+    assert 0 < cells.size < 995328 and (np.diff(cells) > 0).all()
+    assert np.array_equal(a["c"][0], a["phi"] + 1e7) and np.array_equal(a["c"][1], a["phi"] + 2e7) and np.array_equal(a["c_elim"], a["phi"] + 3e7)
+    assert 0 < a["phi_M"].size < 2000000 and (np.diff(a["phi_M"]) > 0).all()
+    S = fields(1000, 10, 3000)
+    bench.dump_outputs(S, str(tmp_path / "small"))
+    assert np.array_equal(np.load(str(tmp_path / "small" / "c.npy")), S.c.a)
+    assert np.array_equal(np.load(str(tmp_path / "small" / "phi_M.npy")), S.phi_M_prev_PDE.a)

@@ -7,7 +7,7 @@ out="gpurun_out/$1"; shift
 IFS=';' read -ra wl <<< "${WORKLOADS:---resolution 2 --steps 20 --warmup 5}"
 for envs in "$@"; do
   for w in "${wl[@]}"; do
-    env $envs python bench.py $w --no-cpu-baseline 2>gpurun_out/ab_last_stderr.log | ENVS="$envs" W="$w" python -c "
+    env $envs python bench.py $w --full --no-cpu-baseline 2>"${out%/*}/ab_last_stderr.log" | ENVS="$envs" W="$w" python -c "
 import sys, json, os
 lines = [l for l in sys.stdin.read().strip().splitlines() if l.startswith('{')]
 if not lines:

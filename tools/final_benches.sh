@@ -3,13 +3,13 @@
 tag=${1:-vX}
 cd "$GRAFT_REPO_ROOT" || exit 1
 o=gpurun_out
-python bench.py > $o/${tag}_bench_default.json 2> $o/${tag}_bench_default.err || exit 1
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $o/${tag}_p1_r2.json 2> $o/${tag}_p1_r2.err || exit 1
-python bench.py --resolution 3 --steps 10 --warmup 3 --no-cpu-baseline > $o/${tag}_p1_r3.json 2> $o/${tag}_p1_r3.err || exit 1
-python bench.py --degree 2 --resolution 1 --steps 20 --warmup 5 --no-cpu-baseline > $o/${tag}_p2_r1.json 2> $o/${tag}_p2_r1.err || exit 1
-python bench.py --degree 2 --resolution 2 --steps 10 --warmup 3 --no-cpu-baseline > $o/${tag}_p2_r2.json 2> $o/${tag}_p2_r2.err || exit 1
+python bench.py --full > $o/${tag}_bench_default.json 2> $o/${tag}_bench_default.err || exit 1
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $o/${tag}_p1_r2.json 2> $o/${tag}_p1_r2.err || exit 1
+python bench.py --full --resolution 3 --steps 10 --warmup 3 --no-cpu-baseline > $o/${tag}_p1_r3.json 2> $o/${tag}_p1_r3.err || exit 1
+python bench.py --full --degree 2 --resolution 1 --steps 20 --warmup 5 --no-cpu-baseline > $o/${tag}_p2_r1.json 2> $o/${tag}_p2_r1.err || exit 1
+python bench.py --full --degree 2 --resolution 2 --steps 10 --warmup 3 --no-cpu-baseline > $o/${tag}_p2_r2.json 2> $o/${tag}_p2_r2.err || exit 1
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_$tag -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $o/${tag}_bench_r2_profiled.json 2> $o/prof_$tag.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_$tag -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $o/${tag}_bench_r2_profiled.json 2> $o/prof_$tag.err
 find $o/prof_$tag -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $o/${tag}_bench_r2_kernel_stats.csv
 rm -rf $o/prof_$tag
 python - "$tag" <<'PY'
