@@ -161,6 +161,7 @@ int knp_knp_rhs(knp_ctx* ctx);             /* B_KNP <- L_knp(C, C_PREV, C_ELIM, 
  *             a sum-type stand-in for the max norm; the caller derives r_abs from the accuracy wanted in the concentrations, and
  *        (ii) ||phi - phi_k||_A <= rtol ||phi||_A   -- the energy-norm error of the iterate, estimated from the CG coefficients through the
  *             Hestenes-Stiefel identity ||x - x_k||_A^2 = sum_{j >= k} alpha_j (r_j . z_j), which holds for ANY SPD preconditioner
+ *             (the tail of the sum extrapolated with the decay rate of its terms smoothed over the last quarter of the iterations)
  *      hold, at the latest when ||M^-1 r|| <= 1e-11 ||M^-1 b|| (targets below what fp64 reaches must not loop forever); atol is not used;
  *      res = {||r0 / vol||_8, ||r / vol||_8, estimated ||phi - phi_k||_A / ||phi||_A}.  Neither (i) nor (ii) depends on the preconditioner.
  * KNP: per-species BiCGStab (or GMRES, knp_set_knp_krylov), same preconditioner family, TRUE residual: converged when
