@@ -71,8 +71,9 @@ def solver_parameters(dim, resolution, **extra):
     return namedtuple('solver_params', names)(*vals)
 
 
-def make_solver(dim=3, resolution=0, n_axons=4, degree=1, dt=1.0e-4, verbose=False, mesh_tuple=None):
-    """Build a ready-to-run solver for the 2D / 3D idealized geometry."""
+def make_solver(dim=3, resolution=0, n_axons=4, degree=1, dt=1.0e-4, verbose=False, mesh_tuple=None, ode_models=None):
+    """Build a ready-to-run solver for the 2D / 3D idealized geometry (ode_models: {tag: model module} instead of the
+    reference's HH membranes)."""
     from knpemidg import setup_worker
     setup_worker.prestart(2)           # the hierarchy helpers start importing now, while the mesh is being built
     from knpemidg import _abi
@@ -82,9 +83,9 @@ def make_solver(dim=3, resolution=0, n_axons=4, degree=1, dt=1.0e-4, verbose=Fal
         mesh_tuple = make_mesh_3D(resolution, n_axons=n_axons) if dim == 3 else make_mesh_2D(resolution)
     _abi._stamp("make_solver: mesh built")
     mesh, subdomains, surfaces = mesh_tuple
-    if dim == 3:
+    if ode_models is None and dim == 3:
         ode_models = {1: mm_hh, 2: mm_hh_no_stim} if n_axons > 1 else {1: mm_hh}          # run_3D.py:196
-    else:
+    elif ode_models is None:
         ode_models = {1: mm_hh}                                                           # run_2D.py:197
     S = SolverIdealized(params, ion_list, degree_emi=degree, degree_knp=degree)
     S.verbose = verbose

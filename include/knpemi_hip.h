@@ -16,6 +16,7 @@
  */
 #ifndef KNPEMI_HIP_H
 #define KNPEMI_HIP_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -267,6 +268,17 @@ int knp_ode_exchange_multi(knp_ctx* ctx, int handle, int n, const int32_t* what,
                            const int64_t* offset, int to_facet);
 int knp_ode_set_stimulus(knp_ctx* ctx, int handle, int n_entries, const int32_t* cols, const double* values, const uint8_t* mask);
 int knp_ode_step(knp_ctx* ctx, int handle, double t0, double dt, double rtol, double atol);
+/* Runtime-compiled right-hand sides (a model module's HIP_RHS, knpemidg/ode_rtc.py builds the translation unit around
+ * csrc/ode_dp5.hpp, the integrator of knp_ode_step):
+ *  knp_ode_rtc_compile: hipRTC for gfx950 with the library's code generation settings; host only (no context, no device).
+ *                       *code / *size: the code object (release with knp_ode_rtc_free); log[logcap]: diagnostics and the
+ *                       resource-usage remarks (VGPRs, scratch).  Non-zero on failure, with the compiler's log.
+ *  knp_ode_register   : loads such a code object on the context's device; returns a model id >= 1000 for knp_ode_create
+ *                       (which checks ns / np against it) and knp_ode_step (same launch shape, arguments, stream and failure
+ *                       flag as the built-in models); the modules are unloaded with the context */
+int knp_ode_rtc_compile(const char* src, const char* name, void** code, size_t* size, char* log, size_t logcap);
+void knp_ode_rtc_free(void* code);
+int knp_ode_register(knp_ctx* ctx, const void* code, size_t size, const char* kernel_name, int ns, int np);
 
 /* ---- host-side setup kernels (no device work): threaded sparse products of the preconditioner setup (knpemidg/amg.py), the
  * counterpart of the BoomerAMG setup PETSc runs inside KSPSetUp (solver.py:433, 505, 688, 767).  CSR, int32 indices, fp64 values.

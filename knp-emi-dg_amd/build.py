@@ -49,7 +49,7 @@ def build(force=False, verbose=False):
     if not ok:
         raise RuntimeError("hipcc failed")
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + objs + \
-          ["-L/opt/rocm/lib", "-lrccl", "-lpthread", "-Wl,-rpath,/opt/rocm/lib"]
+          ["-L/opt/rocm/lib", "-lrccl", "-lhiprtc", "-lpthread", "-Wl,-rpath,/opt/rocm/lib"]
     subprocess.check_call(cmd)
     return OUT
 

@@ -6,14 +6,18 @@
 // membrane models of the idealized examples (reference: examples/idealized-geometries/mm_hh.py:118-161).
 #include "../../include/knpemi_hip.h"
 #include "knpemi_internal.hpp"
+#include "ode_dp5.hpp"
+#include <hip/hiprtc.h>
+#include <cstdlib>
+#include <cstring>
 
 #define ODE_MAX_STATES 11
 #define ODE_MAX_PARAMS 20
-#define ODE_MAX_STIM 4
 #define ODE_MAX_OPS 12
+#define ODE_RTC_ID0 1000        // model ids of runtime-compiled right-hand sides (knp_ode_register): 1000, 1001, ... per context
 
 struct OdeSet {
-    int model = 0;              // 1 = HH with synaptic stimulus, 2 = HH without, 3 = EMIx HH (cm/ms/mV), 4 = glial, 5 = passive leak, 6 = EMIx calibration system
+    int model = 0;              // 1 = HH with synaptic stimulus, 2 = HH without, 3 = EMIx HH (cm/ms/mV), 4 = glial, 5 = passive leak, 6 = EMIx calibration system, >= 1000 = a registered HIP_RHS kernel
     int ns = 0, np = 0;
     int64_t n = 0;
     int32_t* facet = nullptr;   // [n] facet id of every node
@@ -27,9 +31,21 @@ struct OdeSet {
     double stim_val[ODE_MAX_STIM] = {0};
 };
 
-struct StimArgs { int n; int col[ODE_MAX_STIM]; double val[ODE_MAX_STIM]; };
-
 static std::map<knp_ctx*, std::vector<OdeSet>> g_ode;
+
+// a model module's HIP_RHS compiled by hipRTC (knpemidg/ode_rtc.py) and loaded on one context's device
+struct RtcModel {
+    hipModule_t mod = nullptr;
+    hipFunction_t fn = nullptr;
+    int ns = 0, np = 0;
+};
+static std::map<knp_ctx*, std::vector<RtcModel>> g_rtc;
+
+static const RtcModel* rtc_model(knp_ctx* c, int model) {
+    auto it = g_rtc.find(c);
+    if (it == g_rtc.end() || model < ODE_RTC_ID0 || model - ODE_RTC_ID0 >= (int)it->second.size()) return nullptr;
+    return &it->second[model - ODE_RTC_ID0];
+}
 
 // Hodgkin-Huxley squid axon + leak + Na/K pump (+ decaying synaptic conductance), SI units.
 // parameter layout (mm_hh.py:56-64): 0 g_Na_bar 1 g_K_bar 2 g_leak_Na 3 g_leak_K 4 E_Na 5 E_K 6 Cm 7 stim_amplitude
@@ -179,87 +195,16 @@ template <int MODEL> __device__ __forceinline__ void model_rhs(double t, const d
     else calibration_rhs(t, y, p, dy);
 }
 
+template <int MODEL> struct BuiltinRhs {
+    __device__ __forceinline__ void operator()(double t, const double* y, double* p, double* dy) const { model_rhs<MODEL>(t, y, p, dy); }
+};
+
 template <int MODEL, int NS, int NP>
 __global__ __launch_bounds__(64) void k_ode_step(int64_t n, double t0, double t1, double rtol, double atol, int max_steps,
                                                  double* __restrict__ states, double* __restrict__ params,
                                                  double* __restrict__ hstore, int* __restrict__ fail,
                                                  const uint8_t* __restrict__ stim_mask, StimArgs stim) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double y[NS], p[NP], k[7][NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) y[s] = states[i * NS + s];
-#pragma unroll
-    for (int q = 0; q < NP; ++q) p[q] = params[i * NP + q];
-    // the stimulus overwrites its parameters on the masked rows at the start of EVERY step (membrane.py:102-104), whatever a
-    // hook or a parameter upload wrote there in between
-    if (stim.n > 0 && stim_mask[i]) {
-        for (int e = 0; e < stim.n; ++e)
-#pragma unroll
-            for (int q = 0; q < NP; ++q)
-                if (q == stim.col[e]) p[q] = stim.val[e];
-    }
-    // Dormand-Prince 5(4)
-    const double C[7] = {0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1, 1};
-    const double A[7][6] = {{0, 0, 0, 0, 0, 0},
-                            {1.0 / 5, 0, 0, 0, 0, 0},
-                            {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
-                            {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
-                            {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
-                            {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0},
-                            {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}};
-    const double B5[7] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0};
-    const double B4[7] = {5179.0 / 57600, 0, 7571.0 / 16695, 393.0 / 640, -92097.0 / 339200, 187.0 / 2100, 1.0 / 40};
-    double t = t0;
-    double h = hstore[i];
-    if (!(h > 0.0)) h = (t1 - t0) / 16;
-    const double tiny = 1e-14 * fmax(fabs(t1), 1e-30);
-    model_rhs<MODEL>(t, y, p, k[0]);
-    int steps = 0;
-    bool done = false;
-    while (!done && steps < max_steps) {
-        const double hh = fmin(h, t1 - t);
-#pragma unroll
-        for (int s = 1; s < 7; ++s) {
-            double ys[NS];
-#pragma unroll
-            for (int q = 0; q < NS; ++q) {
-                double acc = 0.0;
-#pragma unroll
-                for (int j = 0; j < 6; ++j)
-                    if (j < s) acc += A[s][j] * k[j][q];
-                ys[q] = y[q] + hh * acc;
-            }
-            model_rhs<MODEL>(t + C[s] * hh, ys, p, k[s]);
-        }
-        double e = 0.0, y5[NS];
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-            double a5 = 0.0, ae = 0.0;
-#pragma unroll
-            for (int j = 0; j < 7; ++j) { a5 += B5[j] * k[j][q]; ae += (B5[j] - B4[j]) * k[j][q]; }
-            y5[q] = y[q] + hh * a5;
-            const double scale = fmax(atol + rtol * fmax(fabs(y[q]), fabs(y5[q])), 1e-300);   // atol = 0 is the reference's (membrane.py:112)
-            e = fmax(e, fabs(hh * ae) / scale);
-        }
-        if (!(e == e) || isinf(e)) e = 1e10;
-        ++steps;
-        if (e <= 1.0 || hh < tiny) {
-            t += hh;
-#pragma unroll
-            for (int q = 0; q < NS; ++q) { y[q] = y5[q]; k[0][q] = k[6][q]; }
-            if (t >= t1 - 1e-15 * fabs(t1)) done = true;
-        }
-        const double fac = fmin(5.0, fmax(0.2, 0.9 * pow(1.0 / fmax(e, 1e-10), 0.2)));
-        if (!done) h = hh * fac;
-    }
-    if (!done) atomicExch(fail, 1);
-    model_rhs<MODEL>(t1, y, p, k[0]);                 // leave I_ch_k evaluated at the end state
-#pragma unroll
-    for (int s = 0; s < NS; ++s) states[i * NS + s] = y[s];
-#pragma unroll
-    for (int q = 0; q < NP; ++q) params[i * NP + q] = p[q];
-    hstore[i] = h;
+    ode_dp5_step<NS, NP>(BuiltinRhs<MODEL>(), n, t0, t1, rtol, atol, max_steps, states, params, hstore, fail, stim_mask, stim);
 }
 
 // table[node][col] <- facet_field[facet[node]]   (PDE -> ODE, membrane.py:122-139)
@@ -307,11 +252,22 @@ static OdeSet* get_set(knp_ctx* c, int handle) {
     return &it->second[handle];
 }
 
+static void rtc_unload_all(knp_ctx* c);
+
 void ode_destroy_all(knp_ctx* c) {
+    rtc_unload_all(c);
     auto it = g_ode.find(c);
     if (it == g_ode.end()) return;
     for (auto& S : it->second) { hipFree(S.facet); hipFree(S.states); hipFree(S.params); hipFree(S.h); hipFree(S.stim_mask); }
     g_ode.erase(it);
+}
+
+static void rtc_unload_all(knp_ctx* c) {
+    auto it = g_rtc.find(c);
+    if (it == g_rtc.end()) return;
+    hipStreamSynchronize(c->stream);                // no launch of a registered kernel may still be in flight
+    for (auto& R : it->second) hipModuleUnload(R.mod);
+    g_rtc.erase(it);
 }
 
 extern "C" {
@@ -319,7 +275,11 @@ extern "C" {
 int knp_ode_create(knp_ctx* c, int model, int64_t n, const int32_t* facets, int ns, int np, const double* states,
                    const double* params) {
     if (!c) return -1;
-    if (model < 1 || model > 6) { c->err = "ode: unknown device model id"; return -1; }
+    if (model >= ODE_RTC_ID0) {
+        const RtcModel* R = rtc_model(c, model);
+        if (!R) { c->err = "ode: model id not registered on this context (knp_ode_register)"; return -1; }
+        if (ns != R->ns || np != R->np) { c->err = "ode: state / parameter counts differ from the registered kernel's"; return -1; }
+    } else if (model < 1 || model > 6) { c->err = "ode: unknown device model id"; return -1; }
     if (model <= 3 && (ns != 4 || np != 17)) { c->err = "ode: HH models have 4 states and 17 parameters"; return -1; }
     if (model == 4 && (ns != 1 || np != 19)) { c->err = "ode: the glial model has 1 state and 19 parameters"; return -1; }
     if (model == 5 && (ns != 1 || np != 15)) { c->err = "ode: the leak model has 1 state and 15 parameters"; return -1; }
@@ -429,6 +389,18 @@ int knp_ode_step(knp_ctx* c, int handle, double t0, double dt, double rtol, doub
     StimArgs st;
     st.n = S->n_stim;
     for (int e = 0; e < ODE_MAX_STIM; ++e) { st.col[e] = S->stim_col[e]; st.val[e] = S->stim_val[e]; }
+    if (S->model >= ODE_RTC_ID0) {
+        // a registered HIP_RHS kernel: same integrator text, block size, arguments and failure flag as k_ode_step
+        const RtcModel* R = rtc_model(c, S->model);
+        if (!R) { c->err = "ode_step: registered model is gone"; return -1; }
+        int64_t n = S->n;
+        double t1 = t0 + dt;
+        int ms = max_steps;
+        const uint8_t* mask = S->stim_mask;
+        void* args[] = {&n, &t0, &t1, &rtol, &atol, &ms, &S->states, &S->params, &S->h, &S->fail, &mask, &st};
+        HIPCHK(c, hipModuleLaunchKernel(R->fn, g.x, 1, 1, b.x, 1, 1, 0, c->stream, args, nullptr));
+        return 0;
+    }
 #define ODE_LAUNCH(MODEL, NS, NP)                                                                                          \
     hipLaunchKernelGGL((k_ode_step<MODEL, NS, NP>), g, b, 0, c->stream, S->n, t0, t0 + dt, rtol, atol, max_steps, S->states, \
                        S->params, S->h, S->fail, (const uint8_t*)S->stim_mask, st)
@@ -441,6 +413,73 @@ int knp_ode_step(knp_ctx* c, int handle, double t0, double dt, double rtol, doub
 #undef ODE_LAUNCH
     HIPCHK(c, hipGetLastError());
     return 0;
+}
+
+// hipRTC: the translation unit of knpemidg/ode_rtc.py -> a gfx950 code object.  Host only (no context, no device), so it can run on a
+// worker thread while the context is being created.  Same code generation settings as build.py's hipcc line (-O3, and the floating-
+// point contraction clang applies to HIP by default, stated explicitly), so a HIP_RHS identical to a built-in model's right-hand
+// side gives the same instructions.  The log carries the compiler's resource-usage remarks (VGPRs, scratch) and any diagnostics.
+int knp_ode_rtc_compile(const char* src, const char* name, void** code, size_t* size, char* log, size_t logcap) {
+    if (log && logcap) log[0] = 0;
+    if (!src || !code || !size) return -1;
+    *code = nullptr;
+    *size = 0;
+    hiprtcProgram prog = nullptr;
+    if (hiprtcCreateProgram(&prog, src, name ? name : "knp_ode_rtc.cpp", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
+        if (log && logcap) snprintf(log, logcap, "hiprtcCreateProgram failed");
+        return -2;
+    }
+    const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast-honor-pragmas",
+                          "-Rpass-analysis=kernel-resource-usage"};
+    const hiprtcResult rc = hiprtcCompileProgram(prog, (int)(sizeof(opts) / sizeof(opts[0])), opts);
+    size_t nlog = 0;
+    if (log && logcap && hiprtcGetProgramLogSize(prog, &nlog) == HIPRTC_SUCCESS && nlog > 0) {
+        std::string text(nlog, '\0');
+        if (hiprtcGetProgramLog(prog, &text[0]) == HIPRTC_SUCCESS) {
+            const size_t m = strnlen(text.c_str(), nlog) < logcap - 1 ? strnlen(text.c_str(), nlog) : logcap - 1;
+            memcpy(log, text.data(), m);
+            log[m] = 0;
+        }
+    }
+    if (rc != HIPRTC_SUCCESS) {
+        hiprtcDestroyProgram(&prog);
+        return -3;
+    }
+    size_t n = 0;
+    if (hiprtcGetCodeSize(prog, &n) != HIPRTC_SUCCESS || n == 0 || !(*code = malloc(n)) || hiprtcGetCode(prog, (char*)*code) != HIPRTC_SUCCESS) {
+        free(*code);
+        *code = nullptr;
+        hiprtcDestroyProgram(&prog);
+        if (log && logcap) snprintf(log, logcap, "hiprtcGetCode failed");
+        return -4;
+    }
+    *size = n;
+    hiprtcDestroyProgram(&prog);
+    return 0;
+}
+
+void knp_ode_rtc_free(void* code) { free(code); }
+
+// load a code object of knp_ode_rtc_compile on the context's device; the returned id (>= 1000) is a model id for knp_ode_create
+int knp_ode_register(knp_ctx* c, const void* code, size_t size, const char* kernel_name, int ns, int np) {
+    if (!c) return -1;
+    if (!code || !size || !kernel_name) { c->err = "ode_register: no code object / kernel name"; return -1; }
+    if (ns < 1 || ns > 32 || np < 1 || np > 64) { c->err = "ode_register: 1..32 states and 1..64 parameters"; return -1; }
+    (void)size;                                      // hipModuleLoadData reads the ELF's own size
+    HIPCHK(c, hipSetDevice(c->device));
+    RtcModel R;
+    R.ns = ns;
+    R.np = np;
+    HIPCHK(c, hipModuleLoadData(&R.mod, code));
+    const hipError_t e = hipModuleGetFunction(&R.fn, R.mod, kernel_name);
+    if (e != hipSuccess) {
+        hipModuleUnload(R.mod);
+        c->err = std::string("ode_register: kernel ") + kernel_name + " not in the code object: " + hipGetErrorString(e);
+        return -2;
+    }
+    auto& v = g_rtc[c];
+    v.push_back(R);
+    return ODE_RTC_ID0 + (int)v.size() - 1;
 }
 
 }  // extern "C"

@@ -94,6 +94,9 @@ SIGNATURES = {
     "knp_ode_exchange_multi": (C.c_int, [_ctxp, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i64p, C.c_int]),
     "knp_ode_set_stimulus": (C.c_int, [_ctxp, C.c_int, C.c_int, _i32p, _f64p, C.POINTER(C.c_uint8)]),
     "knp_ode_step": (C.c_int, [_ctxp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "knp_ode_rtc_compile": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
+    "knp_ode_rtc_free": (None, [C.c_void_p]),
+    "knp_ode_register": (C.c_int, [_ctxp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_int, C.c_int]),
     "knp_amg_begin": (C.c_int, [_ctxp, C.c_int, C.c_int64, _i32p, _i32p, _i32p]),
     "knp_amg_columns": (C.c_int, [_ctxp, C.c_int, C.c_int]),
     "knp_amg_level": (C.c_int, [_ctxp, C.c_int, C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_double, C.c_int, C.c_double,
@@ -462,6 +465,7 @@ class Device:
         self.nranks = 1
         self.degree = int(degree)
         self._pending = []                 # queued PDE<->ODE column copies: (handle, to_facet, what, col, field, offset)
+        self._rtc_ids = {}                 # kernel name of a registered HIP_RHS model -> its device model id (knp_ode_register)
         self._tmp_slot = -1                # rotating scratch slot of facet_trace results
         self._tmp_gen = [0] * FACET_TMP_SLOTS
         if degree != 1:
@@ -756,6 +760,19 @@ class Device:
     def ode_step(self, handle, t0, dt, rtol=1.0e-8, atol=0.0):
         """Asynchronous (no host round trip); a failed node surfaces as KnpError at the next solve / sync / table read."""
         self._chk(self.lib.knp_ode_step(self.ctx, handle, t0, dt, rtol, atol), "knp_ode_step")
+
+    def ode_register(self, ode):
+        """Device model id (>= 1000) of a model module that carries its right-hand side as HIP_RHS (knpemidg/ode_rtc.py):
+        compiled once per process (or taken from the compile `ode_rtc.prefetch` started), loaded once per context.
+        A compile error raises KnpError with the hipRTC log."""
+        from knpemidg import ode_rtc
+        kernel, ns, np_, code = ode_rtc.compiled(ode)
+        if kernel not in self._rtc_ids:
+            mid = self.lib.knp_ode_register(self.ctx, code, len(code), kernel.encode(), ns, np_)
+            if mid < 0:
+                self._chk(mid, "knp_ode_register")
+            self._rtc_ids[kernel] = mid
+        return self._rtc_ids[kernel]
 
     # -- auxiliary-space AMG (knpemidg/amg.py builds, csrc/amg.hip applies) ------------------
     def amg_interface(self, n_local, peers, lists, uvtx, aptr, asrc):

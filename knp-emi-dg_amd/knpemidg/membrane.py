@@ -123,10 +123,14 @@ class MembraneModel:
 
     # --- device backing: tables live on the GPU, the batched HIP integrator steps them (csrc/ode.hip) ---
     def attach_device(self, dev):
-        """Move the ODE tables to the device if the model has a device implementation (ode.MODEL_ID)."""
-        if getattr(self.ode, "MODEL_ID", None) is None:
-            return False
-        self._handle = dev.ode_create(self.ode.MODEL_ID, self.indices, self._states, self._parameters)
+        """Move the ODE tables to the device if the model has a device implementation: a built-in one (ode.MODEL_ID) or its
+        right-hand side as HIP_RHS, compiled at run time (knpemidg/ode_rtc.py; a compile error raises KnpError)."""
+        model = getattr(self.ode, "MODEL_ID", None)
+        if model is None:
+            if getattr(self.ode, "HIP_RHS", None) is None:
+                return False
+            model = dev.ode_register(self.ode)
+        self._handle = dev.ode_create(model, self.indices, self._states, self._parameters)
         self._dev = dev
         return True
 

@@ -20,7 +20,7 @@ import time
 
 import numpy as np
 
-from knpemidg import _abi
+from knpemidg import _abi, ode_rtc
 from knpemidg.functions import FacetSpace, FacetFunction, DeviceFacetFunction, DeviceFunction
 from knpemidg.membrane import MembraneModel
 from knpemidg.mesh import Constant
@@ -198,6 +198,9 @@ class Solver:
         self.stimulus = stim_params.stimulus
         self.stimulus_locator = stim_params.stimulus_locator
         self.mem_models = []
+        if self.use_device_ode:
+            # HIP_RHS models compile (host only) on a worker thread while the context and the helpers start; attach_device joins
+            ode_rtc.prefetch(odes.values())
         self._ensure_device(membrane_tags=[int(t) for t in odes.keys()])
         for tag, ode in odes.items():
             ode_model = MembraneModel(ode, facet_f=self.surfaces, tag=int(tag), V=self.Q)
