@@ -42,15 +42,17 @@ struct Fields {
 };
 
 // initial guess from the last solutions: nh = number of valid history entries (h1 = previous, h2 = the one before)
-//   nh = 0: h1 <- x;   nh = 1 or order 1: x <- 2 x - h1;   nh = 2 and order 2: x <- 3 x - 3 h1 + h2;   then h2 <- h1, h1 <- x(old)
-__global__ void k_extrapolate_guess(int64_t n, int nh, int order, double* __restrict__ x, double* __restrict__ h1, double* __restrict__ h2) {
+//   nh = 0: h1 <- x;   nh = 1 or order 1: x <- 2 x - h1;   nh = 2 and order 2: x <- 3 x - 3 h1 + h2;   then h2 <- h1 (if keep_h2), h1 <- x(old)
+// Order 1 never reads h2, so it is not written either (4 passes over the field instead of 5); KNP_FUSE_EXTRAP=0 writes it as before.
+__global__ void k_extrapolate_guess(int64_t n, int nh, int order, int keep_h2, double* __restrict__ x, double* __restrict__ h1,
+                                    double* __restrict__ h2) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double xv = x[i];
     const double a = h1[i];
     if (nh >= 2 && order >= 2) x[i] = 3.0 * (xv - a) + h2[i];
     else if (nh >= 1) x[i] = 2.0 * xv - a;
-    h2[i] = a;
+    if (keep_h2) h2[i] = a;
     h1[i] = xv;
 }
 
@@ -72,7 +74,10 @@ static int extrapolate_guess(knp_ctx* c, double* x, double** hist, int* nh, int6
     const bool on = mode == 1 || (mode == 2 && emi) || (mode == 3 && !emi);
     if (!on || c->p.splitting == 2) return 0;
     if (!*hist) HIPCHK(c, hipMalloc((void**)hist, sizeof(double) * 2 * n));
-    hipLaunchKernelGGL(k_extrapolate_guess, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, *nh, order, x, *hist, *hist + n);
+    const char* fe = getenv("KNP_FUSE_EXTRAP");
+    const int keep_h2 = (order >= 2 || (fe && atoi(fe) == 0)) ? 1 : 0;
+    hipLaunchKernelGGL(k_extrapolate_guess, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, *nh, order, keep_h2, x, *hist,
+                       *hist + n);
     HIPCHK(c, hipGetLastError());
     if (*nh < 2) ++*nh;
     return 0;

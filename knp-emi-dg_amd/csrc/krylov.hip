@@ -650,8 +650,8 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_cg_p(VecDims d, const double* __r
 }
 
 // ---- BiCGStab kernels (system = blockIdx.y) ------------------------------------------------------
-// r = b - w ; rhat = r ; p = v = 0 ; partials r.r, b.b
-template <int NV>
+// r = b - w ; rhat = r ; p = v = 0 (ZPV; BiCGStab leaves them alone and runs its first k_bi_p in the FIRST form) ; partials r.r, b.b
+template <int NV, bool ZPV = true>
 __global__ __launch_bounds__(KNP_BLOCK) void k_bi_init(VecDims d, const double* __restrict__ b, const double* __restrict__ w,
                                                        double* __restrict__ r, double* __restrict__ rhat, double* __restrict__ p,
                                                        double* __restrict__ v, double* __restrict__ partial) {
@@ -675,14 +675,16 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_bi_init(VecDims d, const double* 
         }
         stv<NV>(SYS_PTR(r, s), c, rv);
         stv<NV>(SYS_PTR(rhat, s), c, rv);
-        stv<NV>(SYS_PTR(p, s), c, zero);
-        stv<NV>(SYS_PTR(v, s), c, zero);
+        if (ZPV) {
+            stv<NV>(SYS_PTR(p, s), c, zero);
+            stv<NV>(SYS_PTR(v, s), c, zero);
+        }
     }
     write_partials<3>(partial, d.nsys, acc);
 }
 
-// p = r + beta (p - omega v) ; y = Binv p
-template <int NV>
+// p = r + beta (p - omega v) ; y = Binv p.  FIRST (iteration 0, p = v = 0): p = r, and p, v are not read
+template <int NV, bool FIRST = false>
 __global__ __launch_bounds__(KNP_BLOCK) void k_bi_p(VecDims d, const double* __restrict__ scal, const int* __restrict__ status,
                                                     const double* __restrict__ r, const double* __restrict__ v,
                                                     const bjreal* __restrict__ binv, double* __restrict__ p, double* __restrict__ y) {
@@ -693,10 +695,15 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_bi_p(VecDims d, const double* __r
     if (c >= d.nc_owned) return;
     double rv[NV], vv[NV], pv[NV], yv[NV];
     ldv<NV>(SYS_PTR(r, s), c, rv);
-    ldv<NV>(SYS_PTR(v, s), c, vv);
-    ldv<NV>(SYS_PTR(p, s), c, pv);
+    if (FIRST) {
 #pragma unroll
-    for (int a = 0; a < NV; ++a) pv[a] = rv[a] + beta * (pv[a] - omega * vv[a]);
+        for (int a = 0; a < NV; ++a) pv[a] = rv[a] + 0.0;        // beta = 0, omega = 1 after OP_BI_INIT: + 0.0 keeps the sign of a zero r as before
+    } else {
+        ldv<NV>(SYS_PTR(v, s), c, vv);
+        ldv<NV>(SYS_PTR(p, s), c, pv);
+#pragma unroll
+        for (int a = 0; a < NV; ++a) pv[a] = rv[a] + beta * (pv[a] - omega * vv[a]);
+    }
     block_matvec<NV>(bj_block<NV>(d, binv, s, c), 0, pv, yv);
     stv<NV>(SYS_PTR(p, s), c, pv);
     stv<NV>(SYS_PTR(y, s), c, yv);
@@ -915,12 +922,21 @@ static int poll_status(knp_ctx* c, int nsys, int* host_status) {
 // How many iterations to enqueue before the next look at the device's convergence flag.  Kernels of iterations past
 // convergence are no-ops only for the vector updates -- operator applies and V-cycles still run -- so a fixed chunk of
 // 25 wastes up to a whole solve's worth of work (17 useful + 8 wasted iterations at r=2).  Iteration counts are stable
-// from one time step to the next: enqueue (previous count - 1) iterations without looking, then look every 2.
+// from one time step to the next: enqueue (previous count - 1) iterations without looking, then look after every iteration.
+// A look costs one status read and the host's re-enqueue (about 30 us of idle GPU); an iteration enqueued past convergence
+// costs its applies and V-cycles (r=2: about 0.75 ms for KNP, 0.2 ms for EMI), so past the prediction looking every time wins
+// (profiles/r05_poll_tail.txt).  KNP_POLL_TAIL=0 restores the previous rule (every 2, every 1 for 1-2 iteration solves).
+static int poll_tail() {
+    const char* e = getenv("KNP_POLL_TAIL");               // read per call: tests switch it inside one process
+    return e ? atoi(e) : 1;
+}
 static inline int next_chunk(int it, int maxit, int check_every, int predicted) {
     int chunk = check_every;
     if (predicted > 0) {
         const int ahead = predicted - 1 - it;
-        chunk = ahead > 0 ? (ahead < 4 * check_every ? ahead : 4 * check_every) : (predicted <= 2 ? 1 : 2);   // 1-2 iteration solves: look every time
+        const int tail = poll_tail();
+        chunk = ahead > 0 ? (ahead < 4 * check_every ? ahead : 4 * check_every)
+                          : (tail > 0 ? tail : (predicted <= 2 ? 1 : 2));   // old rule: 1-2 iteration solves look every time
     }
     return (maxit - it < chunk) ? (maxit - it) : chunk;
 }
@@ -1194,6 +1210,13 @@ static int knp_coarse_correction(knp_ctx* c, const VecDims& d, const double* in,
     return 0;
 }
 
+// BiCGStab's first iteration with p = v = 0 folded in: k_bi_init does not write the two zero vectors and the first k_bi_p does not
+// read them (same bits: r + beta (0 - omega 0) = r).  KNP_FUSE_BI_FIRST=0: zeros written and read as before.
+static bool bi_first_form() {
+    const char* e = getenv("KNP_FUSE_BI_FIRST");            // read per call: tests switch it inside one process
+    return !(e && atoi(e) == 0);
+}
+
 template <int NV>
 static int bicgstab_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, int maxit, int min_it, int check_every,
                          int* niter, double* res) {
@@ -1203,7 +1226,9 @@ static int bicgstab_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, i
     const dim3 g((unsigned)grid_for(c->m.nc_owned), (unsigned)ns), b(KNP_BLOCK);
     int rc;
     if ((rc = dist_apply(c, 1, kv.x, kv.coef, kv.w))) return rc;
-    hipLaunchKernelGGL(k_bi_init<NV>, g, b, 0, c->stream, d, kv.b, kv.w, kv.r, kv.rhat, kv.p, kv.v, c->partial);
+    const bool first_form = bi_first_form();
+    if (first_form) hipLaunchKernelGGL((k_bi_init<NV, false>), g, b, 0, c->stream, d, kv.b, kv.w, kv.r, kv.rhat, kv.p, kv.v, c->partial);
+    else hipLaunchKernelGGL((k_bi_init<NV, true>), g, b, 0, c->stream, d, kv.b, kv.w, kv.r, kv.rhat, kv.p, kv.v, c->partial);
     if ((rc = finalize(c, OP_BI_INIT, ns, 3, rtol, atol, min_it, 0.0, d.d8))) return rc;
     int hs[2 * KNP_MAX_SYS];
     auto all_done = [&]() { for (int s = 0; s < ns; ++s) if (!hs[2 * s]) return false; return true; };
@@ -1212,7 +1237,10 @@ static int bicgstab_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, i
     while (!all_done() && it < maxit) {
         const int chunk = next_chunk(it, maxit, check_every, c->last_it_knp);
         for (int k = 0; k < chunk; ++k) {
-            hipLaunchKernelGGL(k_bi_p<NV>, g, b, 0, c->stream, d, c->scal, c->status, kv.r, kv.v, kv.binv, kv.p, kv.y);
+            if (first_form && it + k == 0)
+                hipLaunchKernelGGL((k_bi_p<NV, true>), g, b, 0, c->stream, d, c->scal, c->status, kv.r, kv.v, kv.binv, kv.p, kv.y);
+            else
+                hipLaunchKernelGGL((k_bi_p<NV, false>), g, b, 0, c->stream, d, c->scal, c->status, kv.r, kv.v, kv.binv, kv.p, kv.y);
             const bool hyb = kv.bj_lmax > 0.0 && knp_hybrid();
             const double ct = hyb ? 1.0 / bj_theta<false>(kv) : 0.0;
             const bool fuse = (int)c->amg.size() > 1 && fuse_restrict(c, kv, c->amg[1], ns);

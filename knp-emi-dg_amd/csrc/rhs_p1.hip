@@ -47,6 +47,16 @@ template <int DEG> struct FacetRule<2, DEG> {       // degree 4 and 5 both need 
     }
 };
 
+// volume + Gram matrix of a geometry-class record ([0] vol, [1..10] upper triangle of G; 3D only)
+template <int D> __device__ __forceinline__ void class_gram(const double* __restrict__ rec, CellGeom<D>& K) {
+    K.vol = rec[0];
+    int q = 1;
+#pragma unroll
+    for (int a = 0; a <= D; ++a)
+#pragma unroll
+        for (int b = a; b <= D; ++b) { K.G[a][b] = rec[q]; K.G[b][a] = rec[q]; ++q; }
+}
+
 struct IonArgs {
     int n;                    // total species (last eliminated)
     double z[KNP_MAX_IONS];
@@ -76,8 +86,9 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_kappa(MeshDev m, const double* __
 // ------------------------------------------------------------------------------------------
 // L_emi
 // ------------------------------------------------------------------------------------------
-template <int D, int I>
-__device__ __forceinline__ void emi_rhs_facet(const MeshDev& m, const CellGeom<D>& K, int64_t c, const int* nb,
+template <int D, int I, bool CLS>
+__device__ __forceinline__ void emi_rhs_facet(const MeshDev& m, const CellGeom<D>& K, const double* __restrict__ rec,
+                                              const double* __restrict__ ext, int64_t c, const int* nb,
                                               uint32_t flags, const double* __restrict__ cc,
                                               const double* __restrict__ celim, const double* __restrict__ Dall,
                                               const double* __restrict__ phiM, const double* __restrict__ Ich,
@@ -98,16 +109,30 @@ __device__ __forceinline__ void emi_rhs_facet(const MeshDev& m, const CellGeom<D
             g -= It / C_phi;
         }
         const double sgn = ((fb >> 4) & 1u) ? -1.0 : 1.0;           // JUMP(v) = v_i - v_e
-        const double w = sgn * C_phi * g * fast_sqrt(K.G[I][I]) * K.vol;   // area / D = sqrt(G_ii) vol
+        const double sq = CLS ? rec[11 + 6 * I + 4] : fast_sqrt(K.G[I][I]);
+        const double w = sgn * C_phi * g * sq * K.vol;   // area / D = sqrt(G_ii) vol
 #pragma unroll
         for (int mm = 0; mm < D; ++mm) b[mm + (mm >= I)] += w;
         return;
     }
-    double Xo[D], L[NV];
-    load_vertex<D>(m.coords, m.cells[Kp * NV + j], Xo);
-    apex_bary<D>(K, Xo, L);
-    const double rLi = fast_rcp(L[I]);
-    const double gr = K.G[I][I] * rLi;
+    // neighbour's gradient through the own basis: s_nb = x'_apex gr + sum_m x'_m e_m (cell_geom.hpp); class path: both from cls_ext
+    double gr, e[D];
+    if (CLS) {
+        gr = ext[8 * I];
+#pragma unroll
+        for (int mm = 0; mm < D; ++mm) e[mm] = ext[8 * I + 1 + mm];
+    } else {
+        double Xo[D], L[NV];
+        load_vertex<D>(m.coords, m.cells[Kp * NV + j], Xo);
+        apex_bary<D>(K, Xo, L);
+        const double rLi = fast_rcp(L[I]);
+        gr = K.G[I][I] * rLi;
+#pragma unroll
+        for (int mm = 0; mm < D; ++mm) {
+            const int a = mm + (mm >= I);
+            e[mm] = fma(-L[a], gr, K.G[a][I]);
+        }
+    }
     double flux = 0.0;
     for (int i = 0; i < ia.n; ++i) {
         const double* src = (i < ia.n - 1) ? cc + (int64_t)i * m.nc * NV : celim;
@@ -119,10 +144,7 @@ __device__ __forceinline__ void emi_rhs_facet(const MeshDev& m, const CellGeom<D
         for (int a = 0; a < NV; ++a) s_own = fma(cv[a], K.G[a][I], s_own);
         double s_nb = pick_apex<D>(cn, j) * gr;
 #pragma unroll
-        for (int mm = 0; mm < D; ++mm) {
-            const int a = mm + (mm >= I);
-            s_nb = fma(pick_facet<D>(cn, mm, j), fma(-L[a], gr, K.G[a][I]), s_nb);
-        }
+        for (int mm = 0; mm < D; ++mm) s_nb = fma(pick_facet<D>(cn, mm, j), e[mm], s_nb);
         flux += F * ia.z[i] * 0.5 * (Dall[(int64_t)i * m.nc + c] * s_own + Dall[(int64_t)i * m.nc + Kp] * s_nb);
     }
     // area/D * (grad c . n) = -vol (grad c . g_i)
@@ -131,7 +153,11 @@ __device__ __forceinline__ void emi_rhs_facet(const MeshDev& m, const CellGeom<D
     for (int mm = 0; mm < D; ++mm) b[mm + (mm >= I)] += w;
 }
 
-template <int D>
+// CLS (structured 3D meshes with geometry classes, rhs_cls below): volume, Gram matrix and the neighbour
+// coefficients from the cell's class record instead of 4 + 4 gathered vertices and a Jacobian per cell (KNP_RHS_CLS=0: coordinates).
+// Bytes it must move per cell (3 ions, Na eliminated): class id 2 + neighbours 16 + facet flags 4 + c_K, c_Cl, c_Na 96 + D 24 + b 32
+// = 174 B (neighbours' c and D come from L2: 85 % of them sit in the same 256-cell Morton block).
+template <int D, bool CLS>
 __global__ __launch_bounds__(KNP_BLOCK) void k_emi_rhs(MeshDev m, const double* __restrict__ cc,
                                                        const double* __restrict__ celim, const double* __restrict__ Dall,
                                                        const double* __restrict__ phiM, const double* __restrict__ Ich,
@@ -140,32 +166,53 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_emi_rhs(MeshDev m, const double* 
     constexpr int NV = D + 1;
     const int64_t c = (int64_t)blockIdx.x * KNP_BLOCK + threadIdx.x;
     if (c >= m.nc_owned) return;
-    int verts[NV], nb[NV];
-    load_cell_ints<D>(m.cells, c, verts);
+    int nb[NV];
     load_cell_ints<D>(m.nbr, c, nb);
     const uint32_t flags = m.fflag[c];
     CellGeom<D> K;
-    load_cell_geometry<D>(m, verts, K);
+    const double* rec = nullptr;
+    const double* ext = nullptr;
+    if (CLS) {
+        const unsigned q = m.cls[c];
+        rec = m.cls_table + (size_t)q * KNP_CLS_STRIDE;
+        ext = m.cls_ext + (size_t)q * KNP_CLS_EXT;
+        class_gram<D>(rec, K);
+    } else {
+        int verts[NV];
+        load_cell_ints<D>(m.cells, c, verts);
+        load_cell_geometry<D>(m, verts, K);
+    }
     double b[NV];
 #pragma unroll
     for (int a = 0; a < NV; ++a) b[a] = 0.0;
     for (int i = 0; i < ia.n; ++i) {
-        double cv[NV], gc[D];
+        double cv[NV];
         load_nodal<D>((i < ia.n - 1) ? cc + (int64_t)i * m.nc * NV : celim, c, cv);
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            gc[k] = 0.0;
-#pragma unroll
-            for (int a = 0; a < NV; ++a) gc[k] += cv[a] * K.g[a][k];
-        }
         const double f = -F * ia.z[i] * Dall[(int64_t)i * m.nc + c] * K.vol;
+        if (CLS) {                                  // grad c . g_a = sum_b c_b G_ab
 #pragma unroll
-        for (int a = 0; a < NV; ++a) b[a] += f * dotD<D>(gc, K.g[a]);
+            for (int a = 0; a < NV; ++a) {
+                double sa = 0.0;
+#pragma unroll
+                for (int bb = 0; bb < NV; ++bb) sa = fma(K.G[a][bb], cv[bb], sa);
+                b[a] += f * sa;
+            }
+        } else {
+            double gc[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                gc[k] = 0.0;
+#pragma unroll
+                for (int a = 0; a < NV; ++a) gc[k] += cv[a] * K.g[a][k];
+            }
+#pragma unroll
+            for (int a = 0; a < NV; ++a) b[a] += f * dotD<D>(gc, K.g[a]);
+        }
     }
-    emi_rhs_facet<D, 0>(m, K, c, nb, flags, cc, celim, Dall, phiM, Ich, ia, F, C_phi, splitting, b);
-    emi_rhs_facet<D, 1>(m, K, c, nb, flags, cc, celim, Dall, phiM, Ich, ia, F, C_phi, splitting, b);
-    emi_rhs_facet<D, 2>(m, K, c, nb, flags, cc, celim, Dall, phiM, Ich, ia, F, C_phi, splitting, b);
-    if (D == 3) emi_rhs_facet<D, (D == 3 ? 3 : 0)>(m, K, c, nb, flags, cc, celim, Dall, phiM, Ich, ia, F, C_phi, splitting, b);
+    emi_rhs_facet<D, 0, CLS>(m, K, rec, ext, c, nb, flags, cc, celim, Dall, phiM, Ich, ia, F, C_phi, splitting, b);
+    emi_rhs_facet<D, 1, CLS>(m, K, rec, ext, c, nb, flags, cc, celim, Dall, phiM, Ich, ia, F, C_phi, splitting, b);
+    emi_rhs_facet<D, 2, CLS>(m, K, rec, ext, c, nb, flags, cc, celim, Dall, phiM, Ich, ia, F, C_phi, splitting, b);
+    if (D == 3) emi_rhs_facet<D, (D == 3 ? 3 : 0), CLS>(m, K, rec, ext, c, nb, flags, cc, celim, Dall, phiM, Ich, ia, F, C_phi, splitting, b);
     if (extra) {
         double ev[NV];
         load_nodal<D>(extra, c, ev);
@@ -185,8 +232,8 @@ struct KnpRhsArgs {
     const double* extra;      // [n_sys][nc*nd] or null
 };
 
-template <int D, int I>
-__device__ __forceinline__ void knp_rhs_facet(const MeshDev& m, const CellGeom<D>& K, int64_t c, const int* nb,
+template <int D, int I, bool CLS>
+__device__ __forceinline__ void knp_rhs_facet(const MeshDev& m, const CellGeom<D>& K, const double* __restrict__ rec, int64_t c, const int* nb,
                                               uint32_t flags, int k, double zk, double Dk, const double* ck,
                                               const double* asum, const double* pv, const double* __restrict__ phi,
                                               const double* __restrict__ phiM, const double* __restrict__ Ich,
@@ -198,7 +245,7 @@ __device__ __forceinline__ void knp_rhs_facet(const MeshDev& m, const CellGeom<D
     const int j = (int)(fb & 3u);
     const int64_t Kp = nb[I];
     const bool is_e = (fb >> 4) & 1u;
-    const double area = fast_sqrt(K.G[I][I]) * (double)D * K.vol;
+    const double area = (CLS ? rec[11 + 6 * I + 4] : fast_sqrt(K.G[I][I])) * (double)D * K.vol;
     const int64_t f = m.cfacet[c * NV + I];
     const double pM = phiM[f];
     const double Ik = Ich[(int64_t)k * m.nf + f];
@@ -251,7 +298,10 @@ __device__ __forceinline__ void knp_rhs_facet(const MeshDev& m, const CellGeom<D
     }
 }
 
-template <int D>
+// CLS: volume and facet areas from the class record (see k_emi_rhs); the Gram matrix is not needed.  Bytes it must move per
+// (cell, solved species): class id 2 + facet flags 4 + c_prev 32 + b 32 = 70 B, i.e. 140 B per cell for K and Cl; the 2.4 % of cells
+// with a membrane facet also read neighbours, c, phi, D, phi_M and I_ch.
+template <int D, bool CLS>
 __global__ __launch_bounds__(KNP_BLOCK) void k_knp_rhs(MeshDev m, const double* __restrict__ cc,
                                                        const double* __restrict__ cprev, const double* __restrict__ celim,
                                                        const double* __restrict__ phi, const double* __restrict__ Dall,
@@ -262,12 +312,18 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_knp_rhs(MeshDev m, const double* 
     const int64_t c = (int64_t)blockIdx.x * KNP_BLOCK + threadIdx.x;
     const int k = blockIdx.y;
     if (c >= m.nc_owned) return;
-    int verts[NV], nb[NV];
-    load_cell_ints<D>(m.cells, c, verts);
-    load_cell_ints<D>(m.nbr, c, nb);
+    int nb[NV];
     const uint32_t flags = m.fflag[c];
     CellGeom<D> K;
-    load_cell_geometry<D>(m, verts, K);
+    const double* rec = nullptr;
+    if (CLS) {
+        rec = m.cls_table + (size_t)m.cls[c] * KNP_CLS_STRIDE;
+        K.vol = rec[0];
+    } else {
+        int verts[NV];
+        load_cell_ints<D>(m.cells, c, verts);
+        load_cell_geometry<D>(m, verts, K);
+    }
     double cp[NV], b[NV], sp = 0.0;
     load_nodal<D>(cprev + (int64_t)k * m.nc * NV, c, cp);
 #pragma unroll
@@ -281,6 +337,7 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_knp_rhs(MeshDev m, const double* 
 #pragma unroll
     for (int i = 0; i < NV; ++i) has_mem |= (((flags >> (8 * i + 2)) & 3u) == FK_MEMBRANE);
     if (has_mem) {
+        load_cell_ints<D>(m.nbr, c, nb);
         double ck[NV], asum[NV], pv[NV];
         load_nodal<D>(cc + (int64_t)k * m.nc * NV, c, ck);
         load_nodal<D>(phi, c, pv);
@@ -294,10 +351,10 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_knp_rhs(MeshDev m, const double* 
             for (int a = 0; a < NV; ++a) asum[a] += f * cv[a];
         }
         const double zk = ia.z[k], Dk = Dall[(int64_t)k * m.nc + c];
-        knp_rhs_facet<D, 0>(m, K, c, nb, flags, k, zk, Dk, ck, asum, pv, phi, phiM, Ich, ia, ra, b);
-        knp_rhs_facet<D, 1>(m, K, c, nb, flags, k, zk, Dk, ck, asum, pv, phi, phiM, Ich, ia, ra, b);
-        knp_rhs_facet<D, 2>(m, K, c, nb, flags, k, zk, Dk, ck, asum, pv, phi, phiM, Ich, ia, ra, b);
-        if (D == 3) knp_rhs_facet<D, (D == 3 ? 3 : 0)>(m, K, c, nb, flags, k, zk, Dk, ck, asum, pv, phi, phiM, Ich, ia, ra, b);
+        knp_rhs_facet<D, 0, CLS>(m, K, rec, c, nb, flags, k, zk, Dk, ck, asum, pv, phi, phiM, Ich, ia, ra, b);
+        knp_rhs_facet<D, 1, CLS>(m, K, rec, c, nb, flags, k, zk, Dk, ck, asum, pv, phi, phiM, Ich, ia, ra, b);
+        knp_rhs_facet<D, 2, CLS>(m, K, rec, c, nb, flags, k, zk, Dk, ck, asum, pv, phi, phiM, Ich, ia, ra, b);
+        if (D == 3) knp_rhs_facet<D, (D == 3 ? 3 : 0), CLS>(m, K, rec, c, nb, flags, k, zk, Dk, ck, asum, pv, phi, phiM, Ich, ia, ra, b);
     }
     if (ra.extra) {
         double ev[NV];
@@ -419,16 +476,39 @@ static IonArgs ion_args(knp_ctx* c) {
         HIPCHK(c, hipGetLastError());                                                            \
     } while (0)
 
+// DISPATCH_DIM for the kernels with a CLS flag: the coordinate path
+#define DISPATCH_DIM2(c, KERN, grid, ...)                                                        \
+    do {                                                                                         \
+        if ((c)->m.dim == 3) hipLaunchKernelGGL((KERN<3, false>), grid, dim3(KNP_BLOCK), 0, (c)->stream, __VA_ARGS__); \
+        else hipLaunchKernelGGL((KERN<2, false>), grid, dim3(KNP_BLOCK), 0, (c)->stream, __VA_ARGS__); \
+        HIPCHK(c, hipGetLastError());                                                            \
+    } while (0)
+
 int launch_kappa(knp_ctx* c, const double* cc, const double* celim, double* kappa) {
     if (c->degree != 1) return tab_kappa(c, cc, celim, kappa);
     DISPATCH_DIM(c, k_kappa, dim3((unsigned)grid_for(c->m.nc)), c->m, cc, celim, c->D, kappa, ion_args(c), c->p.F, c->p.psi);
     return 0;
 }
 
+// the right-hand sides take the cell geometry from the class records on every 3D mesh that has them (the meshes of the ring-staged
+// applies; the records are read through the cache, so unlike ring_usable there is no limit on the number of classes).
+// KNP_RHS_CLS=0: always from vertex coordinates (read per call, tests switch it inside one process)
+static bool rhs_cls(const knp_ctx* c) {
+    const char* e = getenv("KNP_RHS_CLS");
+    return !(e && atoi(e) == 0) && c->m.dim == 3 && c->m.cls && c->m.cls_table && c->m.cls_ext;
+}
+
 int launch_emi_rhs(knp_ctx* c, const double* cc, const double* celim, const double* phiM, const double* Ich, double* b) {
     if (c->degree != 1) return tab_emi_rhs(c, cc, celim, phiM, Ich, b);
-    DISPATCH_DIM(c, k_emi_rhs, dim3((unsigned)grid_for(c->m.nc_owned)), c->m, cc, celim, c->D, phiM, Ich, b,
-                 ion_args(c), c->p.F, c->p.C_phi, c->p.splitting, (const double*)c->extra_emi);
+    const dim3 g((unsigned)grid_for(c->m.nc_owned));
+    if (rhs_cls(c)) {
+        hipLaunchKernelGGL((k_emi_rhs<3, true>), g, dim3(KNP_BLOCK), 0, c->stream, c->m, cc, celim, c->D, phiM, Ich, b,
+                           ion_args(c), c->p.F, c->p.C_phi, c->p.splitting, (const double*)c->extra_emi);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }
+    DISPATCH_DIM2(c, k_emi_rhs, g, c->m, cc, celim, c->D, phiM, Ich, b,
+                  ion_args(c), c->p.F, c->p.C_phi, c->p.splitting, (const double*)c->extra_emi);
     return 0;
 }
 
@@ -436,8 +516,14 @@ int launch_knp_rhs(knp_ctx* c, const double* cc, const double* cprev, const doub
                    const double* phiM, const double* Ich, double* b) {
     if (c->degree != 1) return tab_knp_rhs(c, cc, cprev, celim, phi, phiM, Ich, b);
     KnpRhsArgs ra{c->p.F, c->p.C_M, c->p.dt, c->p.splitting, (const double*)c->mms_C, (const double*)c->extra_knp};
-    DISPATCH_DIM(c, k_knp_rhs, dim3((unsigned)grid_for(c->m.nc_owned), (unsigned)c->p.n_sys), c->m, cc, cprev, celim, phi,
-                 c->D, phiM, Ich, (const double*)c->fsrc, b, ion_args(c), ra);
+    const dim3 g((unsigned)grid_for(c->m.nc_owned), (unsigned)c->p.n_sys);
+    if (rhs_cls(c)) {
+        hipLaunchKernelGGL((k_knp_rhs<3, true>), g, dim3(KNP_BLOCK), 0, c->stream, c->m, cc, cprev, celim, phi,
+                           c->D, phiM, Ich, (const double*)c->fsrc, b, ion_args(c), ra);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }
+    DISPATCH_DIM2(c, k_knp_rhs, g, c->m, cc, cprev, celim, phi, c->D, phiM, Ich, (const double*)c->fsrc, b, ion_args(c), ra);
     return 0;
 }
 
