@@ -1,0 +1,38 @@
+#!/usr/bin/python3
+"""The run_3D.py configuration with the traces of the reference's figure script recorded on the device instead of per-step field
+output (reference: examples/idealized-geometries/make_figures_3D.py:179-194): phi and the concentrations at one intracellular and
+one extracellular point, the area-averaged phi_M / E_k / I_ch_k over the membrane facets of a small box, and the subdomain integrals.
+Writes results/data/3D/timeseries.h5 and no fields.
+
+    python run_3D_traces.py [resolution] [Tstop]
+"""
+import sys
+
+import numpy as np
+
+from idealized_common import make_solver, solver_parameters, Constant
+
+UM = 1.0e-6          # the figure script works in micrometres, the mesh is in metres
+
+if __name__ == "__main__":
+    resolution = int(sys.argv[1]) if len(sys.argv) > 1 else 0
+    Tstop = float(sys.argv[2]) if len(sys.argv) > 2 else 2.0e-2
+    S = make_solver(dim=3, resolution=resolution, verbose=False)
+    x_i, x_e = (25.0, 0.3, 0.3), (25.0, 0.45, 0.65)                    # make_figures_3D.py:181-183
+    x_M = np.array([25.6, 0.34, 0.4])                                  # make_figures_3D.py:179, box of :95-97
+    eps = 1.0e-6                                                       # the membrane plane z = 0.4 is a rounded grid coordinate
+    box = ((x_M - [0.0, 0.01, 0.01]) * UM, (x_M + [0.5, eps, eps]) * UM)
+    rec = S.record(points=np.array([x_i, x_e]) * UM, membrane_sets=[box], regions=True)
+    t = Constant(0.0)
+    S.solve_system_active(Tstop, t, solver_parameters(3, resolution), filename="results/data/3D/", save_fields=False,
+                          save_solver_stats=False)
+    phi_M = 1.0e3 * rec.membrane["phi_M"][:, 0]
+    k = int(np.argmax(phi_M))
+    print("steps %d  membrane set of %d facets  phi_M peak %.3f mV at t = %.2f ms  (E_K %.2f mV, E_Na %.2f mV there)"
+          % (len(rec.t), len(rec.set_facets[0]), phi_M[k], 1.0e3 * rec.t[k], 1.0e3 * rec.membrane["E_K"][k, 0],
+             1.0e3 * rec.membrane["E_Na"][k, 0]))
+    print("intracellular probe: K %.4f -> %.4f mM, extracellular probe: K %.4f -> %.4f mM"
+          % (rec.points["K"][0, 0], rec.points["K"][-1, 0], rec.points["K"][0, 1], rec.points["K"][-1, 1]))
+    busy = S.emi_solve_timer + S.knp_solve_timer + S.emi_ass_timer + S.knp_ass_timer + S.ode_solve_timer
+    print("EMI iterations %.2f per step, KNP %.2f, %.2f ms per step (solve, assembly and ODE timers); timeseries written to "
+          "results/data/3D/timeseries.h5" % (np.mean(S.emi_niter), np.mean([max(n) for n in S.knp_niter]), 1.0e3 * busy / len(rec.t)))

@@ -245,6 +245,35 @@ int knp_max_abs_diff(knp_ctx* ctx, int field_a, int field_b, double* out);
 #define KNP_FACET_TMP_SLOTS 4
 int knp_facet_trace(knp_ctx* ctx, int field, int species, int side, int slot);
 
+/* ---- time-series recorder ------------------------------------------------------------------------
+ * Samples probe, membrane and region quantities on the device, so that a run without field output still yields the traces the
+ * reference's figure scripts compute from results.h5 (examples/idealized-geometries/make_figures_3D.py:28-168: point values of phi
+ * and every concentration, the area-averaged phi_M / E_K / E_Na over a few membrane facets, subdomain integrals).  One sample is one
+ * row of knp_rec_channels doubles plus its time in a device buffer of `capacity` rows; the row counter lives on the device.
+ * Row layout:
+ *   per probe   : phi, the n_sys solved concentrations, the eliminated one       = sum_a w[a] u[cell*nd + a]
+ *   per set     : weighted mean of PHI_M, of E[k] and of I_CH[k], k < n_ions      (1 + 2 n_ions values)
+ *   per region  : integral of c_k dx, k < n_ions (eliminated ion last), then the volume mean of phi; exact nodal weights
+ *                 (P1: vol/(d+1); P2 triangle: 0 on vertices, 1/3 on edge nodes; P2 tetrahedron: -1/20 and 1/5)
+ * Sums run in a fixed order and without floating-point atomics: the same inputs give the same bits.
+ *  knp_rec_create  : point_cell[n_points] containing cell and point_w[n_points][nd] basis values at the point (P2: local dof order
+ *                    of knp_set_tabulation); set s = facets set_facet[set_ptr[s] .. set_ptr[s+1]) with weights set_w (summing to 1
+ *                    per set; facet ids are the caller's); region[nc] in [0, n_regions) or 255 = not counted, n_regions <= 16,
+ *                    vol[nc] cell volumes (ghost cells are never counted).  Cell-indexed arguments are in DEVICE cell order.  One
+ *                    recorder per context: a second call replaces the first.  A cell outside [0, nc_owned), a facet that is not a
+ *                    membrane facet, an empty set or a region id >= n_regions other than 255 fails with a message and launches nothing.
+ *  knp_rec_sample  : appends one row for time t; asynchronous, on the context's stream; -5 when `capacity` rows wait to be read
+ *  knp_rec_read    : synchronises, copies the waiting rows (rows_out[capacity][channels], t_out[capacity]; *n_rows of them are
+ *                    valid) in one device-to-host transfer and empties the buffer
+ *  knp_rec_channels: doubles per row (< 0 without a recorder) */
+int knp_rec_create(knp_ctx* ctx, int64_t capacity, int64_t n_points, const int32_t* point_cell, const double* point_w,
+                   int64_t n_sets, const int64_t* set_ptr, const int32_t* set_facet, const double* set_w,
+                   int n_regions, const uint8_t* region, const double* vol);
+int knp_rec_sample(knp_ctx* ctx, double t);
+int knp_rec_read(knp_ctx* ctx, int64_t* n_rows, double* t_out, double* rows_out);
+int64_t knp_rec_channels(knp_ctx* ctx);
+int knp_rec_destroy(knp_ctx* ctx);
+
 /* ---- membrane ODEs: batched device integrator replacing the per-facet LSODA loop of
  * MembraneModel.step_lsoda (membrane.py:84-119).  model: 1 = Hodgkin-Huxley + stimulus (examples/idealized-geometries/mm_hh.py),
  * 2 = without (mm_hh_no_stim.py), 3 = EMIx neuron (examples/emix-simulations/mm_hh.py), 4 = EMIx glia (mm_glial.py), 5 = passive

@@ -255,6 +255,8 @@ int knp_ctx_create(knp_ctx** out, int device, int dim, int degree, int n_ions, i
 
     stamp("facet flags, neighbours");
     c->h_fflag = fflag;
+    c->h_mf_mask.assign((size_t)nf, 0);
+    for (size_t i = 0; i < mf.size(); i += 6) c->h_mf_mask[(size_t)mf[i + 4]] = 1;
     MeshDev& m = c->m;
     m.dim = dim; m.nv = nv; m.nc = nc; m.nc_owned = nc_owned; m.nf = nf; m.nmf = (int64_t)mf.size() / 6;
     m.c_begin = 0; m.c_end = nc_owned; m.n_interior = nc_owned;
@@ -381,6 +383,7 @@ void knp_ctx_destroy(knp_ctx* c) {
     for (auto ev : c->aux_events) hipEventDestroy(ev);
     if (c->fork_event) hipEventDestroy(c->fork_event);
     ode_destroy_all(c);
+    rec_destroy(c);
     tab_free(c);
     Fields* fl = g_fields[c];
     if (fl) {

@@ -97,6 +97,7 @@ struct knp_ctx {
     // material (distinct D tuple, any count up to 65535; empty = too many), flag bytes (facet kinds)
     std::vector<uint16_t> h_cls, h_mat;
     std::vector<uint32_t> h_fflag;
+    std::vector<uint8_t> h_mf_mask;  // [nf] 1 on membrane facets: what knp_rec_create checks the caller's facet sets against
     int* halo_ctr = nullptr;       // [2 operators][2 sets][64 queues] block counters of the persistent halo-staged applies (apply_p1.hip)
     int halo_flip[2] = {0, 0};
     double* rho = nullptr;         // [nc]
@@ -244,4 +245,5 @@ int allreduce_sum_host(knp_ctx* c, double* host_values, int n);    // sum of n <
 // (same bits on every owner: added in rank order).  On the context's stream; 2 messages per peer (comm.hip)
 int interface_accumulate(knp_ctx* c, double* v, int64_t n, int ncol);
 int max_abs_diff(knp_ctx* c, const double* a, const double* b, int nsys, double* out);
+void rec_destroy(knp_ctx* c);       // record.hip: frees the context's time-series recorder, if any
 int ode_check_failed(knp_ctx* c);   // ode.hip: reads and clears the ODE failure flag (stream idle); sets c->err

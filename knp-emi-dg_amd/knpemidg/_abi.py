@@ -116,6 +116,11 @@ SIGNATURES = {
     "knp_amg_clear": (C.c_int, [_ctxp, C.c_int]),
     "knp_amg_interface": (C.c_int, [_ctxp, C.c_int64, C.c_int, _i32p, _i64p, _i32p, C.c_int64, _i32p, _i32p, _i32p]),
     "knp_amg_dist0": (C.c_int, [_ctxp, C.c_int]),
+    "knp_rec_create": (C.c_int, [_ctxp, C.c_int64, C.c_int64, _i32p, _f64p, C.c_int64, _i64p, _i32p, _f64p, C.c_int, C.POINTER(C.c_uint8), _f64p]),
+    "knp_rec_sample": (C.c_int, [_ctxp, C.c_double]),
+    "knp_rec_read": (C.c_int, [_ctxp, _i64p, _f64p, _f64p]),
+    "knp_rec_channels": (C.c_int64, [_ctxp]),
+    "knp_rec_destroy": (C.c_int, [_ctxp]),
 }
 
 _lib = None
@@ -849,6 +854,43 @@ class Device:
     def halo_exchange(self, field):
         self._chk(self.lib.knp_halo_exchange(self.ctx, field), "knp_halo_exchange")
 
+    # -- time-series recorder (csrc/record.hip; knpemidg/recorder.py prepares the tables) ----------
+    def rec_create(self, capacity, point_cell, point_w, set_ptr, set_facet, set_w, n_regions, region, vol):
+        """Cell-indexed arguments in the CALLER's cell order: point_cell [n_points], region uint8 [nc] (255 = not counted), vol [nc].
+        Returns the number of channels of a row."""
+        pc = np.ascontiguousarray(self.cell_rank[np.asarray(point_cell, dtype=np.int64)], dtype=np.int32)
+        pw = np.ascontiguousarray(np.asarray(point_w, dtype=np.float64).reshape(len(pc), self.nd))
+        sp = np.ascontiguousarray(set_ptr, dtype=np.int64)
+        sf = np.ascontiguousarray(set_facet, dtype=np.int32)
+        sw = np.ascontiguousarray(set_w, dtype=np.float64)
+        assert sp.ndim == 1 and len(sp) >= 1 and sf.shape == sw.shape == (int(sp[-1]),)
+        reg = vl = None
+        if n_regions:
+            reg = np.ascontiguousarray(np.asarray(region, dtype=np.uint8)[self.cell_order])
+            vl = np.ascontiguousarray(np.asarray(vol, dtype=np.float64)[self.cell_order])
+            assert reg.shape == vl.shape == (self.nc,)
+        self._chk(self.lib.knp_rec_create(self.ctx, int(capacity), len(pc), _p(pc, _i32p), _p(pw, _f64p), len(sp) - 1, _p(sp, _i64p),
+                                          _p(sf, _i32p), _p(sw, _f64p), int(n_regions), _p(reg, C.POINTER(C.c_uint8)), _p(vl, _f64p)),
+                  "knp_rec_create")
+        self._rec_capacity = int(capacity)
+        self._rec_channels = int(self.lib.knp_rec_channels(self.ctx))
+        return self._rec_channels
+
+    def rec_sample(self, t):
+        """One row at time t; asynchronous.  KnpError (-5) when the buffer is full."""
+        self._chk(self.lib.knp_rec_sample(self.ctx, float(t)), "knp_rec_sample")
+
+    def rec_read(self):
+        """(t [n], rows [n, channels]) of the samples since the last read; synchronises and empties the device buffer."""
+        n = C.c_int64(0)
+        t = np.empty(self._rec_capacity)
+        rows = np.empty((self._rec_capacity, self._rec_channels))
+        self._chk(self.lib.knp_rec_read(self.ctx, C.byref(n), _p(t, _f64p), _p(rows, _f64p)), "knp_rec_read")
+        return t[:n.value].copy(), rows[:n.value].copy()
+
+    def rec_destroy(self):
+        self._chk(self.lib.knp_rec_destroy(self.ctx), "knp_rec_destroy")
+
 
 def _flushing(fn):
     def wrapped(self, *a, **k):
@@ -863,7 +905,8 @@ def _flushing(fn):
 for _name in ("close", "set_params", "set_mms", "upload", "download", "copy_field", "update_kappa", "update_dnphi", "emi_apply",
               "knp_apply", "emi_rhs", "knp_rhs", "emi_solve", "knp_solve", "step_updates", "picard_updates", "max_abs_diff",
               "nernst", "sync", "timer_begin", "timer_end", "bench_apply", "ode_table", "ode_step", "ode_set_stimulus",
-              "amg_upload", "amg_interface", "halo_exchange", "knp_load_measure", "apply_timing_read", "comm_init", "set_interior"):
+              "amg_upload", "amg_interface", "halo_exchange", "knp_load_measure", "apply_timing_read", "comm_init", "set_interior", "rec_sample",
+              "rec_read"):
     setattr(Device, _name, _flushing(getattr(Device, _name)))
 
 

@@ -84,6 +84,7 @@ class Solver:
         self.use_amg = os.environ.get("KNP_NO_AMG", "0") != "1"
         self.use_device_ode = os.environ.get("KNP_HOST_ODE", "0") != "1"
         self.max_it_knp = 5000
+        self.recorder = None             # time-series recorder (Solver.record), sampled after step III of every time step
 
     # ------------------------------------------------------------------ setup_domain (solver.py:85-121)
     def setup_domain(self, mesh, subdomains, surfaces):
@@ -247,6 +248,36 @@ class Solver:
         self._push_params(splitting=True)
         dev.nernst()                                                 # initial E_k (solver.py:299-300)
         _abi._stamp("solver: initial fields and parameters on the device")
+        if self.recorder is not None:
+            self.recorder.attach(dev, self.membrane_tags)
+
+    # ------------------------------------------------------------------ time series (no reference counterpart: knpemidg/recorder.py)
+    def record(self, points=None, membrane_sets=None, regions=True, capacity=256, point_tags=None):
+        """Attach a recorder of point probes, membrane-set means and region integrals, sampled on the device after step III of
+        every time step (csrc/record.hip) -- the traces the reference's figure scripts compute from per-step field output
+        (examples/idealized-geometries/make_figures_3D.py:28-168).  Callable once setup_domain has run; the device tables are
+        created as soon as the device context exists.  Returns the `knpemidg.recorder.Recorder`; a second call replaces it.
+          points         [n, dim] coordinates; point_tags[i] (optional) = subdomain of the cell to take for a point on a membrane
+          membrane_sets  list of facet-id arrays or (lo, hi) boxes (the membrane facets whose midpoint lies inside)
+          regions        True = one region per distinct subdomain tag, ascending; False = none
+          capacity       rows of the device buffer = time steps between two device-to-host copies"""
+        from knpemidg.recorder import Recorder
+        if getattr(self, "local_mesh", None) is not None or getattr(self, "nc_owned", None) is not None:
+            raise _abi.KnpError("Solver.record: partitioned solvers (distribute_solver) are not supported; record on a one-GPU run")
+        if getattr(self, "mesh", None) is None:
+            raise _abi.KnpError("Solver.record: call setup_domain first")
+        mtags = self.membrane_tags if self.dev is not None else None
+        rec = Recorder(self.mesh, self.subdomains.array(), self.surfaces.array(), self.degree_knp, [ion['name'] for ion in self.ion_list],
+                       points=points, membrane_sets=membrane_sets, regions=regions, capacity=capacity, point_tags=point_tags,
+                       membrane_tags=mtags)
+        if self.dev is not None:
+            rec.attach(self.dev)
+        self.recorder = rec
+        return rec
+
+    def _save_timeseries(self):
+        if self.recorder is not None and self.filename is not None:
+            self.recorder.save(self.filename + 'timeseries.h5')
 
     def _push_params(self, splitting):
         z = [float(ion['z']) for ion in self.ion_list]
@@ -828,6 +859,8 @@ class Solver:
         if first:
             self.dev.sync(); _abi._stamp("first step: step III")
         t.assign(float(t + self.dt))
+        if self.recorder is not None:
+            self.recorder.sample(float(t))
         return
 
     # ------------------------------------------------------------------ Picard variant (solver.py:850-927)
@@ -851,6 +884,8 @@ class Solver:
                 print("Picard solver diverged")
                 sys.exit(2)
         self.dev.step_updates()                             # c_prev_n <- c_prev_k, phi_M, (E_k, c_elim unchanged)
+        if self.recorder is not None:
+            self.recorder.sample(float(t))
         self.picard_iters = getattr(self, "picard_iters", []) + [it]
         if self.verbose:
             print(f" Summary Picard: eps = {eps}, #iters = {it}")
@@ -897,6 +932,7 @@ class Solver:
                 self.save_h5()
         if self.save_fields:
             self.close_h5()
+        self._save_timeseries()
         if self.save_solver_stats:
             self.close_solver_stats()
         uh = self.c.split() + (self.phi,)
@@ -921,6 +957,7 @@ class Solver:
                 self.save_h5()
         if self.save_fields:
             self.close_h5()
+        self._save_timeseries()
         if self.save_solver_stats:
             self.close_solver_stats()
         return
