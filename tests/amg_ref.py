@@ -1,30 +1,501 @@
-"""Reference (numpy) V-cycle over a knpemidg.amg hierarchy -- test infrastructure mirroring csrc/amg.hip."""
+"""Host replica of the auxiliary-space preconditioner (csrc/amg.hip, csrc/krylov.hip) -- test infrastructure.
+
+  * `store`: a knpemidg.amg-style hierarchy as the device stores it -- CSR values of A, P, R and the coarse (pseudo-)inverse rounded to
+    fp32 (amg.hip: up_csr, amg_finish_impl), dinv / rho / cheb_lower in fp64 -- converted to a working precision: float64, or
+    np.longdouble where that has a 64-bit mantissa (`HP`; elsewhere the high-precision run sums its rows with math.fsum).
+  * `vcycle`: amg_vcycle_eager, level by level, for [ncol, n] right-hand sides (the columns are independent).
+  * `EmiPrecond` / `KnpPrecond`: the two-level preconditioners of pcg_impl / bicgstab_impl around it; `bj_lambda_max`.
+  * `bicgstab`: k iterations in the form of bicgstab_impl (the PCG twin is krylov_ref.pcg with `precond` / `iters`).
+  * `launches`: which (kernel, G, NC) instantiations a hierarchy reaches (LAUNCH_BY_DENSITY / launch_csr_on).
+  * `synthetic`: seeded hand-built hierarchies (any density, any level size) for tests/test_amg_ref_host.py and a comparison on the device.
+A `mut = (name, level)` argument applies one deliberate error (MUTATIONS; drop_tail: (name, (level, matrix))) -- the CPU tests show
+that each one is far above the comparison bound (`bound`).
+The "fsum" fallback is NOT a wider arithmetic: only the row sums of the matrix products are exactly rounded, the vector updates, inner
+products and cell-block products stay float64 (measured on a three-level V-cycle: 2.2e-15 from the long-double result against 3.0e-15
+for plain float64).  Where long double has no 64-bit mantissa, `bound` therefore rests on its 1e-13 floor rather than on a measured
+rounding error; on x86-64, where the tests run, HP is the 80-bit long double."""
+import math
+
 import numpy as np
+import scipy.sparse as sp
+
+HP = np.longdouble if np.finfo(np.longdouble).nmant >= 63 else None
+
+# average-row-length limits of LAUNCH_BY_DENSITY / launch_csr_on (csrc/amg.hip; the second one is g4_limit(), KNP_AMG_G4)
+BANDS = ((12.0, 1), (40.0, 4), (96.0, 8), (math.inf, 64))
+KERNELS = ("k_csr<0>", "k_csr<1>", "k_csr<2>", "k_csr_first", "k_cheb_first_res", "k_cheb_step")
+MUTATIONS = ("no_round_A", "drop_tail", "swap_columns", "short_post_smooth", "no_prolongation", "dense_last_row")
 
 
-def cheb_smooth(lv, x, b, zero_guess):
-    lmax, lmin = lv.rho, lv.cheb_lower * lv.rho
-    theta, delta = 0.5 * (lmax + lmin), 0.5 * (lmax - lmin)
+class _Level:
+    pass
+
+
+def band_G(M):
+    avg = M.nnz / M.shape[0] if M.shape[0] else 0.0
+    return next(g for lim, g in BANDS if avg <= lim)
+
+
+def _unroll(ncol):
+    return 2 if ncol % 2 == 0 else 4                    # row_dot: (col, val) pairs in flight per lane
+
+
+class _FsumCsr:
+    """float64 matrix whose products sum every row with math.fsum (the high-precision run where long double is no wider)"""
+
+    def __init__(self, M):
+        self.M = sp.csr_matrix(M)
+        self.shape = self.M.shape
+
+    def __matmul__(self, x):
+        M, out = self.M, np.zeros(self.shape[0])
+        for i in range(self.shape[0]):
+            k = slice(M.indptr[i], M.indptr[i + 1])
+            out[i] = math.fsum((M.data[k] * x[M.indices[k]]).tolist())
+        return out
+
+
+def _drop_tail(M, ncol):
+    """mutation: the last entry of every row whose length is 1 modulo U * G is lost"""
+    M = M.tocsr().copy()
+    M.sort_indices()
+    m = _unroll(ncol) * band_G(M)
+    ln = np.diff(M.indptr)
+    hit = np.nonzero(ln % m == 1)[0]
+    M.data[M.indptr[hit + 1] - 1] = 0.0
+    return M, len(hit)
+
+
+def store(levels, dtype=np.float64, mut=None, ncol=1):
+    """device storage of `levels` (objects with A, dinv, rho, cheb_degree, cheb_lower, P, R; the last one with pinv) in `dtype`"""
+    fsum = dtype == "fsum"
+    wd = np.float64 if fsum else dtype
+    name, ml = mut if mut else (None, -1)
+    out, dropped = [], 0
+    for l, lv in enumerate(levels):
+        L = _Level()
+        L.n = lv.A.shape[0]
+        L.cheb_degree = int(lv.cheb_degree)
+        L.dinv = np.asarray(lv.dinv, dtype=np.float64).astype(wd)
+        L.rho, L.cheb_lower = wd(lv.rho), wd(lv.cheb_lower)
+        mats = {"A": lv.A}
+        if l < len(levels) - 1:
+            mats.update(P=lv.P, R=lv.R)
+        for key, M in mats.items():
+            M = sp.csr_matrix(M, dtype=np.float64)
+            M.sort_indices()
+            if not (name == "no_round_A" and l == ml and key == "A"):
+                M = sp.csr_matrix((M.data.astype(np.float32).astype(np.float64), M.indices, M.indptr), shape=M.shape)
+            if name == "drop_tail" and (l, key) == tuple(ml):                       # ml = (level, "A" | "P" | "R")
+                M, k = _drop_tail(M, ncol)
+                dropped += k
+            setattr(L, key, _FsumCsr(M) if fsum else M.astype(wd))
+        out.append(L)
+    assert name != "drop_tail" or dropped, "drop_tail: no row of length 1 modulo U * G"
+    pinv = np.asarray(levels[-1].pinv).astype(np.float32).astype(np.float64)
+    out[-1].pinv = _FsumCsr(pinv) if fsum else pinv.astype(wd)
+    return out
+
+
+def smooth(L, x, b, zero_guess, steps=None):
+    """amg.hip: smooth() -- Chebyshev polynomial of D^-1 A on [cheb_lower * rho, rho]"""
+    lmax, lmin = L.rho, L.cheb_lower * L.rho
+    theta, delta = (lmax + lmin) / 2, (lmax - lmin) / 2
     sigma = theta / delta
-    rho = 1.0 / sigma
-    r = b.copy() if zero_guess else b - lv.A @ x
-    d = lv.dinv * r / theta
-    for k in range(lv.cheb_degree):
+    rho = 1 / sigma
+    steps = L.cheb_degree if steps is None else steps
+    if steps < 1:
+        return x
+    r = b.copy() if zero_guess else b - L.A @ x
+    d = L.dinv * r * (1 / theta)                                        # k_cheb_first / k_cheb_first_res / k_csr_first
+    x = d.copy() if zero_guess else x + d
+    for _ in range(1, steps):                                           # k_cheb_step
+        rho_new = 1 / (2 * sigma - rho)
+        r = r - L.A @ d
+        d = (rho_new * rho) * d + (2 * rho_new / delta) * L.dinv * r
         x = x + d
-        if k == lv.cheb_degree - 1:
-            break
-        r = r - lv.A @ d
-        rho_new = 1.0 / (2.0 * sigma - rho)
-        d = rho_new * rho * d + (2.0 * rho_new / delta) * (lv.dinv * r)
         rho = rho_new
     return x
 
 
-def vcycle(levels, b, l=0):
-    lv = levels[l]
-    if l == len(levels) - 1:
-        return lv.pinv @ b
-    x = cheb_smooth(lv, np.zeros_like(b), b, True)
-    r = b - lv.A @ x
-    x = x + lv.P @ vcycle(levels, lv.R @ r, l + 1)
-    return cheb_smooth(lv, x, b, False)
+def _vcycle_levels(H, B, l, mut):
+    """B: list of the columns' right-hand sides on level l"""
+    L = H[l]
+    name, ml = mut if mut else (None, -1)
+    here = l == ml
+    if name == "drop_tail":
+        here = False                                                    # (applied by `store`)
+    if l == len(H) - 1:                                                 # k_dense_mv
+        X = [L.pinv @ b for b in B]
+        if here and name == "dense_last_row":
+            for x in X:
+                x[-1] = 0
+    elif L.cheb_degree == 0:                                            # transfer-only level
+        Xc = _vcycle_levels(H, [L.R @ b for b in B], l + 1, mut)
+        X = [L.P @ xc for xc in Xc]
+        if here and name == "no_prolongation":
+            X = [0 * x for x in X]
+    else:
+        X = [smooth(L, None, b, True) for b in B]
+        Xc = _vcycle_levels(H, [L.R @ (b - L.A @ x) for b, x in zip(B, X)], l + 1, mut)
+        if not (here and name == "no_prolongation"):
+            X = [x + L.P @ xc for x, xc in zip(X, Xc)]
+        post = L.cheb_degree - 1 if here and name == "short_post_smooth" else None
+        X = [smooth(L, x, b, False, post) for x, b in zip(X, B)]
+    if here and name == "swap_columns":
+        assert len(X) >= 2, "swap_columns needs two right-hand-side columns"
+        X[0], X[1] = X[1], X[0]
+    return X
+
+
+def vcycle(H, B, mut=None):
+    """x = V(b) for every row of B [ncol, n_0] (or one vector [n_0]); H from `store`"""
+    B = np.asarray(B)
+    if B.ndim == 1:
+        return _vcycle_levels(H, [B], 0, mut)[0]
+    return np.stack(_vcycle_levels(H, [b for b in B], 0, mut))
+
+
+# ---- the two-level preconditioners of krylov.hip -------------------------------------------------------------------------------------
+BJ_LMIN = 0.05                                                          # krylov.hip: bj_lmin_frac
+
+
+def _blocks(binv, r):
+    nb, nd, _ = binv.shape
+    return np.einsum("bij,bj->bi", binv, r.reshape(nb, nd)).ravel()
+
+
+def bj_lambda_max(As, binvs, bs, iters=20):
+    """krylov.hip: bj_lambda_max_impl (the systems are normalised together: max over the species), times the 1.1 of abi.hip"""
+    v = [np.asarray(b, dtype=np.float64).copy() for b in bs]
+    nv = max(np.abs(x).max() for x in v)
+    lam = 0.0
+    for _ in range(iters):
+        y = [_blocks(Bi, A @ x) for A, Bi, x in zip(As, binvs, v)]
+        ny = max(np.abs(x).max() for x in y)
+        lam = ny / nv
+        a = 1.0 / ny
+        v = [a * x for x in y]
+        nv = 1.0
+    return 1.1 * lam
+
+
+def _cheb2_coefficients(lmax, wd):
+    lmax = wd(lmax)
+    lmin = wd(BJ_LMIN) * lmax
+    theta, delta = (lmax + lmin) / 2, (lmax - lmin) / 2
+    sigma = theta / delta
+    rho0 = 1 / sigma
+    rho1 = 1 / (2 * sigma - rho0)
+    return (1 + rho1 * rho0) / theta + 2 * rho1 / delta, (2 * rho1 / delta) / theta, theta       # cr, ctt, theta
+
+
+class _TwoLevel:
+    def __init__(self, A, binv, dg2cg, ncg, dtype):
+        self.wd = np.float64 if dtype == "fsum" else dtype
+        self.A = [_FsumCsr(M) if dtype == "fsum" else sp.csr_matrix(M).astype(self.wd) for M in A]
+        self.binv = [np.asarray(b).astype(self.wd) for b in binv]
+        d = np.asarray(dg2cg).ravel()
+        Pd = sp.csr_matrix((np.ones(len(d)), (np.arange(len(d)), d)), shape=(len(d), ncg))
+        self.Pd, self.Pdt = (Pd.astype(self.wd), Pd.T.tocsr().astype(self.wd)) if dtype != "fsum" else (_FsumCsr(Pd), _FsumCsr(Pd.T))
+
+
+class EmiPrecond(_TwoLevel):
+    """pcg_impl: z = S(r) + P_dg V(P_dg^T r); S = the fp32 cell blocks (lmax = 0) or the two-step Chebyshev block-Jacobi (k_bj_cheb2)"""
+
+    def __init__(self, A, binv, dg2cg, H, lmax=0.0, dtype=np.float64, mut=None):
+        super().__init__([A], [binv], dg2cg, H[0].n, dtype)
+        self.H, self.lmax, self.mut = H, lmax, mut
+
+    def __call__(self, r):
+        z = _blocks(self.binv[0], r)
+        if self.lmax > 0.0:
+            cr, ctt, _ = _cheb2_coefficients(self.lmax, self.wd)
+            z = _blocks(self.binv[0], cr * r - ctt * (self.A[0] @ z))
+        return z + self.Pd @ vcycle(self.H, self.Pdt @ r, self.mut)
+
+
+class KnpPrecond(_TwoLevel):
+    """bicgstab_impl, hybrid form: z_s = S2(r_s) + P_dg V(P_dg^T (r_s - t_s / theta)), t_s = A_s Binv_s r_s.  Hs: one shared hierarchy
+    (the species are its columns) or one hierarchy per species."""
+
+    def __init__(self, As, binvs, dg2cg, Hs, lmax, dtype=np.float64, mut=None):
+        super().__init__(As, binvs, dg2cg, (Hs[0] if isinstance(Hs[0], list) else Hs)[0].n, dtype)
+        self.shared = not isinstance(Hs[0], list)
+        self.Hs, self.lmax, self.mut = Hs, lmax, mut
+
+    def __call__(self, R):
+        cr, ctt, theta = _cheb2_coefficients(self.lmax, self.wd)
+        Z, C = [], []
+        for A, Bi, r in zip(self.A, self.binv, R):
+            t = A @ _blocks(Bi, r)
+            Z.append(_blocks(Bi, cr * r - ctt * t))
+            C.append(self.Pdt @ (r - (1 / theta) * t))
+        E = vcycle(self.Hs, np.stack(C), self.mut) if self.shared else [vcycle(H, c, self.mut) for H, c in zip(self.Hs, C)]
+        return [z + self.Pd @ e for z, e in zip(Z, E)]
+
+
+def bicgstab(As, bs, precond, iters, dtype=np.float64):
+    """`iters` iterations of bicgstab_impl from x0 = 0 for the species' systems (their scalars are separate, the preconditioner sees all
+    of them); the first iteration in the folded form p = r.  Returns [nsys, n]."""
+    wd = np.float64 if dtype == "fsum" else dtype
+    A = [_FsumCsr(M) if dtype == "fsum" else sp.csr_matrix(M).astype(wd) for M in As]
+    ns = len(A)
+    r = [np.asarray(b).astype(wd) for b in bs]                          # x0 = 0
+    rhat = [x.copy() for x in r]
+    x = [np.zeros_like(b) for b in r]
+    rho = [b @ b for b in r]
+    p = v = None
+    alpha, omega, beta = [wd(1)] * ns, [wd(1)] * ns, [wd(0)] * ns
+    for it in range(iters):
+        p = [r[s].copy() if it == 0 else r[s] + beta[s] * (p[s] - omega[s] * v[s]) for s in range(ns)]
+        y = precond(p)
+        v = [A[s] @ y[s] for s in range(ns)]
+        alpha = [rho[s] / (rhat[s] @ v[s]) for s in range(ns)]
+        r = [r[s] - alpha[s] * v[s] for s in range(ns)]
+        z = precond(r)
+        t = [A[s] @ z[s] for s in range(ns)]
+        omega = [(t[s] @ r[s]) / (t[s] @ t[s]) for s in range(ns)]
+        x = [x[s] + alpha[s] * y[s] + omega[s] * z[s] for s in range(ns)]
+        r = [r[s] - omega[s] * t[s] for s in range(ns)]
+        rho_new = [rhat[s] @ r[s] for s in range(ns)]
+        beta = [(rho_new[s] / rho[s]) * (alpha[s] / omega[s]) for s in range(ns)]
+        rho = rho_new
+    return np.stack(x)
+
+
+# ---- which kernel instantiations a hierarchy reaches -----------------------------------------------------------------------------------
+def launches(levels, ncol):
+    """set of (kernel, G, NC) that amg_restrict_tail and amg_vcycle_eager launch through LAUNCH_BY_DENSITY / launch_csr_on"""
+    nc = 2 if ncol % 2 == 0 else 1
+    out = set()
+
+    def hit(kernel, M):
+        out.add((kernel, band_G(sp.csr_matrix(M)), nc))
+    nl = len(levels)
+    if nl > 1 and levels[0].cheb_degree == 0:                           # amg_restrict_tail_impl
+        hit("k_csr<0>", levels[0].R)
+    for l in range(nl - 1):                                             # the way down
+        L = levels[l]
+        if L.cheb_degree == 0:
+            if l > 0:
+                hit("k_csr<0>", L.R)
+            continue
+        if L.cheb_degree > 1:
+            hit("k_cheb_step", L.A)
+        hit("k_csr<1>", L.A)
+        hit("k_csr_first" if l + 1 < nl - 1 and levels[l + 1].cheb_degree > 0 else "k_csr<0>", L.R)
+    for l in range(nl - 2, -1, -1):                                     # and up
+        L = levels[l]
+        if L.cheb_degree == 0:
+            hit("k_csr<0>", L.P)
+            continue
+        hit("k_csr<2>", L.P)
+        hit("k_cheb_first_res", L.A)
+    return out
+
+
+# ---- hand-built hierarchies ------------------------------------------------------------------------------------------------------------
+def _pattern(rng, nrows, ncols, lengths):
+    rows = np.repeat(np.arange(nrows), lengths)
+    cols = np.concatenate([rng.choice(ncols, size=k, replace=False) for k in lengths]) if nrows else np.zeros(0, int)
+    return rows, cols
+
+
+def _lengths(rng, nrows, ncols, avg):
+    """row lengths around `avg`; where they fit, lengths 1 modulo U * G of both unrollings sit in the first rows (5, 17, 33, 257)"""
+    ln = np.clip(rng.poisson(avg, size=nrows), 1, ncols)
+    special = [k for k in (5, 17, 33, 257) if k <= ncols and 0.4 * avg <= k <= 2.7 * avg]
+    ln[:len(special)] = special[:nrows]
+    return ln
+
+
+def _spd(rng, n, avg, scale):
+    """sparse, symmetric, strictly diagonally dominant; about `avg` entries per row"""
+    half = max((avg - 1.0) / 2.0, 0.0)
+    r, c = _pattern(rng, n, n, np.clip(rng.poisson(half, size=n), 0, n))
+    keep = r != c
+    S = sp.coo_matrix((-rng.uniform(0.1, 1.0, size=int(keep.sum())), (r[keep], c[keep])), shape=(n, n)).tocsr()
+    S = S + S.T
+    off = np.asarray(abs(S).sum(axis=1)).ravel()
+    A = (S + sp.diags(off * rng.uniform(1.002, 1.05, size=n) + 0.01)).tocsr() * (scale / (off.mean() + 0.01))   # mean diagonal ~ scale
+    A.sort_indices()
+    # every value 2.5e-8 (less than half an fp32 step) above an fp32 number: the device's rounding is then a shift of the whole matrix
+    # in one direction, which a replica that forgets it cannot hide in averaging sums
+    A.data = A.data.astype(np.float32).astype(np.float64) * (1.0 + 2.5e-8)
+    return A
+
+
+def _prolongator(rng, n, ncoarse, avg):
+    ln = _lengths(rng, n, ncoarse, avg)
+    r, c = _pattern(rng, n, ncoarse, ln)
+    if ncoarse - 1 not in c:
+        c[0] = ncoarse - 1                                              # every coarse dof down to the last one has a say
+    P = sp.coo_matrix((rng.uniform(1.0, 3.0, size=len(r)) / np.repeat(ln, ln), (r, c)), shape=(n, ncoarse)).tocsr()
+    P.sort_indices()
+    return P
+
+
+def synthetic(sizes, dens_A, dens_P, degrees, scale, seed):
+    """Levels of sizes `sizes` with about dens_A[l] / dens_P[l] entries per row of A_l / P_l (R_l = P_l^T), Chebyshev degrees
+    `degrees` and a dense symmetric positive fp32 matrix G G^T / n + I on the last one.  `scale`: size of the entries of A (the V-cycle
+    then answers with about b / scale, like the cell blocks of the operator it is added to)."""
+    rng = np.random.default_rng(seed)
+    levels = []
+    for l, n in enumerate(sizes):
+        lv = _Level()
+        last = l == len(sizes) - 1
+        lv.A = _spd(rng, n, 3.0 if last else dens_A[l], scale)
+        lv.dinv = 1.0 / lv.A.diagonal()
+        # (the spectrum of D^-1 A lies in (0, 2), most of it near 1: a generous rho leaves every level about half of its residual, so
+        # that all levels have their share in the result)
+        lv.rho = float(rng.uniform(2.6, 3.4))
+        lv.cheb_lower = float(rng.uniform(0.1, 0.3))
+        lv.cheb_degree = 0 if last else int(degrees[l])
+        if not last:
+            lv.P = _prolongator(rng, n, sizes[l + 1], dens_P[l])
+            lv.R = lv.P.T.tocsr()
+            lv.R.sort_indices()
+        levels.append(lv)
+    n = sizes[-1]
+    G = rng.standard_normal((n, n))
+    levels[-1].pinv = ((G @ G.T / n + np.eye(n)) / scale).astype(np.float32)
+    return levels
+
+
+COARSE_N = (1, 2, 33, 255, 257, 769, 1030, 2051)
+# the hierarchies of synthetic_set: the CPU coverage assertion and the device tests (one column: EMI, two: KNP) run this same list
+SYNTHETIC = ("bands", "bands_t0", "mid") + tuple("coarse_%d" % n for n in COARSE_N)
+
+
+def drop_tail_targets(levels, ncol):
+    """(level, matrix) pairs the V-cycle uses that have a row of length 1 modulo U * G of the variant the matrix selects"""
+    out = []
+    for l, lv in enumerate(levels[:-1]):
+        for key in ("A", "P", "R"):
+            if key == "A" and lv.cheb_degree == 0:
+                continue
+            if _drop_tail(sp.csr_matrix(getattr(lv, key)), ncol)[1]:
+                out.append((l, key))
+    return out
+
+
+def synthetic_set(n0, scale):
+    """name -> levels: the hierarchies to run on the device, for a conforming space of n0 dofs"""
+    out = {
+        # every density band among the A's, P's and R's; all smoother degrees
+        "bands": synthetic((n0, 300, 150, 70, 33), (25, 120, 60, 8), (105, 8, 5, 20), (2, 3, 1, 2), scale, 11),
+        # the same with a transfer-only finest level, as the EMI production hierarchy had it
+        "bands_t0": synthetic((n0, 300, 150, 70, 33), (25, 120, 60, 8), (105, 8, 5, 20), (0, 2, 3, 1), scale, 11),
+        # a restriction in the top band that also carries the next level's first smoother update (k_csr_first<64, .>)
+        "mid": synthetic((n0, 140, 40), (50, 100), (60, 30), (1, 2), scale, 12),
+    }
+    dens = {1: (6, 1), 2: (30, 1), 33: (70, 4), 255: (110, 5), 257: (10, 60), 769: (45, 120), 1030: (20, 20), 2051: (8, 3)}
+    for k, n in enumerate(COARSE_N):
+        out["coarse_%d" % n] = synthetic((n0, n), (dens[n][0],), (dens[n][1],), (1 + k % 3,), scale, 20 + k)
+    return out
+
+
+# ---- the k-iteration observable on the oracle's matrices ------------------------------------------------------------------------------
+EXTRA_IONS = dict(X=(1.0, 1.6e-9), Y=(-1.0, 1.8e-9))                    # (z, D) of the ions beyond K, Cl, Na (monovalent: see
+                                                                        # test_knp_solve_with_other_species_counts)
+
+
+class Host:
+    """One of the test meshes ("box_P1": small_3d((8, 4, 4)), "box_P2": small_3d((6, 3, 3)) with DG-P2, "2D_P1": make_mesh_2D(0)) with
+    the oracle's problem in the seeded synthetic state, its matrices (krylov_ref.Ref) and the conforming map of the preconditioner.
+    names: ions of the problem, the last one eliminated (default: the K / Cl / Na problem of the examples)."""
+
+    def __init__(self, mesh, names=None):
+        import knpemi_oracle as ko
+        import krylov_ref as kr
+        from common import synthetic_state, small_3d
+        from knpemidg import amg
+        self.mesh_name, p = mesh, (2 if mesh.endswith("P2") else 1)
+        if mesh == "2D_P1":
+            from knpemidg.mesh import make_mesh_2D
+            self.mt = make_mesh_2D(0)
+        else:
+            self.mt = small_3d((8, 4, 4) if p == 1 else (6, 3, 3))
+        m, s, f = self.mt
+        if names is None:
+            pb = ko.build_idealized(m, s.array(), f.array(), p=p, membrane_tags=(1,))
+        else:
+            P = ko.idealized_params()
+            z = dict(P["z"], **{n: v[0] for n, v in EXTRA_IONS.items()})
+            D = dict(P["D"], **{n: v[1] for n, v in EXTRA_IONS.items()})
+            ions = [dict(name=n, z=z[n], D=np.full(m.num_cells(), D[n])) for n in names]
+            pb = ko.Problem(m, s.array().astype(np.int64), f.array(), p, ions, P, membrane_tags=(1,))
+            rng = np.random.default_rng(7)
+            pb.c = rng.uniform(80.0, 120.0, size=pb.c.shape)
+            pb.c_prev_n = pb.c * (1 + 1e-3 * rng.uniform(-1, 1, size=pb.c.shape))
+            pb.c_elim = rng.uniform(80.0, 120.0, size=pb.c_elim.shape)
+        synthetic_state(pb)
+        self.pb, self.ref, self.nd = pb, kr.Ref(pb), pb.nd
+        self.cs = amg.ConformingSpace(m, f.array(), (1,))
+        self.cs2 = amg.ConformingSpaceP2(self.cs) if p != 1 else None
+        self.dg2cg = np.asarray((self.cs2 or self.cs).dof)
+        self.ncg = int(self.dg2cg.max()) + 1
+        self._knp = None
+
+    def emi_levels(self):
+        """the production hierarchy (Case.upload_amg of test_gpu_krylov.py)"""
+        from knpemidg import amg
+        tags = self.mt[2].array()
+        mem = sorted({int(t) for t in np.unique(tags[self.pb.mem])})
+        return amg.build_emi_levels(self.cs, self.cs2, tags, mem, self.pb.kappa(), self.pb.C_phi)
+
+    def scale(self, knp=False):
+        """entry size of a synthetic hierarchy whose V-cycle answers in the size of the cell blocks' part of the preconditioner"""
+        A = self.knp()[0][0] if knp else self.ref.A_emi
+        return float(A.diagonal().mean()) * self.pb.ndof / self.ncg
+
+    def knp(self):
+        """([A_k], [fp32 cell-block inverses of A_k], [oracle b_k]) of the solved species"""
+        if self._knp is None:
+            import krylov_ref as kr
+            mats = [self.ref.knp(k) for k in range(self.pb.N_ions)]
+            self._knp = ([A for A, _ in mats], [kr.block_inverses(A, self.nd) for A, _ in mats], [b.ravel() for _, b in mats])
+        return self._knp
+
+    def peclet(self):
+        """abi.hip: k_cell_peclet -- above 0.5 the KNP solve uses the per-cell block inverses (drift included), as `knp` does"""
+        zmax = max(abs(ion["z"]) for ion in self.pb.ions[:-1])
+        return float(self.pb.psi * zmax * (self.pb.phi.max(axis=1) - self.pb.phi.min(axis=1)).max())
+
+
+def emi_xk(host, levels, cheb, k, dtype=np.float64, b=None, mut=None):
+    """x_k of the device's EMI PCG from x_0 = 0 with the two-level preconditioner over `levels`; cheb: the Chebyshev DG smoother"""
+    import types
+    import krylov_ref as kr
+    ref = host.ref
+    b = ref.b_emi if b is None else np.asarray(b, dtype=np.float64).ravel()
+    lmax = bj_lambda_max([ref.A_emi], [ref.binv_emi], [b]) if cheb else 0.0
+    M = EmiPrecond(ref.A_emi, ref.binv_emi, host.dg2cg, store(levels, dtype, mut), lmax, dtype, mut)
+    return kr.pcg(types.SimpleNamespace(A_emi=ref.A_emi, b_emi=b, binv_emi=ref.binv_emi), 0.0, 0.0, precond=M, iters=k, dtype=dtype)[0]
+
+
+def knp_xk(host, levels, k, dtype=np.float64, bs=None, lmax_bs=None, mut=None):
+    """x_k [nsys, ndof] of the device's KNP BiCGStab from x_0 = 0.  levels: one hierarchy shared by the species (its columns), or a
+    list with one hierarchy per species.  lmax_bs: the right-hand sides the spectral bound was estimated from (default: bs)."""
+    As, binvs, b0 = host.knp()
+    bs = b0 if bs is None else [np.asarray(b, dtype=np.float64).ravel() for b in bs]
+    ns = len(As)
+    lmax = bj_lambda_max(As, binvs, bs if lmax_bs is None else lmax_bs)
+    shared = hasattr(levels[0], "A")
+    Hs = store(levels, dtype, mut, ncol=ns) if shared else [store(lv, dtype, mut) for lv in levels]
+    return bicgstab(As, bs, KnpPrecond(As, binvs, host.dg2cg, Hs, lmax, dtype, mut), k, dtype)
+
+
+def hp_dtype():
+    return HP if HP is not None else "fsum"
+
+
+def bound(x64, xhp):
+    """the comparison bound of DESIGN.md ("V-cycle parity"), measured on the reference itself: 32 times the rounding error of the
+    float64 replica against the extended-precision one, at least 1e-13 of the result; above 1e-9 the case is ill-conditioned"""
+    x64, xhp = np.asarray(x64), np.asarray(xhp)
+    scale = float(np.abs(xhp).max())
+    bd = max(32.0 * float(np.abs(x64 - xhp).max()), 1e-13 * scale)
+    assert bd <= 1e-9 * scale, "ill-conditioned case: bound %.3g of the result" % (bd / scale)
+    return bd

@@ -100,17 +100,25 @@ def apply_blocks(binv, r):
     return np.einsum("bij,bj->bi", binv, np.asarray(r, dtype=np.float64).reshape(nb, nd)).ravel()
 
 
-def pcg(ref, rtol, r_abs, x0=None, maxit=20000, rule="device"):
+def pcg(ref, rtol, r_abs, x0=None, maxit=20000, rule="device", precond=None, iters=None, dtype=np.float64):
     """Replica of the device PCG (krylov.hip: pcg_impl, scalar_op OP_CG_*) with block-Jacobi only and r_abs > 0 (error-controlled stop).
     rule "device": the stopping test of csrc/krylov.hip (cg_converged, OP_CG_BETA: smoothed decay rate); "onestep": the one-term
-    extrapolation it replaced (alpha_k rho_{k+1} / (1 - min(beta_k, 0.9))).  Returns (x, iterations)."""
+    extrapolation it replaced (alpha_k rho_{k+1} / (1 - min(beta_k, 0.9))).  Returns (x, iterations).
+    precond: z = precond(r) instead of the cell blocks (amg_ref.EmiPrecond).  iters: exactly that many iterations, no stopping test
+    (what the device returns for maxit = iters and a tolerance it cannot reach), in `dtype` (float64, np.longdouble, or "fsum":
+    float64 with exactly rounded row sums)."""
+    if iters is not None:
+        return _pcg_fixed(ref, x0, precond, iters, dtype), iters
     A, b, binv = ref.A_emi, ref.b_emi, ref.binv_emi
+    if precond is None:
+        def precond(r):
+            return apply_blocks(binv, r)
     x = np.zeros(A.shape[0]) if x0 is None else np.asarray(x0, dtype=np.float64).ravel().copy()
     w = A @ x
     r = b - w                                                           # k_cg_init
-    z = apply_blocks(binv, r)
+    z = precond(r)
     p = z.copy()
-    st = dict(rho=float(z @ r), res=math.sqrt(z @ z), bnorm=math.sqrt(np.sum(apply_blocks(binv, b) ** 2)),
+    st = dict(rho=float(z @ r), res=math.sqrt(z @ z), bnorm=math.sqrt(np.sum(precond(b) ** 2)),
               rnorm=ref.norm_d8(r), xa=max(float(x @ w), 0.0), sum=0.0, est=1e300, lb=0.0)
     if cg_converged(st, r_abs, rtol, 0):
         return x, 0
@@ -121,7 +129,7 @@ def pcg(ref, rtol, r_abs, x0=None, maxit=20000, rule="device"):
         st["sum"] += alpha * st["rho"]
         x += alpha * p                                                  # k_cg_update
         r -= alpha * w
-        z = apply_blocks(binv, r)
+        z = precond(r)
         rz = float(r @ z)                                               # OP_CG_BETA
         beta = rz / st["rho"]
         if rule == "onestep":
@@ -137,6 +145,36 @@ def pcg(ref, rtol, r_abs, x0=None, maxit=20000, rule="device"):
             return x, it
         p = z + beta * p                                                # k_cg_p
     raise RuntimeError("replica PCG did not converge")
+
+
+def _pcg_fixed(ref, x0, precond, iters, dtype):
+    """the vector recurrence of pcg_impl alone, `iters` times, in the working precision `dtype`"""
+    if dtype == "fsum":
+        import amg_ref
+        wd, A = np.float64, amg_ref._FsumCsr(ref.A_emi)
+    else:
+        wd, A = dtype, ref.A_emi.astype(dtype)
+    b = np.asarray(ref.b_emi).astype(wd)
+    if precond is None:
+        binv = ref.binv_emi.astype(wd)
+
+        def precond(r):
+            return np.einsum("bij,bj->bi", binv, r.reshape(binv.shape[0], -1)).ravel()
+    x = np.zeros(A.shape[0], dtype=wd) if x0 is None else np.asarray(x0).astype(wd).ravel().copy()
+    r = b - A @ x
+    z = precond(r)
+    p = z.copy()
+    rho = z @ r
+    for _ in range(iters):
+        w = A @ p
+        alpha = rho / (p @ w)
+        x = x + alpha * p
+        r = r - alpha * w
+        z = precond(r)
+        rz = r @ z
+        p = z + (rz / rho) * p
+        rho = rz
+    return x
 
 
 def cg_converged(st, r_abs, rtol, it):

@@ -1,0 +1,229 @@
+"""CPU checks of the host replica of the auxiliary-space preconditioner (tests/amg_ref.py), the reference a comparison of the device's
+k-iteration iterates is meant to use: the replica V-cycle is a symmetric positive operator that preconditions, it equals
+P Ac^-1 P^T where that is what it must be, the hand-built hierarchies reach every instantiation of the density-dispatched kernels of csrc/amg.hip, and each of six
+deliberate errors in the replica moves the k-iteration result by at least 100 times the comparison bound (amg_ref.bound).
+No GPU is needed, but knpemidg.amg builds its hierarchies with the host routines of the built library (as tests/test_host.py does)."""
+import os
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+import amg_ref as ar
+
+_HOSTS = {}
+
+
+def _host(names=None):
+    if names not in _HOSTS:
+        _HOSTS[names] = ar.Host("box_P1", names)
+    return _HOSTS[names]
+
+
+def _laplacian(n):
+    T = sp.diags([-1.0, 2.0, -1.0], [-1, 0, 1], shape=(n, n))
+    return (sp.kron(sp.identity(n), T) + sp.kron(T, sp.identity(n)) + 0.01 * sp.identity(n * n)).tocsr()
+
+
+def _cg(A, b, M, tol=1e-10, maxit=2000):
+    x = np.zeros_like(b)
+    r = b.copy()
+    z = M(r)
+    p, rho = z.copy(), r @ z
+    for it in range(1, maxit + 1):
+        w = A @ p
+        alpha = rho / (p @ w)
+        x += alpha * p
+        r -= alpha * w
+        if np.linalg.norm(r) <= tol * np.linalg.norm(b):
+            return x, it
+        z = M(r)
+        rho, rho_old = r @ z, rho
+        p = z + (rho / rho_old) * p
+    return x, maxit
+
+
+def test_replica_vcycle_is_a_symmetric_preconditioner(monkeypatch):
+    from knpemidg import amg
+    monkeypatch.setenv("KNP_AMG_MAXCOARSE", "20")
+    monkeypatch.setenv("KNP_AMG_DEGREE", "2")
+    A = _laplacian(30)
+    levels = amg.build_hierarchy(A)
+    assert len(levels) >= 3, [lv.A.shape[0] for lv in levels]
+    H = ar.store(levels)
+    rng = np.random.default_rng(5)
+    x, y = rng.standard_normal(A.shape[0]), rng.standard_normal(A.shape[0])
+    Vx, Vy = ar.vcycle(H, x), ar.vcycle(H, y)
+    assert abs(x @ Vy - y @ Vx) <= 1e-12 * max(abs(x @ Vy), abs(y @ Vx)), (x @ Vy, y @ Vx)
+    assert x @ Vx > 0 and y @ Vy > 0
+    # several columns: each one from its own right-hand side alone, to the bit
+    XY = ar.vcycle(H, np.stack([x, y]))
+    assert np.array_equal(XY[0], Vx) and np.array_equal(XY[1], Vy)
+    b = rng.standard_normal(A.shape[0])
+    dinv = 1.0 / A.diagonal()
+    x_v, n_v = _cg(A, b, lambda r: ar.vcycle(H, r))
+    x_j, n_j = _cg(A, b, lambda r: dinv * r)
+    assert n_v < n_j and n_v < 40, (n_v, n_j)
+    assert np.abs(x_v - x_j).max() <= 1e-7 * np.abs(x_j).max()
+    # float64 and the extended-precision run agree to rounding
+    hp = ar.vcycle(ar.store(levels, ar.hp_dtype()), x)
+    assert np.abs(Vx - hp).max() <= 1e-13 * np.abs(Vx).max()
+    # the fallback for machines without an 80-bit long double (exactly rounded row sums) is the same operator
+    fs = ar.vcycle(ar.store(levels, "fsum"), x)
+    assert np.abs(fs - hp).max() <= 1e-13 * np.abs(Vx).max()
+
+
+def test_two_levels_without_smoothing_are_the_galerkin_correction():
+    rng = np.random.default_rng(6)
+    levels = ar.synthetic((120, 17), (9,), (4,), (0,), 3.0, 8)
+    Ac = (levels[0].R @ levels[0].A @ levels[0].P).toarray()
+    levels[1].pinv = np.linalg.inv(Ac)                                  # (float64: `store` rounds it as the device does)
+    b = rng.standard_normal(120)
+    P32 = levels[0].P.astype(np.float32).astype(np.float64)
+    want = P32 @ (levels[1].pinv.astype(np.float32).astype(np.float64) @ (P32.T @ b))
+    for dtype in (np.float64, ar.hp_dtype()):
+        got = ar.vcycle(ar.store(levels, dtype), b)
+        assert np.abs(got - want).max() <= 1e-13 * np.abs(want).max()
+    # and with the unrounded inverse it inverts Ac on the range of P
+    e = rng.standard_normal(17)
+    assert np.abs(levels[1].pinv @ (Ac @ e) - e).max() < 1e-9
+
+
+def test_hand_built_hierarchies_reach_every_kernel_instantiation():
+    """LAUNCH_BY_DENSITY / launch_csr_on (csrc/amg.hip) choose G in {1, 4, 8, 64} by the average row length (<= 12, <= 40, <= 96, above:
+    amg_ref.BANDS) and NC = 2 for an even column count; every synthetic hierarchy is meant to run with one column (EMI) and with two
+    (KNP).  No combination is out of reach: k_csr<0> runs on R of every level above a transfer-only or the coarsest one and on P of a
+    transfer-only level, k_csr_first on R above a smoothed level, the other four on A and P of smoothed levels."""
+    assert "KNP_AMG_G4" not in os.environ                               # the library reads it once per process (g4_limit)
+    h = _host()
+    S = ar.synthetic_set(h.ncg, h.scale())
+    got = set()
+    assert set(S) == set(ar.SYNTHETIC)                                  # the list tests/test_gpu_amg.py runs with one and with two columns
+    for name in ar.SYNTHETIC:
+        got |= ar.launches(S[name], 1) | ar.launches(S[name], 2)
+    want = {(k, g, nc) for k in ar.KERNELS for g in (1, 4, 8, 64) for nc in (1, 2)}
+    assert len(want) == 48 and got == want, sorted(want - got)
+    # k_cheb_step needs a smoothed level of degree >= 2 in every band; the top band needs its > 96 entries per row for real
+    top = [lv for lv in S["bands"][:-1] if lv.A.nnz / lv.A.shape[0] > 96.0]
+    assert top and top[0].A.shape[0] >= 130 and top[0].cheb_degree >= 2
+    assert {lv.cheb_degree for name in ("bands", "bands_t0") for lv in S[name][:-1]} == {0, 1, 2, 3}
+    # the production EMI hierarchy of this mesh stays in the two lowest bands: without the hand-built ones 24 instantiations never run
+    prod = ar.launches(h.emi_levels(), 1)
+    assert {g for _, g, _ in prod} <= {1, 4}, sorted(prod)
+
+
+def _targets(levels, mutation, ncol):
+    """where the mutation changes something: levels, or (level, matrix) pairs for drop_tail"""
+    nl = len(levels)
+    if mutation == "drop_tail":
+        t = ar.drop_tail_targets(levels, ncol)
+        assert {l for l, _ in t} == set(range(nl - 1)), ("a level without a row of length 1 modulo U G", t)
+        return t
+    if mutation == "dense_last_row":
+        return [nl - 1]
+    if mutation == "no_prolongation":
+        return list(range(nl - 1))
+    if mutation == "swap_columns":
+        return list(range(nl))
+    return [l for l in range(nl - 1) if levels[l].cheb_degree >= 1]     # a smoothed level: its A is used / it has a post-smoothing step
+
+
+@pytest.mark.parametrize("cheb", [False, True])
+@pytest.mark.parametrize("name", ar.SYNTHETIC)
+def test_mutations_of_the_replica_are_far_above_the_bound(name, cheb):
+    """(a) one level's A not rounded to fp32, (b) the last entry of the rows of length 1 modulo U G lost in one matrix of one level (every
+    level, every matrix that has such rows), (d) one post-smoothing step short, (e) no x += P x_coarse, (f) the dense product without
+    its last row: the EMI result x_3, with either DG smoother, moves by >= 100 bounds on every level where the error can be made."""
+    h = _host()
+    levels = ar.synthetic_set(h.ncg, h.scale())[name]
+    x = ar.emi_xk(h, levels, cheb, 3)
+    bd = ar.bound(x, ar.emi_xk(h, levels, cheb, 3, ar.hp_dtype()))
+    for mutation in ar.MUTATIONS:
+        if mutation == "swap_columns":
+            continue
+        ts = _targets(levels, mutation, 1)
+        assert ts, (name, mutation)
+        for t in ts:
+            moved = np.abs(ar.emi_xk(h, levels, cheb, 3, mut=(mutation, t)) - x).max()
+            assert moved >= 100.0 * bd, (name, mutation, t, moved / bd)
+
+
+@pytest.mark.parametrize("name", ar.SYNTHETIC)
+def test_column_mutations_of_the_replica_are_far_above_the_bound(name):
+    """two species sharing the hierarchy (two interleaved columns, U = 2): (c) the columns' results swapped on one level, and (b) again
+    with the row-length classes of the two-column kernels: the KNP result x_2 of every species moves by >= 100 bounds."""
+    h = _host()
+    levels = ar.synthetic_set(h.ncg, h.scale(knp=True))[name]
+    x = ar.knp_xk(h, levels, 2)
+    xhp = ar.knp_xk(h, levels, 2, ar.hp_dtype())
+    bd = max(ar.bound(x[s], xhp[s]) for s in range(2))
+    for mutation in ("swap_columns", "drop_tail"):
+        for t in _targets(levels, mutation, 2):
+            moved = np.abs(ar.knp_xk(h, levels, 2, mut=(mutation, t)) - x).max(axis=1)
+            assert moved.min() >= 100.0 * bd, (name, mutation, t, moved / bd)
+
+
+def test_one_hierarchy_per_species_and_more_ions():
+    """three solved species (four ions), each with its own hierarchy: the replica's bound holds, the drift-dominated cells keep the
+    per-cell blocks (Peclet number), exchanging two species' hierarchies or breaking one of them moves that species by >= 100 bounds
+    and leaves the others' bits alone; four solved species (five ions) share one hierarchy as four columns."""
+    names = ("K", "Cl", "X", "Na")
+    h = _host(names)
+    assert h.pb.N_ions == 3 and h.peclet() > 0.5
+    S = ar.synthetic_set(h.ncg, h.scale(knp=True))
+    per = [S["bands"], S["bands_t0"], S["coarse_2"]]
+    x = ar.knp_xk(h, per, 2)
+    xhp = ar.knp_xk(h, per, 2, ar.hp_dtype())
+    bd = [ar.bound(x[s], xhp[s]) for s in range(3)]
+    mixed = ar.knp_xk(h, [per[1], per[0], per[2]], 2)
+    # (the spectral bound of the DG smoother is estimated jointly, from the same right-hand sides: species 2 keeps its bits)
+    assert np.array_equal(mixed[2], x[2])
+    assert all(np.abs(mixed[s] - x[s]).max() >= 100.0 * bd[s] for s in (0, 1))
+    broken = ar.knp_xk(h, per, 2, mut=("no_prolongation", 0))
+    assert all(np.abs(broken[s] - x[s]).max() >= 100.0 * bd[s] for s in range(3))
+    h5 = _host(("K", "Cl", "X", "Y", "Na"))
+    assert h5.pb.N_ions == 4 and h5.peclet() > 0.5
+    S5 = ar.synthetic_set(h5.ncg, h5.scale(knp=True))
+    y = ar.knp_xk(h5, S5["bands"], 2)
+    yhp = ar.knp_xk(h5, S5["bands"], 2, ar.hp_dtype())
+    swapped = ar.knp_xk(h5, S5["bands"], 2, mut=("swap_columns", 2))
+    for s in range(4):
+        moved = np.abs(swapped[s] - y[s]).max()
+        assert (moved >= 100.0 * ar.bound(y[s], yhp[s])) == (s < 2), (s, moved)
+
+
+@pytest.mark.parametrize("mesh", ["box_P1", "box_P2", "2D_P1"])
+def test_emi_preconditioner_replica(mesh):
+    """The additive EMI preconditioner z = S(r) + P_dg V(P_dg^T r) of the replica on the three meshes, production hierarchy: with the
+    cell blocks as S it is the sum of its parts; with the two-step Chebyshev S (k_bj_cheb2's closed form) it equals two literal steps
+    of the Chebyshev recurrence on Binv A; both are symmetric, as PCG needs; and the spectral bound the Chebyshev step rests on
+    (bj_lambda_max: 20 power steps from b, times 1.1) lies between 0.9 and 1.1 of the spectral radius of Binv A."""
+    import scipy.sparse.linalg as spla
+    h = _HOSTS.setdefault(mesh, ar.Host(mesh)) if mesh != "box_P1" else _host()
+    ref, levels = h.ref, h.emi_levels()
+    H = ar.store(levels)
+    n, nd = h.pb.ndof, h.nd
+    Bsp = sp.block_diag(list(ref.binv_emi), format="csr")
+    Pd = sp.csr_matrix((np.ones(n), (np.arange(n), h.dg2cg.ravel())), shape=(n, h.ncg))
+    rng = np.random.default_rng(9)
+    r, q = rng.standard_normal(n), rng.standard_normal(n)
+    coarse = lambda v: Pd @ ar.vcycle(H, Pd.T @ v)
+    M0 = ar.EmiPrecond(ref.A_emi, ref.binv_emi, h.dg2cg, H)
+    want = Bsp @ r + coarse(r)
+    assert np.abs(M0(r) - want).max() <= 1e-13 * np.abs(want).max()
+    lmax = ar.bj_lambda_max([ref.A_emi], [ref.binv_emi], [ref.b_emi])
+    true = abs(spla.eigs(Bsp @ ref.A_emi, k=1, which="LM", return_eigenvectors=False, tol=1e-8)[0])
+    assert 0.9 * true <= lmax <= 1.1 * true * (1.0 + 1e-6), (lmax, true)
+    M1 = ar.EmiPrecond(ref.A_emi, ref.binv_emi, h.dg2cg, H, lmax)
+    L = ar._Level()                                                     # Chebyshev on Binv A: `smooth` with A <- Binv A, D <- I
+    L.A, L.dinv, L.rho, L.cheb_lower, L.cheb_degree = (Bsp @ ref.A_emi).tocsr(), np.ones(n), lmax, ar.BJ_LMIN, 2
+    want = ar.smooth(L, None, Bsp @ r, True) + coarse(r)
+    assert np.abs(M1(r) - want).max() <= 1e-12 * np.abs(want).max()
+    for M in (M0, M1):
+        a, b = q @ M(r), r @ M(q)
+        assert abs(a - b) <= 1e-9 * max(abs(a), abs(b)), (mesh, a, b)
+    if mesh != "2D_P1":
+        # k-iteration PCG with it, float64 against extended precision: a usable reference (the 2D mesh's single-level hierarchy is not:
+        # its dense pseudo-inverse carries the 1e8 condition of the isolated subdomain-constant mode)
+        for cheb in (False, True):
+            ar.bound(ar.emi_xk(h, levels, cheb, 3), ar.emi_xk(h, levels, cheb, 3, ar.hp_dtype()))
