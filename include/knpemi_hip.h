@@ -255,6 +255,8 @@ int knp_facet_trace(knp_ctx* ctx, int field, int species, int side, int slot);
  *   per set     : weighted mean of PHI_M, of E[k] and of I_CH[k], k < n_ions      (1 + 2 n_ions values)
  *   per region  : integral of c_k dx, k < n_ions (eliminated ion last), then the volume mean of phi; exact nodal weights
  *                 (P1: vol/(d+1); P2 triangle: 0 on vertices, 1/3 on edge nodes; P2 tetrahedron: -1/20 and 1/5)
+ *   per set     : weighted means of ODE state columns, one per requested state name -- only after knp_rec_add_states, and behind
+ *                 the region block, so that every offset above is what it is without them
  * Sums run in a fixed order and without floating-point atomics: the same inputs give the same bits.
  *  knp_rec_create  : point_cell[n_points] containing cell and point_w[n_points][nd] basis values at the point (P2: local dof order
  *                    of knp_set_tabulation); set s = facets set_facet[set_ptr[s] .. set_ptr[s+1]) with weights set_w (summing to 1
@@ -265,13 +267,41 @@ int knp_facet_trace(knp_ctx* ctx, int field, int species, int side, int slot);
  *  knp_rec_sample  : appends one row for time t; asynchronous, on the context's stream; -5 when `capacity` rows wait to be read
  *  knp_rec_read    : synchronises, copies the waiting rows (rows_out[capacity][channels], t_out[capacity]; *n_rows of them are
  *                    valid) in one device-to-host transfer and empties the buffer
- *  knp_rec_channels: doubles per row (< 0 without a recorder) */
+ *  knp_rec_channels: doubles per row (< 0 without a recorder; state channels included once knp_rec_add_states has run)
+ *
+ * Optional, after knp_rec_create (which alone leaves rows, offsets and launches exactly as described above):
+ *  knp_rec_add_states: appends n_channels channels BEHIND the region block, channel s = sum over its entries
+ *                    i in [chan_ptr[s], chan_ptr[s+1]) of entry_w[i] * states(entry_handle[i])[entry_row[i]][entry_col[i]] -- weighted
+ *                    means of ODE state columns such as the gating variables n, m, h over a membrane set that may span several
+ *                    handles.  Summed in list order by one workgroup per channel (k_rec_states), one launch per sample.  Every entry
+ *                    is checked before anything is uploaded: handle exists, 0 <= row < n, 0 <= col < ns, and the weights of a channel
+ *                    sum to 1 within 1e-12; a failure leaves the recorder as it was.  Not while samples wait to be read.
+ *                    Timing: the solver steps the membrane ODEs of step k before the PDE solves of step k, so the row sampled at the
+ *                    end of step k holds the states AFTER ODE step k, the pairing the reference's saved fields have.
+ *  knp_rec_add_map : per-facet activation map of the n given membrane facets (caller's ids), persistent on the device: prev, t_act,
+ *                    t_repol, peak, t_peak (doubles) and n_up (int32).  Per sample (k_rec_map, one thread per facet, one launch), with
+ *                    v0 = prev at the previous sample's time t0 and v1 = PHI_M[f] at this sample's time t1:
+ *                      v0 < thr && v1 >= thr                                   : ++n_up; t_act = t0 + (thr - v0) / (v1 - v0) (t1 - t0) if unset
+ *                      t_act set, t_repol unset, v0 >= thr_r && v1 < thr_r     : t_repol by the same interpolation with thr_r
+ *                      v1 > peak                                               : peak = v1, t_peak = t1
+ *                      prev = v1
+ *                    t0 lives on the device next to the row counter; a refused sample (buffer full) changes nothing.  A facet that is
+ *                    not a membrane facet, n < 1 or a non-finite threshold fails before anything is uploaded.
+ *  knp_rec_map_arm : t_act = t_repol = NaN, n_up = 0, peak = prev = PHI_M now, t_peak = t0; asynchronous.  knp_rec_sample refuses to
+ *                    sample an unarmed map.
+ *  knp_rec_map_read: synchronises and copies t_act, t_repol, peak, t_peak, n_up ([n] each) in one device-to-host transfer; never
+ *                    part of knp_rec_read */
 int knp_rec_create(knp_ctx* ctx, int64_t capacity, int64_t n_points, const int32_t* point_cell, const double* point_w,
                    int64_t n_sets, const int64_t* set_ptr, const int32_t* set_facet, const double* set_w,
                    int n_regions, const uint8_t* region, const double* vol);
 int knp_rec_sample(knp_ctx* ctx, double t);
 int knp_rec_read(knp_ctx* ctx, int64_t* n_rows, double* t_out, double* rows_out);
 int64_t knp_rec_channels(knp_ctx* ctx);
+int knp_rec_add_states(knp_ctx* ctx, int64_t n_channels, const int64_t* chan_ptr, const int32_t* entry_handle, const int64_t* entry_row,
+                       const int32_t* entry_col, const double* entry_w);
+int knp_rec_add_map(knp_ctx* ctx, int64_t n, const int32_t* facets, double threshold, double repolarisation);
+int knp_rec_map_arm(knp_ctx* ctx, double t0);
+int knp_rec_map_read(knp_ctx* ctx, int64_t n, double* t_act, double* t_repol, double* peak, double* t_peak, int32_t* n_up);
 int knp_rec_destroy(knp_ctx* ctx);
 
 /* ---- membrane ODEs: batched device integrator replacing the per-facet LSODA loop of

@@ -252,6 +252,15 @@ static OdeSet* get_set(knp_ctx* c, int handle) {
     return &it->second[handle];
 }
 
+// state table of a handle for the recorder's state channels (record.hip): device pointer [n][ns]; false = no such handle.  The
+// pointer stays valid until the context is destroyed (tables are never reallocated).
+bool ode_state_table(knp_ctx* c, int handle, const double** states, int64_t* n, int* ns) {
+    const OdeSet* S = get_set(c, handle);
+    if (!S) return false;
+    *states = S->states; *n = S->n; *ns = S->ns;
+    return true;
+}
+
 static void rtc_unload_all(knp_ctx* c);
 
 void ode_destroy_all(knp_ctx* c) {

@@ -1,18 +1,31 @@
 // Time-series recorder: point probes, membrane-set means and region integrals sampled on the device right after step III, so that
 // a run without field output still yields the traces the reference's figure scripts read back from results.h5
 // (examples/idealized-geometries/make_figures_3D.py:28-168).  One sample = one row of n_ch doubles + its time in a small device
-// buffer; the row counter lives on the device, so a sample is four launches on the solver's stream and no host synchronisation.
+// buffer; the row counter lives on the device, so a sample is four launches on the solver's stream (one more each for state
+// channels and a membrane map) and no host synchronisation.
 //
 // Row layout:  [probe][phi, c_0 .. c_{n_sys-1}, c_elim]  |  [set][phi_M, E_0 .. E_{n_ions-1}, I_ch_0 .. I_ch_{n_ions-1}]  |
 //              [region][int c_0 dx .. int c_{n_ions-1} dx, volume mean of phi]
+//              | [set][state_0 .. state_{n_names-1}]   (only after knp_rec_add_states: area-weighted means of ODE state columns,
+//              e.g. the gating variables n, m, h; behind the region block, so that every other offset stays where it is)
 // Every sum runs in a fixed order (thread-strided partial sums -> wave shuffle -> LDS -> one value; no floating-point atomics), so
 // two runs with the same inputs give the same bits.
+//
+// Timing of the state channels: the solver steps the membrane ODEs of step k before the PDE solves of step k, so the row sampled at
+// the end of step k sees the states AFTER ODE step k -- the pairing the reference's saved fields have.
+//
+// Per-facet membrane map (knp_rec_add_map): persistent per selected facet -- previous phi_M, activation time (first upward crossing
+// of the threshold, linearly interpolated between two samples), repolarisation time (first downward crossing after it), peak and
+// its time, number of upward crossings.  One more launch per sample, a pure stream without reductions; read back on request only
+// (knp_rec_map_read).
 #include "../../include/knpemi_hip.h"
 #include "knpemi_internal.hpp"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 double* knp_field_ptr(knp_ctx* c, int field, int64_t* n);   // abi.hip
+bool ode_state_table(knp_ctx* c, int handle, const double** states, int64_t* n, int* ns);   // ode.hip
 
 #define KNP_REC_MAX_REGIONS 16
 #define KNP_REC_FINISH_BLOCK 1024
@@ -35,6 +48,21 @@ struct Recorder {
     double* buf = nullptr;          // rows [capacity][n_ch], then t [capacity]
     int* count = nullptr;           // rows written since the last read
     std::vector<double> host;       // staging of one read
+    // state channels (knp_rec_add_states), optional
+    int64_t n_base = 0;             // channels of knp_rec_create; the state channels follow them in the row
+    int64_t n_sch = 0;
+    int64_t* st_ptr = nullptr;      // [n_sch + 1]
+    const double** st_src = nullptr;   // per entry the address of its value in an ODE state table
+    double* st_w = nullptr;
+    // per-facet map (knp_rec_add_map), optional
+    int64_t n_map = 0, map_k = 0;   // map_k: samples since arming; its parity names the slot of t_hist with the previous sample's time
+    bool map_armed = false;
+    double thr = 0.0, thr_r = 0.0;
+    int32_t* map_facet = nullptr;   // [n_map]
+    double* map_prev = nullptr;     // [n_map] phi_M at the previous sample
+    double* map_out = nullptr;      // t_act, t_repol, peak, t_peak [4][n_map], then n_up int32 [n_map]: one block, one transfer
+    double* t_hist = nullptr;       // [2] times of the last two samples, next to the row counter: sampling never synchronises
+    std::vector<double> map_host;
 };
 
 std::map<knp_ctx*, Recorder> g_rec;
@@ -201,6 +229,59 @@ __global__ __launch_bounds__(KNP_REC_FINISH_BLOCK) void k_rec_finish(int64_t n_b
     }
 }
 
+// one workgroup per state channel: sum_i w_i * (state value of entry i), the workgroup strides over the entries in list order
+__global__ __launch_bounds__(KNP_BLOCK) void k_rec_states(const int64_t* __restrict__ ptr, const double* const* __restrict__ src,
+                                                          const double* __restrict__ w, const int* __restrict__ count, int64_t capacity,
+                                                          int64_t n_ch, int64_t ch0, double* __restrict__ rows) {
+    __shared__ double lds[KNP_BLOCK / 64];
+    const int64_t row = *count;
+    if (row >= capacity) return;
+    const int s = blockIdx.x;
+    const int64_t lo = ptr[s], hi = ptr[s + 1];
+    double acc = 0.0;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += KNP_BLOCK) acc += w[i] * *src[i];
+    const double v = rec_block_sum(acc, lds);
+    if (threadIdx.x == 0) rows[row * n_ch + ch0 + s] = v;
+}
+
+// arming of the map: prev = peak = phi_M now, t_peak = t0, no crossing seen yet
+__global__ __launch_bounds__(KNP_BLOCK) void k_rec_map_arm(int64_t n, const int32_t* __restrict__ facet, const double* __restrict__ phiM, double t0,
+                                                           double* __restrict__ t_hist, double* __restrict__ prev, double* __restrict__ out,
+                                                           int32_t* __restrict__ n_up) {
+    const int64_t i = (int64_t)blockIdx.x * KNP_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double v = phiM[facet[i]], nan = __builtin_nan("");
+    prev[i] = v;
+    out[i] = nan; out[n + i] = nan; out[2 * n + i] = v; out[3 * n + i] = t0;
+    n_up[i] = 0;
+    if (i == 0) { t_hist[0] = t0; t_hist[1] = t0; }
+}
+
+// one thread per selected facet: crossings between the previous sample (v0 at t0) and this one (v1 at t1), peak, prev <- v1.
+// t0 is read from t_hist[slot] and t1 goes to the other slot, which the next sample reads: no thread reads what another writes.
+// A refused sample (buffer full) leaves everything as it is, prev included.
+__global__ __launch_bounds__(KNP_BLOCK) void k_rec_map(int64_t n, const int32_t* __restrict__ facet, const double* __restrict__ phiM, double thr,
+                                                       double thr_r, double t1, double* __restrict__ t_hist, int slot,
+                                                       const int* __restrict__ count, int64_t capacity, double* __restrict__ prev,
+                                                       double* __restrict__ out, int32_t* __restrict__ n_up) {
+    const int64_t i = (int64_t)blockIdx.x * KNP_BLOCK + threadIdx.x;
+    if (i >= n || *count >= capacity) return;
+    const double t0 = t_hist[slot];
+    if (i == 0) t_hist[slot ^ 1] = t1;
+    const double v0 = prev[i], v1 = phiM[facet[i]];
+    double ta = out[i];
+    if (v0 < thr && v1 >= thr) {
+        n_up[i] += 1;
+        if (isnan(ta)) {
+            ta = t0 + (thr - v0) / (v1 - v0) * (t1 - t0);
+            out[i] = ta;
+        }
+    }
+    if (!isnan(ta) && isnan(out[n + i]) && v0 >= thr_r && v1 < thr_r) out[n + i] = t0 + (thr_r - v0) / (v1 - v0) * (t1 - t0);
+    if (v1 > out[2 * n + i]) { out[2 * n + i] = v1; out[3 * n + i] = t1; }
+    prev[i] = v1;
+}
+
 template <typename T> int rec_upload(knp_ctx* c, T** dst, const T* src, size_t n) {
     HIPCHK(c, hipMalloc((void**)dst, std::max<size_t>(n, 1) * sizeof(T)));
     if (n) HIPCHK(c, hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
@@ -210,6 +291,14 @@ template <typename T> int rec_upload(knp_ctx* c, T** dst, const T* src, size_t n
 void rec_free(Recorder& R) {
     hipFree(R.point_cell); hipFree(R.point_w); hipFree(R.set_ptr); hipFree(R.set_facet); hipFree(R.set_w); hipFree(R.region);
     hipFree(R.vol); hipFree(R.inv_rvol); hipFree(R.partials); hipFree(R.buf); hipFree(R.count);
+    hipFree(R.st_ptr); hipFree(R.st_src); hipFree(R.st_w);
+    hipFree(R.map_facet); hipFree(R.map_prev); hipFree(R.map_out); hipFree(R.t_hist);
+}
+
+Recorder* rec_find(knp_ctx* c, const char* who) {
+    auto it = g_rec.find(c);
+    if (it == g_rec.end()) { c->err = std::string(who) + ": no recorder (knp_rec_create)"; return nullptr; }
+    return &it->second;
 }
 
 }  // namespace
@@ -272,6 +361,7 @@ int knp_rec_create(knp_ctx* c, int64_t capacity, int64_t n_points, const int32_t
     Recorder R;
     R.capacity = capacity; R.n_points = n_points; R.n_sets = n_sets; R.n_regions = n_regions;
     R.n_ch = n_points * (n_ions + 1) + n_sets * (1 + 2 * n_ions) + (int64_t)n_regions * (n_ions + 1);
+    R.n_base = R.n_ch;
     R.n_blk = n_regions ? (m.nc_owned + KNP_BLOCK - 1) / KNP_BLOCK : 0;
     int rc = 0;
     rc |= rec_upload(c, &R.point_cell, point_cell, (size_t)n_points);
@@ -297,12 +387,142 @@ int knp_rec_create(knp_ctx* c, int64_t capacity, int64_t n_points, const int32_t
     return 0;
 }
 
+int knp_rec_add_states(knp_ctx* c, int64_t n_channels, const int64_t* chan_ptr, const int32_t* entry_handle, const int64_t* entry_row,
+                       const int32_t* entry_col, const double* entry_w) {
+    if (!c) return -1;
+    Recorder* Rp = rec_find(c, "knp_rec_add_states");
+    if (!Rp) return -1;
+    Recorder& R = *Rp;
+    // ---- validation, all of it before the first upload: no entry may address anything outside its state table ------------------
+    if (R.rows_host) { c->err = "knp_rec_add_states: samples are waiting (call it right after knp_rec_create)"; return -1; }
+    if (n_channels < 1 || n_channels > (int64_t(1) << 20)) { c->err = "knp_rec_add_states: channel count out of range"; return -1; }
+    if (!chan_ptr || !entry_handle || !entry_row || !entry_col || !entry_w) { c->err = "knp_rec_add_states: null table"; return -1; }
+    if (chan_ptr[0] != 0) { c->err = "knp_rec_add_states: chan_ptr must start at 0"; return -1; }
+    for (int64_t s = 0; s < n_channels; ++s)
+        if (chan_ptr[s + 1] <= chan_ptr[s]) { c->err = "knp_rec_add_states: channel " + std::to_string(s) + " is empty"; return -1; }
+    const int64_t ne = chan_ptr[n_channels];
+    std::vector<const double*> src((size_t)ne);
+    for (int64_t s = 0; s < n_channels; ++s) {
+        double wsum = 0.0;
+        for (int64_t i = chan_ptr[s]; i < chan_ptr[s + 1]; ++i) {
+            const double* tab = nullptr;
+            int64_t n = 0;
+            int ns = 0;
+            const std::string where = "knp_rec_add_states: channel " + std::to_string(s) + ", entry " + std::to_string(i - chan_ptr[s]) + ": ";
+            if (!ode_state_table(c, entry_handle[i], &tab, &n, &ns)) { c->err = where + "unknown ODE handle " + std::to_string(entry_handle[i]); return -1; }
+            if (entry_row[i] < 0 || entry_row[i] >= n) {
+                c->err = where + "row " + std::to_string(entry_row[i]) + " outside the handle's " + std::to_string(n) + " rows";
+                return -1;
+            }
+            if (entry_col[i] < 0 || entry_col[i] >= ns) {
+                c->err = where + "column " + std::to_string(entry_col[i]) + " outside the handle's " + std::to_string(ns) + " states";
+                return -1;
+            }
+            src[(size_t)i] = tab + entry_row[i] * ns + entry_col[i];
+            wsum += entry_w[i];
+        }
+        if (!(std::fabs(wsum - 1.0) <= 1e-12)) { c->err = "knp_rec_add_states: the weights of channel " + std::to_string(s) + " do not sum to 1"; return -1; }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));        // nothing may still write into the row buffer that is replaced below
+    int64_t* d_ptr = nullptr;
+    const double** d_src = nullptr;
+    double *d_w = nullptr, *d_buf = nullptr;
+    const int64_t n_ch = R.n_base + n_channels;
+    const size_t nbuf = (size_t)R.capacity * (size_t)(n_ch + 1);
+    int rc = 0;
+    rc |= rec_upload(c, &d_ptr, chan_ptr, (size_t)n_channels + 1);
+    rc |= rec_upload(c, &d_src, src.data(), (size_t)ne);
+    rc |= rec_upload(c, &d_w, entry_w, (size_t)ne);
+    if (!rc && (hipMalloc((void**)&d_buf, sizeof(double) * nbuf) != hipSuccess || hipMemset(d_buf, 0, sizeof(double) * nbuf) != hipSuccess)) rc = -2;
+    if (rc) {
+        hipFree(d_ptr); hipFree(d_src); hipFree(d_w); hipFree(d_buf);
+        if (c->err.empty()) c->err = "knp_rec_add_states: device allocation failed";
+        return -2;
+    }
+    hipFree(R.st_ptr); hipFree(R.st_src); hipFree(R.st_w); hipFree(R.buf);        // a second call replaces the first
+    R.st_ptr = d_ptr; R.st_src = d_src; R.st_w = d_w; R.buf = d_buf;
+    R.n_sch = n_channels;
+    R.n_ch = n_ch;
+    R.host.assign(nbuf, 0.0);
+    return 0;
+}
+
+int knp_rec_add_map(knp_ctx* c, int64_t n, const int32_t* facets, double threshold, double repolarisation) {
+    if (!c) return -1;
+    Recorder* Rp = rec_find(c, "knp_rec_add_map");
+    if (!Rp) return -1;
+    Recorder& R = *Rp;
+    if (n < 1 || !facets) { c->err = "knp_rec_add_map: empty facet selection"; return -1; }
+    if (!std::isfinite(threshold) || !std::isfinite(repolarisation)) { c->err = "knp_rec_add_map: thresholds must be finite"; return -1; }
+    for (int64_t i = 0; i < n; ++i)
+        if (facets[i] < 0 || facets[i] >= c->m.nf || !c->h_mf_mask[(size_t)facets[i]]) {
+            c->err = "knp_rec_add_map: facet " + std::to_string(facets[i]) + " is not a membrane facet";
+            return -1;
+        }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int32_t* d_facet = nullptr;
+    double *d_prev = nullptr, *d_out = nullptr, *d_t = nullptr;
+    int rc = rec_upload(c, &d_facet, facets, (size_t)n);
+    if (!rc && (hipMalloc((void**)&d_prev, sizeof(double) * (size_t)n) != hipSuccess ||
+                hipMalloc((void**)&d_out, (4 * sizeof(double) + sizeof(int32_t)) * (size_t)n) != hipSuccess ||
+                hipMalloc((void**)&d_t, 2 * sizeof(double)) != hipSuccess)) rc = -2;
+    if (rc) {
+        hipFree(d_facet); hipFree(d_prev); hipFree(d_out); hipFree(d_t);
+        if (c->err.empty()) c->err = "knp_rec_add_map: device allocation failed";
+        return -2;
+    }
+    hipFree(R.map_facet); hipFree(R.map_prev); hipFree(R.map_out); hipFree(R.t_hist);
+    R.map_facet = d_facet; R.map_prev = d_prev; R.map_out = d_out; R.t_hist = d_t;
+    R.n_map = n; R.map_k = 0; R.map_armed = false;
+    R.thr = threshold; R.thr_r = repolarisation;
+    R.map_host.assign((size_t)(4 * n + (n + 1) / 2), 0.0);
+    return 0;
+}
+
+int knp_rec_map_arm(knp_ctx* c, double t0) {
+    if (!c) return -1;
+    Recorder* Rp = rec_find(c, "knp_rec_map_arm");
+    if (!Rp) return -1;
+    Recorder& R = *Rp;
+    if (!R.n_map) { c->err = "knp_rec_map_arm: no map (knp_rec_add_map)"; return -1; }
+    if (!std::isfinite(t0)) { c->err = "knp_rec_map_arm: the time must be finite"; return -1; }
+    hipLaunchKernelGGL(k_rec_map_arm, dim3((unsigned)((R.n_map + KNP_BLOCK - 1) / KNP_BLOCK)), dim3(KNP_BLOCK), 0, c->stream, R.n_map, R.map_facet,
+                       knp_field_ptr(c, KNP_F_PHI_M, nullptr), t0, R.t_hist, R.map_prev, R.map_out, reinterpret_cast<int32_t*>(R.map_out + 4 * R.n_map));
+    HIPCHK(c, hipGetLastError());
+    R.map_k = 0;
+    R.map_armed = true;
+    return 0;
+}
+
+int knp_rec_map_read(knp_ctx* c, int64_t n, double* t_act, double* t_repol, double* peak, double* t_peak, int32_t* n_up) {
+    if (!c) return -1;
+    Recorder* Rp = rec_find(c, "knp_rec_map_read");
+    if (!Rp) return -1;
+    Recorder& R = *Rp;
+    if (!R.n_map) { c->err = "knp_rec_map_read: no map (knp_rec_add_map)"; return -1; }
+    if (!R.map_armed) { c->err = "knp_rec_map_read: the map is not armed (knp_rec_map_arm)"; return -1; }
+    if (n != R.n_map || !t_act || !t_repol || !peak || !t_peak || !n_up) { c->err = "knp_rec_map_read: outputs must hold one entry per map facet"; return -1; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t nn = (size_t)n;
+    HIPCHK(c, hipMemcpy(R.map_host.data(), R.map_out, (4 * sizeof(double) + sizeof(int32_t)) * nn, hipMemcpyDeviceToHost));
+    const double* h = R.map_host.data();
+    std::memcpy(t_act, h, sizeof(double) * nn);
+    std::memcpy(t_repol, h + nn, sizeof(double) * nn);
+    std::memcpy(peak, h + 2 * nn, sizeof(double) * nn);
+    std::memcpy(t_peak, h + 3 * nn, sizeof(double) * nn);
+    std::memcpy(n_up, h + 4 * nn, sizeof(int32_t) * nn);
+    return 0;
+}
+
 int knp_rec_sample(knp_ctx* c, double t) {
     if (!c) return -1;
     auto it = g_rec.find(c);
     if (it == g_rec.end()) { c->err = "knp_rec_sample: no recorder (knp_rec_create)"; return -1; }
     Recorder& R = it->second;
     if (R.rows_host >= R.capacity) { c->err = "knp_rec_sample: buffer full (knp_rec_read empties it)"; return -5; }
+    if (R.n_map && !R.map_armed) { c->err = "knp_rec_sample: the membrane map is not armed (knp_rec_map_arm)"; return -1; }
     const MeshDev& m = c->m;
     const int n_ions = c->p.n_ions, n_sys = c->p.n_sys, nfld = n_ions + 1, nd = c->nd;
     const int64_t ndof = m.nc * nd;
@@ -332,6 +552,15 @@ int knp_rec_sample(knp_ctx* c, double t) {
         else if (nd == 6) REC_REGIONS(6);
         else REC_REGIONS(10);
 #undef REC_REGIONS
+    }
+    if (R.n_sch)
+        hipLaunchKernelGGL(k_rec_states, dim3((unsigned)R.n_sch), dim3(KNP_BLOCK), 0, c->stream, R.st_ptr, R.st_src, R.st_w, R.count, R.capacity, R.n_ch,
+                           R.n_base, rows);
+    if (R.n_map) {
+        hipLaunchKernelGGL(k_rec_map, dim3((unsigned)((R.n_map + KNP_BLOCK - 1) / KNP_BLOCK)), dim3(KNP_BLOCK), 0, c->stream, R.n_map, R.map_facet,
+                           knp_field_ptr(c, KNP_F_PHI_M, nullptr), R.thr, R.thr_r, t, R.t_hist, (int)(R.map_k & 1), R.count, R.capacity, R.map_prev,
+                           R.map_out, reinterpret_cast<int32_t*>(R.map_out + 4 * R.n_map));
+        ++R.map_k;
     }
     hipLaunchKernelGGL(k_rec_finish, dim3(1), dim3(KNP_REC_FINISH_BLOCK), 0, c->stream, R.n_blk, R.n_regions, nfld, R.partials, R.inv_rvol, t, R.count,
                        R.capacity, R.n_ch, ch_reg, rows, times);

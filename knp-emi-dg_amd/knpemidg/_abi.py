@@ -121,6 +121,10 @@ SIGNATURES = {
     "knp_rec_read": (C.c_int, [_ctxp, _i64p, _f64p, _f64p]),
     "knp_rec_channels": (C.c_int64, [_ctxp]),
     "knp_rec_destroy": (C.c_int, [_ctxp]),
+    "knp_rec_add_states": (C.c_int, [_ctxp, C.c_int64, _i64p, _i32p, _i64p, _i32p, _f64p]),
+    "knp_rec_add_map": (C.c_int, [_ctxp, C.c_int64, _i32p, C.c_double, C.c_double]),
+    "knp_rec_map_arm": (C.c_int, [_ctxp, C.c_double]),
+    "knp_rec_map_read": (C.c_int, [_ctxp, C.c_int64, _f64p, _f64p, _f64p, _f64p, _i32p]),
 }
 
 _lib = None
@@ -888,6 +892,36 @@ class Device:
         self._chk(self.lib.knp_rec_read(self.ctx, C.byref(n), _p(t, _f64p), _p(rows, _f64p)), "knp_rec_read")
         return t[:n.value].copy(), rows[:n.value].copy()
 
+    def rec_add_states(self, chan_ptr, entry_handle, entry_row, entry_col, entry_w):
+        """State channels behind the region block (knp_rec_add_states): channel s = sum of entry_w * state table value over its
+        entries.  Returns the new number of channels of a row."""
+        cp = np.ascontiguousarray(chan_ptr, dtype=np.int64)
+        eh = np.ascontiguousarray(entry_handle, dtype=np.int32)
+        er = np.ascontiguousarray(entry_row, dtype=np.int64)
+        ec = np.ascontiguousarray(entry_col, dtype=np.int32)
+        ew = np.ascontiguousarray(entry_w, dtype=np.float64)
+        assert cp.ndim == 1 and len(cp) >= 1 and eh.shape == er.shape == ec.shape == ew.shape == (int(cp[-1]),)
+        self._chk(self.lib.knp_rec_add_states(self.ctx, len(cp) - 1, _p(cp, _i64p), _p(eh, _i32p), _p(er, _i64p), _p(ec, _i32p),
+                                              _p(ew, _f64p)), "knp_rec_add_states")
+        self._rec_channels = int(self.lib.knp_rec_channels(self.ctx))
+        return self._rec_channels
+
+    def rec_add_map(self, facets, threshold, repolarisation):
+        """Per-facet activation map of the given membrane facets (knp_rec_add_map); arm it before the first sample."""
+        f = np.ascontiguousarray(facets, dtype=np.int32)
+        self._chk(self.lib.knp_rec_add_map(self.ctx, len(f), _p(f, _i32p), float(threshold), float(repolarisation)), "knp_rec_add_map")
+        self._rec_map_n = len(f)
+
+    def rec_map_arm(self, t0):
+        self._chk(self.lib.knp_rec_map_arm(self.ctx, float(t0)), "knp_rec_map_arm")
+
+    def rec_map_read(self):
+        """(activation time, repolarisation time, peak, peak time, upward crossings) per map facet; synchronises."""
+        n = getattr(self, "_rec_map_n", 0)
+        out = [np.empty(n) for _ in range(4)] + [np.empty(n, dtype=np.int32)]
+        self._chk(self.lib.knp_rec_map_read(self.ctx, n, *[_p(a, _f64p) for a in out[:4]], _p(out[4], _i32p)), "knp_rec_map_read")
+        return tuple(out)
+
     def rec_destroy(self):
         self._chk(self.lib.knp_rec_destroy(self.ctx), "knp_rec_destroy")
 
@@ -906,7 +940,7 @@ for _name in ("close", "set_params", "set_mms", "upload", "download", "copy_fiel
               "knp_apply", "emi_rhs", "knp_rhs", "emi_solve", "knp_solve", "step_updates", "picard_updates", "max_abs_diff",
               "nernst", "sync", "timer_begin", "timer_end", "bench_apply", "ode_table", "ode_step", "ode_set_stimulus",
               "amg_upload", "amg_interface", "halo_exchange", "knp_load_measure", "apply_timing_read", "comm_init", "set_interior", "rec_sample",
-              "rec_read"):
+              "rec_read", "rec_add_states", "rec_map_arm", "rec_map_read"):
     setattr(Device, _name, _flushing(getattr(Device, _name)))
 
 

@@ -139,6 +139,11 @@ class MembraneModel:
         return self._dev is not None
 
     @property
+    def handle(self):
+        """Handle of the device ODE tables (None while the model lives on the host)."""
+        return self._handle
+
+    @property
     def states(self):
         """ODE states [nodes, n_states] (a snapshot when device backed; assign the whole array to write)."""
         if self.on_device:

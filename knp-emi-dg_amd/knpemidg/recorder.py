@@ -6,6 +6,11 @@ subdomains, all from the full fields that `save_fields=True, sf=1` wrote at ever
 `Recorder`; after step III of every time step one row is appended to a small device buffer, which comes back in one copy per
 `capacity` steps.  The host part below only prepares tables: containing cell and basis values of every probe, facet lists with
 area weights, a region id and the volume of every cell.
+
+Two optional additions serve the reference's other figure scripts (examples/rat-neuron/make_figures_rat_neuron.py:238-315, 423-692):
+`membrane_states` appends the area-weighted means of ODE state columns (the gating variables n, m, h) over the membrane sets, read
+straight from the state tables on the device, and `membrane_map` keeps a per-facet activation map (activation and repolarisation
+time, peak, number of activations) from which `Recorder.conduction_velocity` follows.
 """
 import numpy as np
 
@@ -119,6 +124,62 @@ def select_box(mesh, facets, lo, hi):
     return facets[inside]
 
 
+def model_has_state(ode, name):
+    try:
+        ode.state_indices(name)
+    except (ValueError, KeyError):
+        return False
+    return True
+
+
+def state_entries(set_facets, set_areas, models, names):
+    """Entry lists of the state channels, channel = set * len(names) + name (knp_rec_add_states).
+
+    models: the membrane models -- anything with `facets` (ascending facet ids; row r of the state table belongs to facets[r]),
+    `ode.state_indices(name)` (ValueError for a name the model does not have) and `handle` (the device ODE handle).
+    Channel (s, q) is the mean of state q over those facets of set s whose model has a state q, in the set's facet order, weighted
+    by the facet areas renormalised over exactly those facets.  Returns (chan_ptr, handle, row, col, weight); ValueError naming
+    the set and the state when no facet of the set has it."""
+    owner, row_of = {}, {}
+    for k, m in enumerate(models):
+        for r, f in enumerate(np.asarray(m.facets, dtype=np.int64)):
+            owner[int(f)] = k
+            row_of[int(f)] = r
+    cols = [{q: (m.ode.state_indices(q) if model_has_state(m.ode, q) else None) for q in names} for m in models]
+    ptr, eh, er, ec, ew = [0], [], [], [], []
+    for s, (facets, areas) in enumerate(zip(set_facets, set_areas)):
+        facets = np.asarray(facets, dtype=np.int64)
+        areas = np.asarray(areas, dtype=np.float64)
+        for q in names:
+            keep = [i for i, f in enumerate(facets) if int(f) in owner and cols[owner[int(f)]][q] is not None]
+            if not keep:
+                raise ValueError("membrane set %d: no facet of the set belongs to a membrane model with a state '%s'" % (s, q))
+            w = areas[keep] / areas[keep].sum()
+            for i, wi in zip(keep, w):
+                k = owner[int(facets[i])]
+                eh.append(int(models[k].handle))
+                er.append(row_of[int(facets[i])])
+                ec.append(int(cols[k][q]))
+                ew.append(float(wi))
+            ptr.append(len(eh))
+    return (np.asarray(ptr, dtype=np.int64), np.asarray(eh, dtype=np.int32), np.asarray(er, dtype=np.int64),
+            np.asarray(ec, dtype=np.int32), np.asarray(ew, dtype=np.float64))
+
+
+def first_upward_crossing(t, v, threshold):
+    """Time at which the sampled trace v(t) first goes from below `threshold` to at or above it, linearly interpolated between the
+    two samples; NaN if it never does."""
+    t, v = np.asarray(t, dtype=np.float64), np.asarray(v, dtype=np.float64)
+    k = np.nonzero((v[:-1] < threshold) & (v[1:] >= threshold))[0]
+    if not len(k):
+        return float("nan")
+    k = int(k[0])
+    return float(t[k] + (threshold - v[k]) / (v[k + 1] - v[k]) * (t[k + 1] - t[k]))
+
+
+MAP_FIELDS = ("activation_time", "repolarisation_time", "peak", "peak_time", "n_activations")
+
+
 def _is_box(entry, d):
     try:
         a = np.asarray(entry, dtype=np.float64)
@@ -135,10 +196,14 @@ class Recorder:
     regions       True: one region per distinct subdomain tag, ascending; False / None: none; or an array [nc] of region ids
                   (255 = not counted)
     ion_names     names in ion_list order (the eliminated ion last)
+    membrane_states  names of ODE states (as the membrane models declare them), averaged over every membrane set; the device tables
+                  follow with `attach_states(models)` once the membrane models exist
+    membrane_map  dict(threshold=0.0, repolarisation=None, tags=None): per-facet activation map, in the units of phi_M;
+                  repolarisation None = the threshold, tags None = every membrane facet, else the facets with those surface tags
     """
 
     def __init__(self, mesh, cell_tags, facet_tags, degree, ion_names, points=None, membrane_sets=None, regions=True, capacity=256,
-                 point_tags=None, membrane_tags=None):
+                 point_tags=None, membrane_tags=None, membrane_states=None, membrane_map=None):
         self.mesh = mesh
         self.cell_tags = np.asarray(cell_tags)
         self.facet_tags = np.asarray(facet_tags)
@@ -176,6 +241,27 @@ class Recorder:
         # membrane sets: resolved once the membrane tags are known
         self._set_spec = list(membrane_sets) if membrane_sets is not None else []
         self.set_facets = None
+        self.state_names = [str(q) for q in membrane_states] if membrane_states else []
+        if len(set(self.state_names)) != len(self.state_names) or set(self.state_names) & set(self.channel_names()[1]):
+            raise ValueError("membrane_states must be distinct and differ from the other membrane channels")
+        if self.state_names and not self._set_spec:
+            raise ValueError("membrane_states need at least one membrane set")
+        self._states_on_device = False
+        self._map_spec = None
+        self.map_facets = None
+        if membrane_map is not None:
+            spec = dict(threshold=0.0, repolarisation=None, tags=None)
+            unknown = set(membrane_map) - set(spec)
+            if unknown:
+                raise ValueError("membrane_map: unknown key %s" % sorted(unknown)[0])
+            spec.update(membrane_map)
+            if spec["repolarisation"] is None:
+                spec["repolarisation"] = spec["threshold"]
+            spec["threshold"], spec["repolarisation"] = float(spec["threshold"]), float(spec["repolarisation"])
+            if not (np.isfinite(spec["threshold"]) and np.isfinite(spec["repolarisation"])):
+                raise ValueError("membrane_map: threshold and repolarisation must be finite")
+            self._map_spec = spec
+        self._armed = False
         if membrane_tags is not None:
             self.resolve_sets(membrane_tags)
         self.dev = None
@@ -204,6 +290,19 @@ class Recorder:
         for f in out:
             a = facet_areas(mesh, f)
             self.set_weights.append(a / a.sum())
+        if self._map_spec is not None:
+            tags = self._map_spec["tags"]
+            if tags is None:
+                sel = mem
+            else:
+                tags = [int(x) for x in np.atleast_1d(tags)]
+                bad = [x for x in tags if x not in [int(y) for y in membrane_tags]]
+                if bad:
+                    raise ValueError("membrane_map: the facets of tag %d are not membrane facets" % bad[0])
+                sel = mem[np.isin(self.facet_tags[mem], tags)]
+            if not len(sel):
+                raise ValueError("membrane_map: the selection holds no membrane facet")
+            self.map_facets = np.asarray(sel, dtype=np.int64)
 
     @property
     def n_points(self):
@@ -222,8 +321,9 @@ class Recorder:
         ions = self.ion_names
         return (["phi"] + ions, ["phi_M"] + ["E_" + n for n in ions] + ["I_ch_" + n for n in ions], ions + ["phi_mean"])
 
-    def attach(self, dev, membrane_tags=None):
-        """Create the device recorder on `dev` (a knpemidg._abi.Device without ghost cells)."""
+    def attach(self, dev, membrane_tags=None, models=None):
+        """Create the device recorder on `dev` (a knpemidg._abi.Device without ghost cells).  models: the membrane models, for the
+        state channels; they may follow later through `attach_states`."""
         if self.set_facets is None:
             self.resolve_sets(membrane_tags if membrane_tags is not None else [])
         ptr = np.concatenate([[0], np.cumsum([len(f) for f in self.set_facets])]).astype(np.int64)
@@ -231,15 +331,53 @@ class Recorder:
         sw = np.concatenate(self.set_weights) if self.set_facets else np.zeros(0)
         self.n_channels = dev.rec_create(self.capacity, self.point_cells, self.point_w, ptr, sf, sw, self.n_regions, self.region, self.vol)
         n_ions = len(self.ion_names)
-        assert self.n_channels == self.n_points * (n_ions + 1) + self.n_sets * (1 + 2 * n_ions) + self.n_regions * (n_ions + 1)
+        self.n_base = self.n_points * (n_ions + 1) + self.n_sets * (1 + 2 * n_ions) + self.n_regions * (n_ions + 1)
+        assert self.n_channels == self.n_base
         self.dev = dev
         self._waiting = 0
+        self._states_on_device = False
+        if self._map_spec is not None:
+            dev.rec_add_map(self.map_facets, self._map_spec["threshold"], self._map_spec["repolarisation"])
+            self._armed = False
+        if self.state_names and models is not None:
+            self.attach_states(models)
+
+    def attach_states(self, models):
+        """Build and upload the entry lists of the state channels from the membrane models (`state_entries`); right after `attach`,
+        before the first sample."""
+        if not self.state_names or self._states_on_device:
+            return
+        if self.dev is None:
+            raise KnpError("the recorder is not attached to a device context yet")
+        for m in models:
+            if getattr(m, "handle", None) is None:
+                raise KnpError("membrane_states: the state tables of membrane tag %s are not on the device (KNP_HOST_ODE=1, or a model "
+                               "without a device implementation)" % getattr(m, "tag", "?"))
+        areas = [facet_areas(self.mesh, f) for f in self.set_facets]
+        self.state_entry_lists = state_entries(self.set_facets, areas, models, self.state_names)
+        self.n_channels = self.dev.rec_add_states(*self.state_entry_lists)
+        assert self.n_channels == self.n_base + self.n_sets * len(self.state_names)
+        self._states_on_device = True
+
+    def arm(self, t0):
+        """Arm the membrane map at time t0: peak = previous value = phi_M now, no crossing seen yet.  The solver's time loops call
+        it; call it yourself when stepping by hand.  Without a map: nothing."""
+        if self._map_spec is None:
+            return
+        if self.dev is None:
+            raise KnpError("the recorder is not attached to a device context yet")
+        self.dev.rec_map_arm(float(t0))
+        self._armed = True
 
     # -- sampling -----------------------------------------------------------------
     def sample(self, t):
         """One row at time t (asynchronous).  A full device buffer is read back first: the only synchronisation."""
         if self.dev is None:
             raise KnpError("the recorder is not attached to a device context yet")
+        if self.state_names and not self._states_on_device:
+            raise KnpError("membrane_states need the membrane models (setup_membrane_model / Recorder.attach_states) before the first sample")
+        if self._map_spec is not None and not self._armed:
+            raise KnpError("the membrane map is not armed (Recorder.arm(t0))")
         if self._waiting >= self.capacity:
             self.flush()
         self.dev.rec_sample(float(t))
@@ -282,8 +420,56 @@ class Recorder:
 
     @property
     def membrane(self):
+        """{name: [n_steps, n_sets]}: phi_M, E_<ion>, I_ch_<ion> and, with membrane_states, one entry per state name."""
         n_ions = len(self.ion_names)
-        return self._block(self.n_points * (n_ions + 1), self.n_sets, self.channel_names()[1])
+        out = self._block(self.n_points * (n_ions + 1), self.n_sets, self.channel_names()[1])
+        if self.state_names and self._states_on_device:
+            out.update(self._block(self.n_base, self.n_sets, self.state_names))
+        return out
+
+    @property
+    def membrane_map(self):
+        """The per-facet map as it stands: facets (caller's ids), activation_time, repolarisation_time (NaN = not yet), peak,
+        peak_time, n_activations.  Synchronises and reads the device arrays in one transfer."""
+        if self._map_spec is None:
+            raise KnpError("no membrane map was asked for (record(membrane_map=...))")
+        if self.dev is None or not self._armed:
+            raise KnpError("the membrane map is not armed yet")
+        out = {"facets": self.map_facets.copy()}
+        out.update(zip(MAP_FIELDS, self.dev.rec_map_read()))
+        return out
+
+    def set_centroid(self, s):
+        return self.set_weights[s] @ self.mesh.facet_midpoints()[self.set_facets[s]]
+
+    def conduction_velocity(self, set_a, set_b, distance=None, method="map", threshold=None):
+        """distance / (t_b - t_a) between two membrane sets (reference: get_velocity, make_figures_rat_neuron.py:613-692).
+        method "map": t = area-weighted mean of the map's per-facet activation times over the set (every facet of both sets must be
+        in the map).  method "set_mean": t = first upward crossing of `threshold` (default: the map's, else 0) by the recorded
+        set-mean phi_M, linearly interpolated between steps -- the reference's definition at sub-step resolution.  distance defaults
+        to the distance between the area-weighted centroids.  NaN when either set has not (entirely) activated."""
+        if distance is None:
+            distance = float(np.linalg.norm(self.set_centroid(set_b) - self.set_centroid(set_a)))
+        if method == "map":
+            m = self.membrane_map
+            pos = {int(f): i for i, f in enumerate(m["facets"])}
+            times = []
+            for s in (set_a, set_b):
+                missing = [int(f) for f in self.set_facets[s] if int(f) not in pos]
+                if missing:
+                    raise ValueError("membrane set %d: facet %d is not in the membrane map" % (s, missing[0]))
+                idx = np.asarray([pos[int(f)] for f in self.set_facets[s]], dtype=np.int64)
+                times.append(float(self.set_weights[s] @ m["activation_time"][idx]))
+        elif method == "set_mean":
+            if threshold is None:
+                threshold = self._map_spec["threshold"] if self._map_spec is not None else 0.0
+            v = self.membrane["phi_M"]
+            times = [first_upward_crossing(self.t, v[:, s], float(threshold)) for s in (set_a, set_b)]
+        else:
+            raise ValueError("method must be 'map' or 'set_mean'")
+        if not np.isfinite(times).all():
+            return float("nan")
+        return distance / (times[1] - times[0])
 
     @property
     def regions(self):
@@ -292,7 +478,8 @@ class Recorder:
 
     def save(self, path):
         """/timeseries/t, /timeseries/points/<name>, /timeseries/membrane/<name>, /timeseries/regions/<name> ([n_steps, n_items]) plus
-        the probe coordinates and cells, the facets and weights of every membrane set and the region tags."""
+        the probe coordinates and cells, the facets and weights of every membrane set and the region tags; with a map,
+        /membrane_map/{facets, activation_time, repolarisation_time, peak, peak_time, n_activations, threshold, repolarisation}."""
         import os
         from knpemidg.h5lite import H5Writer
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
@@ -311,4 +498,12 @@ class Recorder:
                 w.write("/membrane_sets/set_%d/weights" % i, self.set_weights[i])
             if self.n_regions:
                 w.write("/regions/tags", np.asarray(self.region_tags, dtype=np.int64))
+            if self._map_spec is not None and self._armed:
+                m = self.membrane_map
+                w.write("/membrane_map/facets", m["facets"].astype(np.int64))
+                for name in MAP_FIELDS[:4]:
+                    w.write("/membrane_map/" + name, m[name])
+                w.write("/membrane_map/n_activations", m["n_activations"].astype(np.int64))
+                w.write("/membrane_map/threshold", np.asarray([self._map_spec["threshold"]]))
+                w.write("/membrane_map/repolarisation", np.asarray([self._map_spec["repolarisation"]]))
         return path

@@ -213,6 +213,8 @@ class Solver:
                 ode_model.get_parameter("I_ch_" + ion['name'], I_ch_k_)
                 I_ch_k[ion['name']] = I_ch_k_
             self.mem_models.append({'ode': ode_model, 'I_ch_k': I_ch_k})
+        if self.recorder is not None:
+            self.recorder.attach_states([m['ode'] for m in self.mem_models])     # state channels of a record() call made earlier
         return
 
     # ------------------------------------------------------------------ device context
@@ -252,7 +254,8 @@ class Solver:
             self.recorder.attach(dev, self.membrane_tags)
 
     # ------------------------------------------------------------------ time series (no reference counterpart: knpemidg/recorder.py)
-    def record(self, points=None, membrane_sets=None, regions=True, capacity=256, point_tags=None):
+    def record(self, points=None, membrane_sets=None, regions=True, capacity=256, point_tags=None, membrane_states=None,
+               membrane_map=None):
         """Attach a recorder of point probes, membrane-set means and region integrals, sampled on the device after step III of
         every time step (csrc/record.hip) -- the traces the reference's figure scripts compute from per-step field output
         (examples/idealized-geometries/make_figures_3D.py:28-168).  Callable once setup_domain has run; the device tables are
@@ -260,8 +263,20 @@ class Solver:
           points         [n, dim] coordinates; point_tags[i] (optional) = subdomain of the cell to take for a point on a membrane
           membrane_sets  list of facet-id arrays or (lo, hi) boxes (the membrane facets whose midpoint lies inside)
           regions        True = one region per distinct subdomain tag, ascending; False = none
-          capacity       rows of the device buffer = time steps between two device-to-host copies"""
+          capacity       rows of the device buffer = time steps between two device-to-host copies
+          membrane_states  names of ODE states as the membrane models declare them, e.g. ("n", "m", "h"): per membrane set the
+                         area-weighted mean over the facets whose model has that state, read from the state tables on the device
+                         (the reference's get_time_series_gating, examples/rat-neuron/make_figures_rat_neuron.py:238-315).  The row
+                         of step k holds the states after ODE step k.  Recorder.membrane['<state>'] is [n_steps][n_sets].
+          membrane_map   dict(threshold=0.0, repolarisation=None, tags=None), in the units of phi_M: per membrane facet (of the
+                         given surface tags) the interpolated activation and repolarisation times, the peak and its time and the
+                         number of activations (Recorder.membrane_map; plot_surface / get_velocity of the same script).  Armed by
+                         the time loops of solve_system_active / solve_system_passive; call Recorder.arm(t0) when stepping by hand.
+        Without the last two arguments the recorder issues the same device calls and rows as before."""
         from knpemidg.recorder import Recorder
+        if membrane_states and not self.use_device_ode:
+            raise _abi.KnpError("Solver.record: membrane_states read the ODE state tables on the device; with KNP_HOST_ODE=1 they "
+                                "live on the host")
         if getattr(self, "local_mesh", None) is not None or getattr(self, "nc_owned", None) is not None:
             raise _abi.KnpError("Solver.record: partitioned solvers (distribute_solver) are not supported; record on a one-GPU run")
         if getattr(self, "mesh", None) is None:
@@ -269,9 +284,9 @@ class Solver:
         mtags = self.membrane_tags if self.dev is not None else None
         rec = Recorder(self.mesh, self.subdomains.array(), self.surfaces.array(), self.degree_knp, [ion['name'] for ion in self.ion_list],
                        points=points, membrane_sets=membrane_sets, regions=regions, capacity=capacity, point_tags=point_tags,
-                       membrane_tags=mtags)
+                       membrane_tags=mtags, membrane_states=membrane_states, membrane_map=membrane_map)
         if self.dev is not None:
-            rec.attach(self.dev)
+            rec.attach(self.dev, models=[m['ode'] for m in self.mem_models] if self.mem_models else None)
         self.recorder = rec
         return rec
 
@@ -926,6 +941,8 @@ class Solver:
         self.setup_solver_emi()
         self.setup_solver_knp()
         self._check_output_args(filename)
+        if self.recorder is not None:
+            self.recorder.arm(float(t))
         for k in range(int(round(Tstop / float(self.dt)))):
             self.solve_for_time_step(k, t)
             if (k % self.sf) == 0 and self.save_fields:
@@ -952,6 +969,10 @@ class Solver:
         self._check_output_args(filename)
         for k in range(int(round(Tstop / float(self.dt)))):
             self.step_membrane_models(k)
+            if k == 0 and self.recorder is not None:
+                # the time loop starts: with phi_M_init_type 'constant' PHI_M holds the membrane potential only from here on (it
+                # comes from the ODE states in the first membrane step), so this is where the map takes its starting values
+                self.recorder.arm(float(t))
             self.solve_for_time_step(k, t)
             if (k % self.sf) == 0 and self.save_fields:
                 self.save_h5()
