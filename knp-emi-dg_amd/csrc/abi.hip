@@ -63,13 +63,13 @@ __global__ void k_extrapolate_guess(int64_t n, int nh, int order, int keep_h2, d
 // KNP_EXTRAPOLATE_ORDER=2 uses three solutions (quadratic).  A state upload invalidates the history.
 static int extrapolate_guess(knp_ctx* c, double* x, double** hist, int* nh, int64_t n, bool emi) {
     // KNP_EXTRAPOLATE = 1: both solves, 2: EMI only, 3: KNP only
-    static const int mode = getenv("KNP_EXTRAPOLATE") ? atoi(getenv("KNP_EXTRAPOLATE")) : 1;
+    static const int mode = env_int("KNP_EXTRAPOLATE", 1);
     // order 1: x0 = 2 x_{k-1} - x_{k-2}; order 2: x0 = 3 x_{k-1} - 3 x_{k-2} + x_{k-3}.  KNP_EXTRAPOLATE_ORDER sets both solves,
     // KNP_EXTRAPOLATE_ORDER_KNP / _EMI one of them (r=2: order 2 costs the EMI solve 4.7 -> 7.0 iterations per step -- the potential
     // jumps with the membrane currents -- and saves the KNP solve 0.45 of 5.05: profiles/r04_min_it.txt)
-    static const int order_all = getenv("KNP_EXTRAPOLATE_ORDER") ? atoi(getenv("KNP_EXTRAPOLATE_ORDER")) : 0;
-    static const int order_emi = getenv("KNP_EXTRAPOLATE_ORDER_EMI") ? atoi(getenv("KNP_EXTRAPOLATE_ORDER_EMI")) : (order_all ? order_all : 1);
-    static const int order_knp = getenv("KNP_EXTRAPOLATE_ORDER_KNP") ? atoi(getenv("KNP_EXTRAPOLATE_ORDER_KNP")) : (order_all ? order_all : 1);
+    static const int order_all = env_int("KNP_EXTRAPOLATE_ORDER", 0);
+    static const int order_emi = env_int("KNP_EXTRAPOLATE_ORDER_EMI", (order_all ? order_all : 1));
+    static const int order_knp = env_int("KNP_EXTRAPOLATE_ORDER_KNP", (order_all ? order_all : 1));
     const int order = emi ? order_emi : order_knp;
     const bool on = mode == 1 || (mode == 2 && emi) || (mode == 3 && !emi);
     if (!on || c->p.splitting == 2) return 0;
@@ -161,7 +161,7 @@ int knp_ctx_create(knp_ctx** out, int device, int dim, int degree, int n_ions, i
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device visible"; return -5; }
     if (device < 0 || device >= ndev) { g_err = "device index out of range"; return -5; }
     // KNP_DEBUG_SETUP=1: wall-clock stamps of the stages below on stderr (next to the host-side stamps of knpemidg/_abi.py)
-    const bool stamps = getenv("KNP_DEBUG_SETUP") && atoi(getenv("KNP_DEBUG_SETUP")) == 1;
+    const bool stamps = env_int("KNP_DEBUG_SETUP", 0) == 1;
     auto t_last = std::chrono::steady_clock::now();
     auto stamp = [&](const char* what) {
         if (!stamps) return;
@@ -362,7 +362,7 @@ int knp_ctx_create(knp_ctx** out, int device, int dim, int degree, int n_ions, i
     rc |= dev_zeros(c, &c->rho, nc);
     c->partial_blocks = grid_for(nc_owned) + 8;
     rc |= dev_zeros(c, &c->partial, (size_t)c->partial_blocks * KNP_MAX_SYS * KNP_MAX_RED);
-    rc |= dev_zeros(c, &c->scal, KNP_GM_OFFSET + KNP_MAX_SYS * KNP_GM_STRIDE);        // Krylov scalars, reduction results, GMRES state
+    rc |= dev_zeros(c, &c->scal, KNP_SCAL_DOUBLES);        // Krylov scalars, reduction results, GMRES state
     if (!rc && hipMalloc((void**)&c->status, sizeof(int) * KNP_STATUS_WORDS) != hipSuccess) rc = -2;
     if (!rc) hipMemset(c->status, 0, sizeof(int) * KNP_STATUS_WORDS);
     if (!rc && hipHostMalloc(&c->pinned, 4096) != hipSuccess) rc = -2;
@@ -758,7 +758,7 @@ int knp_knp_early_stop(knp_ctx* c, double factor) {
 int knp_knp_load_measure(knp_ctx* c, double* out) {
     if (!c || !out) return -1;
     Fields* f = F(c);
-    const bool d8 = !(getenv("KNP_KNP_NORM2") && atoi(getenv("KNP_KNP_NORM2")) == 1);
+    const bool d8 = env_int("KNP_KNP_NORM2", 0) != 1;
     return load_measure(c, f->f[KNP_F_B_KNP], f->ivol, d8, out);
 }
 
@@ -767,7 +767,7 @@ int knp_emi_solve(knp_ctx* c, double rtol, double atol, int maxit, int check_eve
     Fields* f = F(c);
     // the cell-block inverses only precondition: rebuilt every KNP_BJ_LAG-th solve (default 8; the coefficients move by < 1 %
     // per step), like the lagged AMG hierarchy; 1 = every solve
-    static const int bj_lag = getenv("KNP_BJ_LAG") ? atoi(getenv("KNP_BJ_LAG")) : 8;
+    static const int bj_lag = env_int("KNP_BJ_LAG", 8);
     int rc = 0;
     if (f->bj_age_emi % (bj_lag > 0 ? bj_lag : 1) == 0) rc = launch_emi_blockjacobi(c, f->f[KNP_F_KAPPA], f->binv_emi);
     ++f->bj_age_emi;
@@ -776,12 +776,12 @@ int knp_emi_solve(knp_ctx* c, double rtol, double atol, int maxit, int check_eve
     KrylovVecs kv{};
     kv.x = f->f[KNP_F_PHI]; kv.b = f->f[KNP_F_B_EMI]; kv.coef = f->f[KNP_F_KAPPA]; kv.binv = f->binv_emi;
     kv.ivol = f->ivol; kv.r_abs = f->emi_r_abs;
-    kv.d8 = !(getenv("KNP_KNP_NORM2") && atoi(getenv("KNP_KNP_NORM2")) == 1);   // the residual target is a density norm of order 8, like the KNP test
+    kv.d8 = env_int("KNP_KNP_NORM2", 0) != 1;   // the residual target is a density norm of order 8, like the KNP test
     kv.r = f->r; kv.z = f->z; kv.p = f->p; kv.w = f->w; kv.rhat = f->rhat; kv.v = f->v; kv.y = f->y;
     // the same two-step Chebyshev block-Jacobi smoother for EMI (KNP_EMI_CHEB=0 disables): at the effective tolerance the
     // parity bounds need (rtol 2e-8, knpemidg/solver.py) it cuts the PCG iterations from 5.2 to 4.2 per step and the
     // error of phi by 2x at equal tolerance (r=1, 40 steps through an action potential) for one more apply per iteration
-    static const int cheb_env_emi = getenv("KNP_EMI_CHEB") ? atoi(getenv("KNP_EMI_CHEB")) : -1;
+    static const int cheb_env_emi = env_int("KNP_EMI_CHEB", -1);
     // Round 3: with the finest conforming level smoothed, the step no longer pays on large uniform meshes (r=2: 4.25 -> 4.7 iterations
     // for 27 % less work per iteration, 7.35 -> 7.14 ms/step; r=3 48.9 -> 46.0) while small or badly shaped meshes still need it (EMIx:
     // 9.2 -> 13.5 iterations): the host decides per mesh (knp_set_emi_dg_smoother; knpemidg/solver.py), the environment overrides
@@ -824,7 +824,7 @@ __global__ void k_bj_gather(int nent, const int32_t* __restrict__ rep, int nsys,
 
 static int build_bj_table(knp_ctx* c, Fields* f) {
     f->bj_tab_state = -1;
-    static const bool enabled = !(getenv("KNP_BJ_TABLE") && atoi(getenv("KNP_BJ_TABLE")) == 0);
+    static const bool enabled = env_flag("KNP_BJ_TABLE", true);
     const int64_t nc = c->m.nc, n_own = c->m.nc_owned;
     if (!enabled || c->h_cls.size() != (size_t)nc || c->h_mat.size() != (size_t)nc || c->h_fflag.size() != (size_t)nc || c->p.splitting == 2 ||
         c->p.n_sys > 4 || n_own == 0 || (c->degree != 1 && p2_assembled()))
@@ -874,7 +874,7 @@ static int build_bj_table(knp_ctx* c, Fields* f) {
 int knp_knp_solve(knp_ctx* c, double rtol, double atol, int maxit, int min_it, int check_every, int* niter, double* res) {
     if (!c || !niter || !res) return -1;
     Fields* f = F(c);
-    static const int bj_lag = getenv("KNP_BJ_LAG") ? atoi(getenv("KNP_BJ_LAG")) : 8;
+    static const int bj_lag = env_int("KNP_BJ_LAG", 8);
     int rc = 0;
     if (f->bj_tab_state == 0 && (rc = build_bj_table(c, f))) return rc;
     // the table ignores the drift: good while the potential varies little over a cell (psi |z| dphi << 1: 0.01-0.05 through an action
@@ -910,7 +910,7 @@ int knp_knp_solve(knp_ctx* c, double rtol, double atol, int maxit, int min_it, i
     // measured at 0.03-0.055 of that ratio on both mesh families, so  ratio <= KNP_D8_FACTOR * rtol  asks for an estimated max-norm
     // error of about rtol (profiles/r03_knp_norms_*.txt).  KNP_KNP_NORM2=1: plain rtol on the cell-volume-weighted 2-norm instead.
     // read per call, like knp_knp_load_measure and the EMI target: the load measure and this test must agree after an environment change
-    const bool d8 = !(getenv("KNP_KNP_NORM2") && atoi(getenv("KNP_KNP_NORM2")) == 1);
+    const bool d8 = env_int("KNP_KNP_NORM2", 0) != 1;
     static const double d8_factor = getenv("KNP_D8_FACTOR") ? atof(getenv("KNP_D8_FACTOR")) : 20.0;
     kv.d8 = d8;
     if (d8) rtol *= d8_factor;
@@ -919,7 +919,7 @@ int knp_knp_solve(knp_ctx* c, double rtol, double atol, int maxit, int min_it, i
     // application (one more operator apply per preconditioner application; BiCGStab iterations 14-20 -> 9-13 through an
     // action potential at r=2, -10 % per step).  lambda_max(Binv A) comes from a power iteration at the first solve.
     // Degree 1 only by default: the assembled P2 apply is 3x as expensive and the trade does not pay (21 -> 25 ms/step).
-    static const int cheb_env = getenv("KNP_KNP_CHEB") ? atoi(getenv("KNP_KNP_CHEB")) : -1;
+    static const int cheb_env = env_int("KNP_KNP_CHEB", -1);
     // (round 3, matrix-free P2 applies: with the step DG-P2 takes 8.1 -> 6.1 KNP iterations and steps 5 % faster at r=2, but 40 steps of
     // the P2 configuration then end with 1.08e-6 in the concentrations against the 1e-6 bound: not enabled)
     // (round 4: the step is on for DG-P2 too.  Round 3 had to keep it off because the EMI stop let more error through with better

@@ -389,13 +389,7 @@ __global__ __launch_bounds__(256) void k_restrict_tiles(int64_t ndof_owned, int 
         for (int i = threadIdx.x; i < n; i += 256) s_r[i] = t ? fma(-ct, t[d0 + i], src[i]) : src[i];
     }
     __syncthreads();
-    const int p1 = tile_off[blockIdx.x + 1];
-    for (int p = tile_off[blockIdx.x] + threadIdx.x; p < p1; p += 256) {
-        double acc = 0.0;
-        const int e = slot_ptr[p + 1];
-        for (int k = slot_ptr[p]; k < e; ++k) acc += s_r[slot_idx[k]];
-        part[p] = acc;
-    }
+    tile_slot_sums(s_r, tile_off, slot_ptr, slot_idx, part);
 }
 
 // stage 2: rc[v] = sum of the slots of conforming dof v (fixed order); with dinv also the zero-guess first Chebyshev update of level 0
@@ -494,7 +488,7 @@ static int amg_vcycle_eager(knp_ctx* c, AmgHierarchy& H, int l0 = 0) {
 // The V-cycle is ~40 tiny launch-bound kernels on fixed buffers: capture it once into a hipGraph and replay it
 // (kernel boundaries ~1.5 us instead of ~5 us of eager launch latency each).
 static int amg_vcycle_levels(knp_ctx* c, AmgHierarchy& H, int l0, hipStream_t on_stream) {
-    static const bool use_graph = !(getenv("KNP_NO_GRAPH") && atoi(getenv("KNP_NO_GRAPH")));
+    static const bool use_graph = !env_flag("KNP_NO_GRAPH", false);
     if (use_graph && !H.graph_tried) {
         H.graph_tried = true;
         hipGraph_t graph = nullptr;
@@ -739,7 +733,7 @@ int knp_amg_begin(knp_ctx* c, int which, int64_t ncg, const int32_t* dg2cg, cons
     rc |= up(c, &H->cg_idx, cg_idx, (size_t)cg_ptr[ncg]);
     // tables of the tile-wise restriction over the owned cells (device order = Morton: a tile is a compact patch)
     const int nd = c->nd;
-    static const int tile_env = getenv("KNP_RESTRICT_TILE") ? atoi(getenv("KNP_RESTRICT_TILE")) : 0;
+    static const int tile_env = env_int("KNP_RESTRICT_TILE", 0);
     const int tile_cells = tile_env > 0 ? tile_env : (nd <= 4 ? 512 : 256);      // 16 KB / 20 KB of LDS per workgroup (r=2: 512 -> 10.55, 1024 -> 10.71, 256 -> 10.69 ms/step)
     const int64_t n_own = c->m.nc_owned;
     const int64_t ntiles = (n_own + tile_cells - 1) / tile_cells;
@@ -837,7 +831,7 @@ static int amg_finish_impl(knp_ctx* c, int which, int64_t n, const double* pinv6
         for (size_t i = 0; i < p32.size(); ++i) p32[i] = (float)pinv64[i];
         rc = up(c, &H->pinv, p32.data(), p32.size());
     }
-    const bool fuse_env = !(getenv("KNP_FUSE_FIRST0") && atoi(getenv("KNP_FUSE_FIRST0")) == 0);   // read per upload: tests switch it
+    const bool fuse_env = env_flag("KNP_FUSE_FIRST0", true);   // read per upload: tests switch it
     H->fuse_first0 = fuse_env && !c->dist && H->ntiles > 0 && H->levels.size() > 1 && H->levels[0].cheb_degree > 0;
     H->ready = (rc == 0);
     return rc;

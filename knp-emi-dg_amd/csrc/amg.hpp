@@ -53,6 +53,23 @@ struct AmgHierarchy {
     double *entry_x = nullptr, *entry_r = nullptr, *entry_d0 = nullptr;
 };
 
+#ifdef __HIPCC__
+// Stage 1 of the tile-wise restriction, behind the barrier that completes the tile's values in LDS (s_r): thread by thread, every slot of
+// tile blockIdx.x (256 threads) sums its entries in the order of slot_idx.  Shared by amg.hip: k_restrict_tiles and the fused kernels of
+// krylov.hip (k_cg_update_restrict, k_bj_cheb2_restrict).  The summation order is a CONTRACT between them: the fused paths are tested
+// bit for bit against the unfused ones, so all three go through this one loop.
+__device__ __forceinline__ void tile_slot_sums(const double* s_r, const int32_t* __restrict__ tile_off, const int32_t* __restrict__ slot_ptr,
+                                               const uint16_t* __restrict__ slot_idx, double* __restrict__ part) {
+    const int p1 = tile_off[blockIdx.x + 1];
+    for (int p = tile_off[blockIdx.x] + threadIdx.x; p < p1; p += 256) {
+        double acc = 0.0;
+        const int e = slot_ptr[p + 1];
+        for (int k = slot_ptr[p]; k < e; ++k) acc += s_r[slot_idx[k]];
+        part[p] = acc;
+    }
+}
+#endif
+
 struct knp_ctx;
 int amg_vcycle(knp_ctx* c, AmgHierarchy& H, hipStream_t on_stream = nullptr);
 // stage 1 of the tile-wise restriction may be done by a fused kernel of krylov.hip: buffer first, the remaining stages afterwards

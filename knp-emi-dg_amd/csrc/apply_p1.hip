@@ -1015,10 +1015,6 @@ int launch_knp_apply(knp_ctx* c, const double* x, const double* gphi, double* y)
 
 // halo-staged kernels: usable when the class and halo tables exist and the block's LDS footprint stays below 64 KB;
 // KNP_APPLY_HALO=0 selects the previous staged kernels (A/B runs)
-static int env_int(const char* name, int dflt) {            // read per launch (tests switch variants inside one process)
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
 static bool halo_enabled() { return env_int("KNP_APPLY_HALO", 1) != 0; }
 static unsigned halo_entries(const knp_ctx* c) { return (unsigned)(KNP_HALO_BLK + c->m.hb_stride); }
 // block counters of the persistent kernels: per operator two sets of 8 that swap roles at every launch (the kernel zeroes the

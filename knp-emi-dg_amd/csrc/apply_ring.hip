@@ -494,42 +494,6 @@ __global__ __launch_bounds__(2 * RB + 64 * RLOADERS) void k_emi_apply_ring(MeshD
     }
 }
 
-int env_int_ring(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
-int device_cus(int device) {
-    static int ncu = 0;
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        ncu = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return ncu;
-}
-
-// more than 64 KB of dynamic LDS per workgroup has to be granted per kernel, once
-template <typename KernelT> bool ring_grant_lds(KernelT kernel, size_t lds) {
-    static std::map<const void*, size_t> granted;
-    auto it = granted.find((const void*)kernel);
-    if (it != granted.end() && it->second >= lds) return true;
-    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-    granted[(const void*)kernel] = lds;
-    return true;
-}
-
-// one workgroup per CU (the ring takes most of a CU's LDS), a multiple of 8, not more than 8 per 8 blocks
-dim3 ring_grid(const MeshDev& m, int device, int reserve_cus) {
-    const int64_t nblk = (m.c_end - 1) / RB - m.c_begin / RB + 1;
-    const int cus = std::max(device_cus(device) - std::max(reserve_cus, 0), 8);
-    int64_t per_xcd = std::max<int64_t>(1, std::min<int64_t>(cus / 8, (nblk + 7) / 8));
-    // tests only: KNP_RING_WG = workgroups of the launch (rounded down to a multiple of 8), so that small oracle-sized meshes put many
-    // blocks on a workgroup (slot reuse, list-buffer wrap, counted vmcnt with two blocks in flight: the steady state of the r=2 runs)
-    const int wg = env_int_ring("KNP_RING_WG", 0);
-    if (wg >= 8) per_xcd = std::min<int64_t>(per_xcd, wg / 8);
-    return dim3((unsigned)(8 * per_xcd));
-}
-
 }  // namespace
 
 static size_t ring_lds_bytes(const knp_ctx* c, int which) {
@@ -543,14 +507,14 @@ static size_t ring_lds_bytes(const knp_ctx* c, int which) {
 // at most two solved species; KNP_APPLY_RING=0 selects the thread-per-cell kernels of apply_p1.hip (A/B runs)
 bool ring_usable(const knp_ctx* c, int which) {
     if (c->degree != 1 || c->m.dim != 3 || !c->m.cls || c->m.ncls > 32 || !c->m.hb_src || c->m.hb_stride <= 0 || c->m.hb_stride > RH) return false;
-    if (env_int_ring("KNP_APPLY_RING", 1) == 0 || ring_lds_bytes(c, which) > 160 * 1024) return false;
-    if (which == 0) return env_int_ring("KNP_EMI_RING", 1) != 0;
-    return c->nmat > 0 && c->p.n_sys <= 2 && env_int_ring("KNP_APPLY_MAT", 1) != 0 && env_int_ring("KNP_APPLY_HALO", 1) != 0;
+    if (env_int("KNP_APPLY_RING", 1) == 0 || ring_lds_bytes(c, which) > 160 * 1024) return false;
+    if (which == 0) return env_int("KNP_EMI_RING", 1) != 0;
+    return c->nmat > 0 && c->p.n_sys <= 2 && env_int("KNP_APPLY_MAT", 1) != 0 && env_int("KNP_APPLY_HALO", 1) != 0;
 }
 
 int ring_emi_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* kappa, double* y, int reserve_cus) {
     const size_t lds = ring_lds_bytes(c, 0);
-    if (!ring_grant_lds(k_emi_apply_ring, lds)) { c->err = "hipFuncSetAttribute(k_emi_apply_ring) failed"; return -2; }
+    if (!grant_lds(k_emi_apply_ring, lds)) { c->err = "hipFuncSetAttribute(k_emi_apply_ring) failed"; return -2; }
     hipLaunchKernelGGL(k_emi_apply_ring, ring_grid(m, c->device, reserve_cus), dim3(2 * RB + 64 * RLOADERS), lds, c->stream, m, x, kappa, y, c->p.C_phi, c->p.tau_emi);
     HIPCHK(c, hipGetLastError());
     return 0;
@@ -560,12 +524,12 @@ int ring_knp_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* 
     const int ns = c->p.n_sys;
     const size_t lds = ring_lds_bytes(c, 1);
     const dim3 g = ring_grid(m, c->device, reserve_cus);
-    const bool split = ns == 2 && env_int_ring("KNP_RING_SPLIT", 0) != 0;       // two consumer groups, one species each (measured equal to one group: 47.6 vs 46.3 us)
+    const bool split = ns == 2 && env_int("KNP_RING_SPLIT", 0) != 0;       // two consumer groups, one species each (measured equal to one group: 47.6 vs 46.3 us)
 #define RING_KNP_LAUNCH(NS_, NG_)                                                                                                     \
     do {                                                                                                                              \
-        if (!ring_grant_lds(k_knp_apply_ring<NS_, NG_>, lds)) { c->err = "hipFuncSetAttribute(k_knp_apply_ring) failed"; return -2; }  \
+        if (!grant_lds(k_knp_apply_ring<NS_, NG_>, lds)) { c->err = "hipFuncSetAttribute(k_knp_apply_ring) failed"; return -2; }  \
         hipLaunchKernelGGL((k_knp_apply_ring<NS_, NG_>), g, dim3(RB * NG_ + 64 * RLOADERS), lds, c->stream, m, x, gphi, y, ka, (const uint8_t*)c->mat,  \
-                           (const uint8_t*)c->nmat4, (const double*)c->dtab, env_int_ring("KNP_RING_DEBUG", 0));                     \
+                           (const uint8_t*)c->nmat4, (const double*)c->dtab, env_int("KNP_RING_DEBUG", 0));                     \
     } while (0)
     if (ns == 1) RING_KNP_LAUNCH(1, 1);
     else if (split) RING_KNP_LAUNCH(2, 2);

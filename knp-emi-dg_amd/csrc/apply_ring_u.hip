@@ -493,38 +493,6 @@ __global__ __launch_bounds__(RB + 64 * ULOADERS) void k_knp_apply_ring_u(MeshDev
     }
 }
 
-int env_int_u(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
-int device_cus_u(int device) {
-    static int ncu = 0;
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        ncu = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return ncu;
-}
-
-template <typename KernelT> bool grant_lds_u(KernelT kernel, size_t lds) {
-    static std::map<const void*, size_t> granted;
-    auto it = granted.find((const void*)kernel);
-    if (it != granted.end() && it->second >= lds) return true;
-    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-    granted[(const void*)kernel] = lds;
-    return true;
-}
-
-dim3 grid_u(const MeshDev& m, int device, int reserve_cus) {
-    const int64_t nblk = (m.c_end - 1) / RB - m.c_begin / RB + 1;
-    const int cus = std::max(device_cus_u(device) - std::max(reserve_cus, 0), 8);
-    int64_t per_xcd = std::max<int64_t>(1, std::min<int64_t>(cus / 8, (nblk + 7) / 8));
-    const int wg = env_int_u("KNP_RING_WG", 0);                        // tests only (apply_ring.hip: ring_grid)
-    if (wg >= 8) per_xcd = std::min<int64_t>(per_xcd, wg / 8);
-    return dim3((unsigned)(8 * per_xcd));
-}
-
 struct RingUState {
     RingUTables T;
     bool tried = false, usable = false;
@@ -646,8 +614,8 @@ static size_t ring_u_lds(const knp_ctx* c, int which) {
 // usable); KNP_APPLY_RING_U=0 selects the thread-per-cell coordinate kernels (A/B runs).  Builds the tables at the first call.
 int64_t ring_u_cells(knp_ctx* c, int which) {
     if (c->degree != 1 || c->m.dim != 3 || c->m.cls || c->m.nc_owned < RB || c->m.nv >= (int64_t(1) << 31)) return 0;
-    if (env_int_u("KNP_APPLY_RING_U", 1) == 0 || env_int_u("KNP_APPLY_RING", 1) == 0) return 0;
-    if (which == 1 && !(c->nmat > 0 && c->p.n_sys <= 2 && env_int_u("KNP_APPLY_MAT", 1) != 0)) return 0;
+    if (env_int("KNP_APPLY_RING_U", 1) == 0 || env_int("KNP_APPLY_RING", 1) == 0) return 0;
+    if (which == 1 && !(c->nmat > 0 && c->p.n_sys <= 2 && env_int("KNP_APPLY_MAT", 1) != 0)) return 0;
     if (ring_u_lds(c, which) > 160 * 1024) return 0;
     RingUState& S = state_u(c);
     if (!S.tried) {
@@ -660,8 +628,8 @@ int64_t ring_u_cells(knp_ctx* c, int which) {
 int ring_u_emi_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* kappa, double* y, int reserve_cus) {
     const RingUTables& T = state_u(c).T;
     const size_t lds = ring_u_lds(c, 0);
-    if (!grant_lds_u(k_emi_apply_ring_u, lds)) { c->err = "hipFuncSetAttribute(k_emi_apply_ring_u) failed"; return -2; }
-    hipLaunchKernelGGL(k_emi_apply_ring_u, grid_u(m, c->device, reserve_cus), dim3(RB + 64 * ULOADERS), lds, c->stream, m, T, x, kappa, y, c->p.C_phi,
+    if (!grant_lds(k_emi_apply_ring_u, lds)) { c->err = "hipFuncSetAttribute(k_emi_apply_ring_u) failed"; return -2; }
+    hipLaunchKernelGGL(k_emi_apply_ring_u, ring_grid(m, c->device, reserve_cus), dim3(RB + 64 * ULOADERS), lds, c->stream, m, T, x, kappa, y, c->p.C_phi,
                        c->p.tau_emi);
     HIPCHK(c, hipGetLastError());
     return 0;
@@ -670,13 +638,13 @@ int ring_u_emi_apply(knp_ctx* c, const MeshDev& m, const double* x, const double
 int ring_u_knp_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* gphi, double* y, const KnpArgs& ka, int reserve_cus) {
     const RingUTables& T = state_u(c).T;
     const size_t lds = ring_u_lds(c, 1);
-    const dim3 g = grid_u(m, c->device, reserve_cus);
+    const dim3 g = ring_grid(m, c->device, reserve_cus);
     if (c->p.n_sys == 1) {
-        if (!grant_lds_u(k_knp_apply_ring_u<1>, lds)) { c->err = "hipFuncSetAttribute(k_knp_apply_ring_u) failed"; return -2; }
+        if (!grant_lds(k_knp_apply_ring_u<1>, lds)) { c->err = "hipFuncSetAttribute(k_knp_apply_ring_u) failed"; return -2; }
         hipLaunchKernelGGL((k_knp_apply_ring_u<1>), g, dim3(RB + 64 * ULOADERS), lds, c->stream, m, T, x, gphi, y, ka, (const uint8_t*)c->mat,
                            (const uint8_t*)c->nmat4, (const double*)c->dtab);
     } else {
-        if (!grant_lds_u(k_knp_apply_ring_u<2>, lds)) { c->err = "hipFuncSetAttribute(k_knp_apply_ring_u) failed"; return -2; }
+        if (!grant_lds(k_knp_apply_ring_u<2>, lds)) { c->err = "hipFuncSetAttribute(k_knp_apply_ring_u) failed"; return -2; }
         hipLaunchKernelGGL((k_knp_apply_ring_u<2>), g, dim3(RB + 64 * ULOADERS), lds, c->stream, m, T, x, gphi, y, ka, (const uint8_t*)c->mat,
                            (const uint8_t*)c->nmat4, (const double*)c->dtab);
     }

@@ -7,6 +7,7 @@
 // (reference: src/knpemidg/solver.py:16, 529, 789).
 #include "../../include/knpemi_hip.h"
 #include "knpemi_internal.hpp"
+#include "krylov.hpp"
 #include <rccl/rccl.h>
 #include <atomic>
 #include <chrono>
@@ -53,7 +54,7 @@ int allreduce_red(knp_ctx* c, double* red, int count) {
 }
 
 int allreduce_max(knp_ctx* c, double* host_value) {
-    double* d = c->scal + KNP_MAX_SYS * 12;            // reduction scratch (krylov.hpp: KS_N = 12)
+    double* d = krylov_red(c);                         // reduction scratch
     if (c->shm) {
         HIPCHK(c, hipMemcpyAsync(d, host_value, sizeof(double), hipMemcpyHostToDevice, c->stream));
         int rc = shm_allreduce(c, d, 1, true);
@@ -96,7 +97,7 @@ int allreduce_max_word(knp_ctx* c, int* dev_word) {
 int allreduce_sum_host(knp_ctx* c, double* host_values, int n) {
     if (n < 0 || n > KNP_MAX_SYS * KNP_MAX_RED) { c->err = "allreduce_sum_host: at most 56 values"; return -1; }
     if (!c->dist || n == 0) return 0;
-    double* d = c->scal + KNP_MAX_SYS * 12;            // reduction scratch: KNP_MAX_SYS * KNP_MAX_RED doubles (krylov.hip)
+    double* d = krylov_red(c);                         // reduction scratch: KNP_MAX_SYS * KNP_MAX_RED doubles
     HIPCHK(c, hipMemcpyAsync(d, host_values, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     int rc = allreduce_red(c, d, n);
     if (rc) return rc;
@@ -439,7 +440,7 @@ int knp_comm_init(knp_ctx* c, int rank, int nranks, const char* id128) {
     c->nranks = nranks;
     // KNP_FORCE_COMM=1: build the communicator and take every collective code path even with one rank (a 1-GPU box can
     // then exercise ncclCommInitRank / ncclAllReduce on the solver's stream; RCCL refuses two ranks on one device)
-    if (nranks == 1 && !(getenv("KNP_FORCE_COMM") && atoi(getenv("KNP_FORCE_COMM")) == 1)) return 0;
+    if (nranks == 1 && env_int("KNP_FORCE_COMM", 0) != 1) return 0;
     ncclUniqueId id;
     memcpy(&id, id128, sizeof(id));
     HIPCHK(c, hipSetDevice(c->device));
@@ -455,7 +456,7 @@ int knp_comm_init(knp_ctx* c, int rank, int nranks, const char* id128) {
 int knp_comm_init_halo(knp_ctx* c, const char* id128) {
     if (!c || !id128) return -1;
     if (!c->dist) return 0;
-    if (getenv("KNP_HALO_OVERLAP") && atoi(getenv("KNP_HALO_OVERLAP")) == 0) return 0;
+    if (!env_flag("KNP_HALO_OVERLAP", true)) return 0;
     ncclUniqueId id;
     memcpy(&id, id128, sizeof(id));
     HIPCHK(c, hipSetDevice(c->device));
@@ -510,7 +511,7 @@ int knp_comm_init_shm(knp_ctx* c, int rank, int nranks, const char* name, int64_
     c->shm = s;
     c->rank = rank; c->nranks = nranks;
     c->dist = true;
-    if (!(getenv("KNP_HALO_OVERLAP") && atoi(getenv("KNP_HALO_OVERLAP")) == 0)) {     // the overlapped apply, as with the halo communicator
+    if (env_flag("KNP_HALO_OVERLAP", true)) {     // the overlapped apply, as with the halo communicator
         HIPCHK(c, create_halo_stream(c));
         HIPCHK(c, hipEventCreateWithFlags(&c->halo_ready, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&c->halo_done, hipEventDisableTiming));

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 #include <map>
@@ -183,6 +184,14 @@ struct KnpArgs {
 template <int D> struct FacetConst;
 template <> struct FacetConst<3> { static constexpr double mass = 1.0 / 12.0, trip = 1.0 / 60.0; };
 template <> struct FacetConst<2> { static constexpr double mass = 1.0 / 6.0, trip = 1.0 / 24.0; };
+
+// integer / on-off environment knobs.  Both read the environment on every call (tests switch some knobs inside one process); a site
+// that wants its value fixed for the process keeps it in a static of its own
+inline int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
+inline bool env_flag(const char* name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; }
 
 // ---- launchers implemented in the .hip files --------------------------------------------
 int launch_emi_apply(knp_ctx* c, const double* x, const double* kappa, double* y);

@@ -6,68 +6,9 @@
 // fixed-order second stage (bitwise reproducible), all-reduced over RCCL when nranks > 1.
 //
 // Replaces PETSc KSP cg / gmres + hypre (reference: src/knpemidg/solver.py:425-444,509,684-701,771).
-#include "cell_geom.hpp"
-#include "krylov.hpp"
+#include "krylov_reduce.hpp"
 #include <cstdlib>
 #include <cstring>
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// block-level sum of NR values per thread; result valid in thread 0
-template <int NR> __device__ __forceinline__ void block_sum(double* v, double* out) {
-    __shared__ double lds[KNP_BLOCK / 64][NR];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const double s = wave_sum(v[r]);
-        if (lane == 0) lds[wv][r] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            double s = lds[0][r];
-#pragma unroll
-            for (int w = 1; w < KNP_BLOCK / 64; ++w) s += lds[w][r];
-            out[r] = s;
-        }
-    }
-}
-
-template <int NR> __device__ __forceinline__ void write_partials(double* partial, int nsys, double* v) {
-    double out[NR];
-    block_sum<NR>(v, out);
-    if (threadIdx.x == 0) {
-        double* p = partial + ((int64_t)blockIdx.x * nsys + blockIdx.y) * KNP_MAX_RED;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) p[r] = out[r];
-    }
-}
-
-// NV = dofs per cell: 3 / 4 (P1 triangles / tets), 6 / 10 (P2)
-template <int NV> __device__ __forceinline__ void ldv(const double* p, int64_t c, double* v) {
-    if constexpr (NV <= 4) {
-        load_nodal<NV - 1>(p, c, v);
-    } else {
-        static_assert(NV % 2 == 0, "P2 cell vectors are read as double2");
-        const double2* q = reinterpret_cast<const double2*>(p + (int64_t)NV * c);
-#pragma unroll
-        for (int k = 0; k < NV / 2; ++k) { const double2 t = q[k]; v[2 * k] = t.x; v[2 * k + 1] = t.y; }
-    }
-}
-template <int NV> __device__ __forceinline__ void stv(double* p, int64_t c, const double* v) {
-    if constexpr (NV <= 4) {
-        store_nodal<NV - 1>(p, c, v);
-    } else {
-        double2* q = reinterpret_cast<double2*>(p + (int64_t)NV * c);
-#pragma unroll
-        for (int k = 0; k < NV / 2; ++k) q[k] = make_double2(v[2 * k], v[2 * k + 1]);
-    }
-}
 
 // conforming-space correction e gathered into the DG dofs of cell c: dg2cg[c][a] is the conforming dof of DG dof (c, a)
 // (P1: membrane-broken vertex dofs; P2: vertex + edge dofs of the conforming P2 space) -- pure injection
@@ -78,326 +19,7 @@ template <int NV> __device__ __forceinline__ void prolong_cell(const int32_t* __
     for (int a = 0; a < NV; ++a) add[a] = e[(int64_t)dg2cg[c * NV + a] * nil];
 }
 
-template <int NV> __device__ __forceinline__ void block_matvec(const bjreal* __restrict__ binv, int64_t c, const double* r, double* z) {
-    const bjreal* B = binv + c * NV * NV;
-#pragma unroll
-    for (int a = 0; a < NV; ++a) {
-        double s = 0.0;
-#pragma unroll
-        for (int b = 0; b < NV; ++b) s += (double)B[a * NV + b] * r[b];
-        z[a] = s;
-    }
-}
-
-struct VecDims {
-    int64_t nc_owned, nc;   // vectors are [nsys][nc*NV]; only owned cells are updated / reduced
-    int nsys;
-    // block-Jacobi table (KNP on structured meshes, abi.hip: build_bj_table): the cell's inverse block is entry bj_idx[c] of a small
-    // table instead of 4 NV^2 bytes per cell and species read from HBM in every vector kernel; null -> per-cell inverses
-    const uint16_t* bj_idx;
-    const bjreal* bj_tab;   // [n_entries][nsys][NV*NV]
-    // Residual norms of the stopping tests are weighted with 1 / cell volume: ||r||_w^2 = sum_K |r_K|^2 / vol_K ~ r^T M^-1 r, the L2
-    // norm of the residual's Riesz representative.  r and b are load vectors (int f v_i): their plain 2-norm is dominated by the
-    // largest cells, so that on a mesh with slivers (EMIx: cell volumes over 6 decades) a tolerance on it says nothing about the
-    // small cells, where the max-norm error of the concentrations sits.  On a uniform mesh the weight is a constant factor.
-    const float* ivol;      // [nc], or null (weight 1)
-    // KNP stopping test (d8 != 0): order-8 norms of the residual and load DENSITIES, ||r / vol||_8 <= rtol' ||b / vol||_8, a sum-type
-    // stand-in for  max_K ||r_K|| / vol_K  <=  rtol' max_K ||b_K|| / vol_K.  The concentrations are asked for in the MAX norm, and
-    // the measurement behind this choice (tools/knp_norm_experiment.py, profiles/r03_knp_norms_*.txt: BiCGStab stopped after k
-    // iterations, true max-norm error against the converged solution next to four residual measures) shows the max-norm error at
-    // 0.03-0.055 of this ratio on BOTH mesh families -- the idealized BoxMesh and the EMIx reconstruction, whose cell volumes span
-    // 3.5 decades -- while the (weighted) 2-norm ratio sits 5x above the error on the first and 10x BELOW it on the second (round
-    // 2's per-mesh factor 0.03 on rtol_knp).  Sums of 8th powers ride the same deterministic reduction / all-reduce as the inner
-    // products.
-    int d8;
-};
-__device__ __forceinline__ double cell_weight(const VecDims& d, int64_t c) { return d.ivol ? (double)d.ivol[c] : 1.0; }
-// this cell's term of the residual measure the stopping tests sum: |r_K|^2 / vol_K (weighted 2-norm) or (|r_K| / vol_K)^8 (d8)
-__device__ __forceinline__ double residual_measure(const VecDims& d, int64_t c, double rr) {
-    const double w = cell_weight(d, c);
-    if (!d.d8) return rr * w;
-    const double q = rr * w * w;
-    return (q * q) * (q * q);
-}
-
-// inverse block of system s, cell c: from the table when there is one, else from the per-cell array binv [nsys][nc][NV*NV]
-template <int NV> __device__ __forceinline__ const bjreal* bj_block(const VecDims& d, const bjreal* __restrict__ binv, int s, int64_t c) {
-    return d.bj_idx ? d.bj_tab + ((int64_t)d.bj_idx[c] * d.nsys + s) * (NV * NV) : binv + ((int64_t)s * d.nc + c) * (NV * NV);
-}
-
 #define SYS_PTR(p, s) ((p) + (int64_t)(s) * d.nc * NV)
-
-// ---- second-stage reduction + scalar recurrences ------------------------------------------
-// op codes
-enum { OP_CG_INIT = 1, OP_CG_ALPHA, OP_CG_BETA, OP_BI_INIT, OP_BI_ALPHA, OP_BI_OMEGA, OP_BI_RHO, OP_SUM_ONLY, OP_CG_XA,
-       OP_GM_INIT, OP_GM_RESTART, OP_GM_H, OP_GM_NORM, OP_GM_SOLVE };
-// status word of a system: 0 iterating, 1 converged, 2 breakdown, 3 NaN, 4 (GMRES) this restart cycle is complete, waiting for the update
-
-__device__ void scalar_op(int op, double* S, const double* R, int* flag, int* iter, double rtol, double atol, int min_it, double rabs, int norm8,
-                          double* gm = nullptr, int aux = 0);
-
-// op > 0: the block's thread 0 also runs the scalar recurrence of its system (single-GPU: saves one launch per reduction
-// point; with a communicator the all-reduce sits between the two and k_scalar_op runs separately).
-// Eight partial rows per thread are in flight at a time: with one row per loop trip the 15 trips of the r=2 mesh were 15 dependent
-// L2 round trips (11 us for a kernel that moves 250 KB).
-#define KNP_REDUCE_BLOCK 1024
-template <int NR, int UR = 4>
-__global__ __launch_bounds__(KNP_REDUCE_BLOCK) void k_reduce(const double* __restrict__ partial, int64_t nblocks, int nsys, double* red, int op,
-                                                             double* scal, int* status, double rtol, double atol, int min_it, double rabs, int norm8,
-                                                             int aux) {
-    // one block per system; deterministic order
-    const int s = blockIdx.x;
-    __shared__ double lds[KNP_REDUCE_BLOCK / 64][NR];
-    // thread 0 runs the scalar recurrence at the end: its operands travel with the partial sums instead of behind them
-    double S[KS_N];
-    int flag = 0, iter = 0;
-    if (threadIdx.x == 0 && op > 0) {
-#pragma unroll
-        for (int i = 0; i < KS_N; ++i) S[i] = scal[s * KS_N + i];
-        flag = status[2 * s];
-        iter = status[2 * s + 1];
-    }
-    double acc[NR];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) acc[r] = 0.0;
-    for (int64_t b0 = threadIdx.x; b0 < nblocks; b0 += UR * KNP_REDUCE_BLOCK) {
-        double v[UR][NR];
-#pragma unroll
-        for (int u = 0; u < UR; ++u) {
-            const int64_t b = b0 + (int64_t)u * KNP_REDUCE_BLOCK;
-            const double* p = partial + (b * nsys + s) * KNP_MAX_RED;
-#pragma unroll
-            for (int r = 0; r < NR; ++r) v[u][r] = b < nblocks ? p[r] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < UR; ++u)
-#pragma unroll
-            for (int r = 0; r < NR; ++r) acc[r] += v[u][r];
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const double v = wave_sum(acc[r]);
-        if (lane == 0) lds[wv][r] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double R[KNP_MAX_RED];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            double v = lds[0][r];
-#pragma unroll
-            for (int w = 1; w < KNP_REDUCE_BLOCK / 64; ++w) v += lds[w][r];
-            R[r] = v;
-            red[s * KNP_MAX_RED + r] = v;
-        }
-        if (op > 0) {
-            scalar_op(op, S, R, &flag, &iter, rtol, atol, min_it, rabs, norm8, scal + KNP_GM_OFFSET + s * KNP_GM_STRIDE, aux);
-#pragma unroll
-            for (int i = 0; i < KS_N; ++i) scal[s * KS_N + i] = S[i];
-            status[2 * s] = flag;
-            status[2 * s + 1] = iter;
-        }
-    }
-}
-
-// ---- GMRES scalar work (one system): Hessenberg column, Givens rotations, least-squares right-hand side ------------------------------
-// gm: H[(m + 1) * m] column-major | cs[m] | sn[m] | g[m + 1] | y[m];  m = KNP_GM_MAX.  S[KS_GM_K] = columns of this cycle,
-// S[KS_GM_T2] = 2-norm the Arnoldi residual estimate has to reach before the true residual is looked at again, S[KS_ALPHA] = 1 / beta
-// and S[KS_OMEGA] = 1 / h_{j+1,j} (the scalings of the next basis vector), S[KS_RHO] = the current estimate.
-__device__ __forceinline__ void gm_new_cycle(double* S, const double* R, double* gm, int norm8) {
-    constexpr int M = KNP_GM_MAX;
-    const double beta = sqrt(R[0]);
-    S[KS_BETA] = beta;
-    S[KS_ALPHA] = beta > 0.0 ? 1.0 / beta : 0.0;
-    gm[(M + 1) * M + 2 * M] = beta;                       // g[0]
-    S[KS_GM_K] = 0.0;
-    // the stopping test is on the order-8 density norm (or the weighted 2-norm) of the true residual; the Arnoldi estimate is its plain
-    // 2-norm.  Ask the cycle for the reduction the test still needs (with a margin), then test the true residual and, if it is not
-    // there yet, start the next cycle from it.
-    const double need = S[KS_RES] > 0.0 ? S[KS_TOL] / S[KS_RES] : 1.0;
-    S[KS_GM_T2] = beta * fmin(0.5 * need, 0.1);
-    S[KS_RHO] = beta;
-}
-
-__device__ void gm_scalar_op(int op, double* S, const double* R, int* flag, int* iter, double rtol, double atol, int min_it, int norm8,
-                             double* gm, int aux) {
-    constexpr int M = KNP_GM_MAX;
-    double* H = gm;
-    double* cs = gm + (M + 1) * M;
-    double* sn = cs + M;
-    double* g = sn + M;
-    double* y = g + M + 1;
-    switch (op) {
-        case OP_GM_INIT:                 // R: r.r, ||r||_w^2 | ||r/vol||_8^8, ||b||_w^2 | ||b/vol||_8^8  (k_bi_init)
-        case OP_GM_RESTART: {
-            if (op == OP_GM_RESTART && (*flag == 1 || *flag == 2 || *flag == 3)) return;
-            const double rn = norm8 ? pow(R[1], 0.125) : sqrt(R[1]);
-            if (op == OP_GM_INIT) {
-                S[KS_RES0] = rn;
-                S[KS_BNORM] = norm8 ? pow(R[2], 0.125) : sqrt(R[2]);
-                S[KS_TOL] = fmax(rtol * S[KS_BNORM], atol);
-                *iter = 0;
-            }
-            S[KS_RES] = rn;
-            if (!(rn == rn)) { *flag = 3; return; }
-            if (R[0] == 0.0 || (rn <= S[KS_TOL] && *iter >= min_it)) { *flag = 1; return; }
-            *flag = 0;
-            gm_new_cycle(S, R, gm, norm8);
-        } break;
-        case OP_GM_H: {                  // R[0 .. cnt): w . V_{j0 + i};  aux = j0 | j << 8 | cnt << 16
-            if (*flag) return;
-            const int j0 = aux & 0xff, j = (aux >> 8) & 0xff, cnt = (aux >> 16) & 0xff;
-            for (int i = 0; i < cnt; ++i) H[j0 + i + (M + 1) * j] = R[i];
-        } break;
-        case OP_GM_NORM: {               // R[0] = ||w - sum_i h_ij V_i||^2;  aux = j | cycle length m << 8
-            if (*flag) return;
-            const int j = aux & 0xff, m = (aux >> 8) & 0xff, jlo = (aux >> 16) & 0xff;
-            double* h = H + (M + 1) * j;
-            const double hn = sqrt(R[0]);
-            h[j + 1] = hn;
-            for (int i = 0; i < jlo; ++i) h[i] = 0.0;            // truncated orthogonalisation: nothing was projected out there
-            for (int i = 0; i < j; ++i) {                        // previous rotations on the new column
-                const double t = cs[i] * h[i] + sn[i] * h[i + 1];
-                h[i + 1] = -sn[i] * h[i] + cs[i] * h[i + 1];
-                h[i] = t;
-            }
-            const double den = sqrt(h[j] * h[j] + hn * hn);
-            cs[j] = den > 0.0 ? h[j] / den : 1.0;
-            sn[j] = den > 0.0 ? hn / den : 0.0;
-            h[j] = den;
-            g[j + 1] = -sn[j] * g[j];
-            g[j] = cs[j] * g[j];
-            S[KS_OMEGA] = hn > 0.0 ? 1.0 / hn : 0.0;
-            S[KS_GM_K] = (double)(j + 1);
-            S[KS_RHO] = fabs(g[j + 1]);
-            *iter += 1;
-            if (!(den == den)) { *flag = 3; return; }
-            if (((S[KS_RHO] <= S[KS_GM_T2] || hn == 0.0) && *iter >= min_it) || j + 1 >= m) *flag = 4;     // cycle complete
-        } break;
-        case OP_GM_SOLVE: {              // back substitution of the cycle's k columns; the system takes part in the update (flag 4 -> 0)
-            if (*flag != 0 && *flag != 4) return;
-            const int k = (int)S[KS_GM_K];
-            for (int i = k - 1; i >= 0; --i) {
-                double t = g[i];
-                for (int l = i + 1; l < k; ++l) t -= H[i + (M + 1) * l] * y[l];
-                y[i] = H[i + (M + 1) * i] != 0.0 ? t / H[i + (M + 1) * i] : 0.0;
-            }
-            *flag = 0;
-        } break;
-        default: break;
-    }
-}
-
-// PCG stopping test.  rabs = 0: PETSc's test on the preconditioned norm, ||M^-1 r|| <= max(rtol ||M^-1 b||, atol) (solver.py:425-444).
-// rabs > 0 (knp_emi_residual_target): an error-controlled stop on two quantities that do not depend on the preconditioner --
-//   (i)  the TRUE residual in the order-8 norm of its density, ||(b - A x) / vol||_8 <= rabs: the caller derives rabs from the accuracy
-//        it wants in the concentrations (knpemidg/solver.py), which feel the potential through exactly this residual;
-//   (ii) the ENERGY-NORM ERROR of the iterate, ||x - x_k||_A <= rtol ||x||_A, from the identity of Hestenes and Stiefel
-//        ||x - x_k||_A^2 = sum_{j >= k} alpha_j (r_j . z_j), which holds for PCG with ANY symmetric positive definite preconditioner:
-//        the terms of the sum decay like beta_j = rho_{j+1} / rho_j, so behind iteration k (rho_{k+1}, alpha_k known)
-//        ||x - x_{k+1}||_A^2 ~ alpha_k rho_{k+1} / (1 - q_k), and ||x||_A^2 ~ max(x0 . A x0, sum_j alpha_j rho_j).  q_k is the decay
-//        rate SMOOTHED over the last quarter of the iterations (exponential average of log beta_j with memory max(1, k / 4), capped at
-//        0.999): one beta is noisy (CG's rho is not monotone) and a cap at 0.9 hid slow convergence -- with block-Jacobi alone on the
-//        one-axon mesh (beta ~ 0.96-1.03 for hundreds of steps) the one-step estimate stopped at 3.4x / 5.5x the asked error for
-//        rtol 1e-3 / 1e-5, the smoothed one at 1.1x / 0.3x (tests/krylov_ref.py, tests/test_krylov_stop.py).  For the first four iterations
-//        the memory is one step, i.e. fast (AMG-preconditioned) solves see the plain beta_k as before.
-//        It bounds the error of the potential itself, smooth components included, which no residual norm sees.
-// Round 3 used the preconditioned norm ||M^-1 r|| for (ii); how far that under-reports the error depends on M, and a better
-// preconditioner met it with more error left.  A preconditioned residual of 1e-11 ||M^-1 b|| ends the solve
-// whatever the tests say: targets below what fp64 can reach (rtol_emi 1e-11 of the parity tests) must not loop forever.
-__device__ __forceinline__ bool cg_converged(const double* S, double rabs, double rtol, int iter) {
-    if (!(rabs > 0.0)) return S[KS_RES] <= S[KS_TOL];
-    if (S[KS_RES] <= 1.0e-11 * S[KS_BNORM]) return true;
-    return iter > 0 && S[KS_RNORM] <= rabs && S[KS_CG_EST] <= rtol * sqrt(fmax(S[KS_CG_XA], S[KS_CG_SUM]));
-}
-
-// S: the system's KS_N scalars, R: its reduced sums, flag / iter: its two status words (global memory or local copies)
-__device__ void scalar_op(int op, double* S, const double* R, int* flag, int* iter, double rtol, double atol, int min_it, double rabs, int norm8,
-                          double* gm, int aux) {
-    if (op >= OP_GM_INIT) { gm_scalar_op(op, S, R, flag, iter, rtol, atol, min_it, norm8, gm, aux); return; }
-    if (op != OP_CG_INIT && op != OP_BI_INIT && *flag) return;
-    switch (op) {
-        case OP_CG_INIT: {              // R: rz, zz, (Minv b).(Minv b), ||r||_w^2 | ||r/vol||_8^8
-            S[KS_RHO] = R[0];
-            S[KS_RES0] = sqrt(R[1]);
-            S[KS_RES] = S[KS_RES0];
-            S[KS_BNORM] = sqrt(R[2]);
-            S[KS_TOL] = fmax(rtol * S[KS_BNORM], atol);
-            S[KS_RNORM] = norm8 ? pow(R[3], 0.125) : sqrt(R[3]);
-            S[KS_CG_RN0] = S[KS_RNORM];
-            S[KS_CG_XA] = 0.0;
-            S[KS_CG_SUM] = 0.0;
-            S[KS_CG_EST] = 1.0e300;
-            *iter = 0;
-            *flag = cg_converged(S, rabs, rtol, 0) ? 1 : 0;
-        } break;
-        case OP_CG_XA: {                // R: x0 . A x0 (error-controlled stop only)
-            S[KS_CG_XA] = fmax(R[0], 0.0);
-        } break;
-        case OP_CG_ALPHA: {             // R: p.w
-            S[KS_ALPHA] = (R[0] != 0.0) ? S[KS_RHO] / R[0] : 0.0;
-            S[KS_CG_SUM] += S[KS_ALPHA] * S[KS_RHO];
-            if (R[0] == 0.0) *flag = 2;
-        } break;
-        case OP_CG_BETA: {              // R: rz_new, zz, ||r||_w^2 | ||r/vol||_8^8
-            S[KS_BETA] = (S[KS_RHO] != 0.0) ? R[0] / S[KS_RHO] : 0.0;
-            S[KS_RHO] = R[0];
-            S[KS_RES] = sqrt(R[1]);
-            S[KS_RNORM] = norm8 ? pow(R[2], 0.125) : sqrt(R[2]);
-            *iter += 1;
-            {   // smoothed decay rate of the Hestenes-Stiefel terms (see cg_converged); gm[0]: its running log, free in a PCG solve
-                const double lb = log(fmax(S[KS_BETA], 1.0e-300)), lam = 1.0 / fmax(1.0, 0.25 * (double)*iter);
-                gm[0] = *iter == 1 ? lb : (1.0 - lam) * gm[0] + lam * lb;
-                const double q = fmin(exp(gm[0]), 0.999);
-                S[KS_CG_EST] = sqrt(fmax(S[KS_ALPHA] * R[0], 0.0) / (1.0 - q));
-            }
-            if (cg_converged(S, rabs, rtol, *iter) && *iter >= min_it) *flag = 1;
-            if (!(S[KS_RES] == S[KS_RES])) *flag = 3;                      // NaN
-        } break;
-        case OP_BI_INIT: {              // R: r.r, ||r||_w^2 | ||r/vol||_8^8, ||b||_w^2 | ||b/vol||_8^8 ; norm8 selects the order-8 density test
-            if (norm8) { S[KS_RES0] = pow(R[1], 0.125); S[KS_BNORM] = pow(R[2], 0.125); }
-            else { S[KS_RES0] = sqrt(R[1]); S[KS_BNORM] = sqrt(R[2]); }
-            S[KS_TOL] = fmax(rtol * S[KS_BNORM], atol);
-            S[KS_RES] = S[KS_RES0];
-            S[KS_RHO] = R[0];           // rhat = r0  ->  rho_1 = r0.r0
-            S[KS_RHO_OLD] = 1.0;
-            S[KS_ALPHA] = 1.0;
-            S[KS_OMEGA] = 1.0;
-            S[KS_BETA] = 0.0;
-            *iter = 0;
-            *flag = (R[0] == 0.0) ? 1 : 0;   // exact zero residual: nothing to do (rest state)
-        } break;
-        case OP_BI_ALPHA: {             // R: rhat.v
-            if (R[0] == 0.0) { *flag = (S[KS_RES] <= S[KS_TOL]) ? 1 : 2; S[KS_ALPHA] = 0.0; }   // breakdown at a converged residual (forced min_it iterations of a steady state) is convergence
-            else S[KS_ALPHA] = S[KS_RHO] / R[0];
-        } break;
-        case OP_BI_OMEGA: {             // R: t.s, t.t
-            S[KS_OMEGA] = (R[1] != 0.0) ? R[0] / R[1] : 0.0;
-        } break;
-        case OP_BI_RHO: {               // R: rhat.r, ||r||_w^2 | ||r/vol||_8^8
-            S[KS_RES] = norm8 ? pow(R[1], 0.125) : sqrt(R[1]);
-            *iter += 1;
-            if (S[KS_RES] <= S[KS_TOL] && *iter >= min_it) { *flag = 1; break; }
-            // below the floor of min_it iterations: a residual `rabs` (< 1; knp_knp_early_stop) times under the tolerance ends the solve as well.
-            // The floor keeps the per-step errors of a quiet phase (extrapolated guesses pass the test untouched and their errors pile
-            // up) far below the tolerance; a residual that far below it already does the same.
-            if (rabs > 0.0 && S[KS_RES] <= rabs * S[KS_TOL]) { *flag = 1; break; }
-            if (!(S[KS_RES] == S[KS_RES])) { *flag = 3; break; }
-            if (R[0] == 0.0 || S[KS_OMEGA] == 0.0) { *flag = (S[KS_RES] <= S[KS_TOL]) ? 1 : 2; break; }
-            S[KS_BETA] = (R[0] / S[KS_RHO]) * (S[KS_ALPHA] / S[KS_OMEGA]);
-            S[KS_RHO] = R[0];
-        } break;
-        default: break;
-    }
-}
-
-__global__ void k_scalar_op(int op, int nsys, const double* __restrict__ red, double* __restrict__ scal, int* __restrict__ status,
-                            double rtol, double atol, int min_it, double rabs, int norm8, int aux) {
-    const int s = threadIdx.x;
-    if (s < nsys) scalar_op(op, scal + s * KS_N, red + s * KNP_MAX_RED, status + 2 * s, status + 2 * s + 1, rtol, atol, min_it, rabs, norm8,
-                            scal + KNP_GM_OFFSET + s * KNP_GM_STRIDE, aux);
-}
 
 // ---- PCG kernels ----------------------------------------------------------------------------
 // r = b - w(=A x);  z = Binv r;  p = z;  partials: r.z, z.z, (Binv b).(Binv b)
@@ -514,13 +136,7 @@ __global__ __launch_bounds__(256) void k_cg_update_restrict(VecDims d, const dou
         stv<NV>(z, c, zv);
     }
     __syncthreads();
-    const int p1 = tile_off[blockIdx.x + 1];
-    for (int q = tile_off[blockIdx.x] + threadIdx.x; q < p1; q += 256) {
-        double acc = 0.0;
-        const int e = slot_ptr[q + 1];
-        for (int k = slot_ptr[q]; k < e; ++k) acc += s_r[slot_idx[k]];
-        part[q] = acc;
-    }
+    tile_slot_sums(s_r, tile_off, slot_ptr, slot_idx, part);
 }
 
 // z += P e (conforming correction, gathered through dg2cg) ; partials r.z, z.z, ||r||_w^2 (NR = 3)  |  on init (NR = 4): r.z, z.z,
@@ -664,15 +280,8 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_bi_init(VecDims d, const double* 
         ldv<NV>(SYS_PTR(w, s), c, wv);
 #pragma unroll
         for (int a = 0; a < NV; ++a) { rv[a] = bv[a] - wv[a]; zero[a] = 0.0; acc[0] += rv[a] * rv[a]; acc[2] += bv[a] * bv[a]; }
-        const double wgt = cell_weight(d, c);
-        if (d.d8) {
-            const double qr = acc[0] * wgt * wgt, qb = acc[2] * wgt * wgt;       // squared densities
-            acc[1] = (qr * qr) * (qr * qr);
-            acc[2] = (qb * qb) * (qb * qb);
-        } else {
-            acc[1] = acc[0] * wgt;
-            acc[2] *= wgt;
-        }
+        acc[1] = residual_measure(d, c, acc[0]);
+        acc[2] = residual_measure(d, c, acc[2]);
         stv<NV>(SYS_PTR(r, s), c, rv);
         stv<NV>(SYS_PTR(rhat, s), c, rv);
         if (ZPV) {
@@ -690,7 +299,7 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_bi_p(VecDims d, const double* __r
                                                     const bjreal* __restrict__ binv, double* __restrict__ p, double* __restrict__ y) {
     const int s = blockIdx.y;
     if (status[2 * s]) return;
-    const double beta = scal[s * KS_N + KS_BETA], omega = scal[s * KS_N + KS_OMEGA];
+    const double beta = scal_row(scal, s)[KS_BETA], omega = scal_row(scal, s)[KS_OMEGA];
     const int64_t c = (int64_t)blockIdx.x * KNP_BLOCK + threadIdx.x;
     if (c >= d.nc_owned) return;
     double rv[NV], vv[NV], pv[NV], yv[NV];
@@ -716,7 +325,7 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_bi_s(VecDims d, const double* __r
                                                     double* __restrict__ r, double* __restrict__ z) {
     const int s = blockIdx.y;
     if (status[2 * s]) return;
-    const double alpha = scal[s * KS_N + KS_ALPHA];
+    const double alpha = scal_row(scal, s)[KS_ALPHA];
     const int64_t c = (int64_t)blockIdx.x * KNP_BLOCK + threadIdx.x;
     if (c >= d.nc_owned) return;
     double rv[NV], vv[NV], zv[NV];
@@ -776,14 +385,7 @@ __global__ __launch_bounds__(256) void k_bj_cheb2_restrict(VecDims d, const int*
         stv<NV>(SYS_PTR(y, s), c, yv);
     }
     __syncthreads();
-    part += (int64_t)s * nslots;
-    const int p1 = tile_off[blockIdx.x + 1];
-    for (int p = tile_off[blockIdx.x] + threadIdx.x; p < p1; p += 256) {
-        double acc = 0.0;
-        const int e = slot_ptr[p + 1];
-        for (int k = slot_ptr[p]; k < e; ++k) acc += s_r[slot_idx[k]];
-        part[p] = acc;
-    }
+    tile_slot_sums(s_r, tile_off, slot_ptr, slot_idx, part + (int64_t)s * nslots);
 }
 
 // out = alpha[s] * in  (per system)
@@ -804,7 +406,7 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_bi_x(VecDims d, const double* __r
                                                     double* __restrict__ x, double* __restrict__ r, double* __restrict__ partial) {
     const int s = blockIdx.y;
     if (status[2 * s]) return;
-    const double alpha = scal[s * KS_N + KS_ALPHA], omega = scal[s * KS_N + KS_OMEGA];
+    const double alpha = scal_row(scal, s)[KS_ALPHA], omega = scal_row(scal, s)[KS_OMEGA];
     const int64_t c = (int64_t)blockIdx.x * KNP_BLOCK + threadIdx.x;
     double acc[2] = {0.0, 0.0};
     if (c < d.nc_owned) {
@@ -822,13 +424,7 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_bi_x(VecDims d, const double* __r
             acc[0] += hv[a] * rv[a];
             acc[1] += rv[a] * rv[a];
         }
-        const double wgt = cell_weight(d, c);
-        if (d.d8) {
-            const double q = acc[1] * wgt * wgt;
-            acc[1] = (q * q) * (q * q);
-        } else {
-            acc[1] *= wgt;
-        }
+        acc[1] = residual_measure(d, c, acc[1]);
         stv<NV>(SYS_PTR(x, s), c, xv);
         stv<NV>(SYS_PTR(r, s), c, rv);
     }
@@ -873,10 +469,21 @@ int max_abs_diff(knp_ctx* c, const double* a, const double* b, int nsys, double*
 
 // ---- host drivers ---------------------------------------------------------------------------------
 
+// f(std::integral_constant<int, NV>) for the context's dofs per cell; `unsupported` (may be null) becomes the error text otherwise
+template <typename F> static int dispatch_nd(knp_ctx* c, const char* unsupported, F&& f) {
+    switch (c->nd) {
+        case 3: return f(std::integral_constant<int, 3>());
+        case 4: return f(std::integral_constant<int, 4>());
+        case 6: return f(std::integral_constant<int, 6>());
+        case 10: return f(std::integral_constant<int, 10>());
+    }
+    if (unsupported) c->err = unsupported;
+    return -1;
+}
 
-static int finalize(knp_ctx* c, int op, int nsys, int nred, double rtol, double atol, int min_it, double rabs = 0.0, int norm8 = 0, int aux = 0) {
+static int finalize(knp_ctx* c, int op, int nsys, int nred, const StopTest& st, int aux = 0) {
     const int64_t nb = grid_for(c->m.nc_owned);
-    double* red = c->scal + KNP_MAX_SYS * KS_N;
+    double* red = krylov_red(c);
     const int dop = c->dist ? 0 : op;
     // partial rows in flight per thread: 4 up to 8 192 producer blocks (r=2: 3 888), 8 beyond (r=3: 31 104 blocks were eight
     // dependent trips = 64 us)
@@ -884,9 +491,9 @@ static int finalize(knp_ctx* c, int op, int nsys, int nred, double rtol, double 
 #define KNP_REDUCE(NR_)                                                                                                                  \
     do {                                                                                                                                 \
         if (deep) hipLaunchKernelGGL((k_reduce<NR_, 8>), dim3(nsys), dim3(KNP_REDUCE_BLOCK), 0, c->stream, c->partial, nb, nsys, red, dop,  \
-                                     c->scal, c->status, rtol, atol, min_it, rabs, norm8, aux);                                          \
+                                     c->scal, c->status, st, aux);                                                                       \
         else hipLaunchKernelGGL((k_reduce<NR_, 4>), dim3(nsys), dim3(KNP_REDUCE_BLOCK), 0, c->stream, c->partial, nb, nsys, red, dop,       \
-                                c->scal, c->status, rtol, atol, min_it, rabs, norm8, aux);                                               \
+                                c->scal, c->status, st, aux);                                                                            \
     } while (0)
     switch (nred) {
         case 1: KNP_REDUCE(1); break;
@@ -900,7 +507,7 @@ static int finalize(knp_ctx* c, int op, int nsys, int nred, double rtol, double 
     if (c->dist) {
         int rc = allreduce_red(c, red, nsys * KNP_MAX_RED);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_scalar_op, dim3(1), dim3(64), 0, c->stream, op, nsys, red, c->scal, c->status, rtol, atol, min_it, rabs, norm8, aux);
+        hipLaunchKernelGGL(k_scalar_op, dim3(1), dim3(64), 0, c->stream, op, nsys, red, c->scal, c->status, st, aux);
     }
     HIPCHK(c, hipGetLastError());
     return 0;
@@ -927,8 +534,7 @@ static int poll_status(knp_ctx* c, int nsys, int* host_status) {
 // costs its applies and V-cycles (r=2: about 0.75 ms for KNP, 0.2 ms for EMI), so past the prediction looking every time wins
 // (profiles/r05_poll_tail.txt).  KNP_POLL_TAIL=0 restores the previous rule (every 2, every 1 for 1-2 iteration solves).
 static int poll_tail() {
-    const char* e = getenv("KNP_POLL_TAIL");               // read per call: tests switch it inside one process
-    return e ? atoi(e) : 1;
+    return env_int("KNP_POLL_TAIL", 1);                    // read per call: tests switch it inside one process
 }
 static inline int next_chunk(int it, int maxit, int check_every, int predicted) {
     int chunk = check_every;
@@ -947,7 +553,7 @@ static inline int next_chunk(int it, int maxit, int check_every, int predicted) 
 // of 19 BiCGStab iterations to 1e-6 on the oracle's KNP matrix at the r=2 diffusion number (tools/precond_experiment.py).  The EMI
 // system keeps the additive (symmetric) form PCG needs.  KNP_HYBRID=0 restores the additive form.
 static bool knp_hybrid() {
-    static const bool on = !(getenv("KNP_HYBRID") && atoi(getenv("KNP_HYBRID")) == 0);
+    static const bool on = env_flag("KNP_HYBRID", true);
     return on;
 }
 template <bool EMI> static double bj_lmin_frac() {
@@ -986,14 +592,13 @@ static int bj_cheb2(knp_ctx* c, const VecDims& d, const KrylovVecs& kv, const do
 }
 // whether the second Chebyshev step and the restriction into H can share one pass (KNP_FUSE_RESTRICT=0: two passes, A/B runs)
 static bool fuse_restrict(const knp_ctx* c, const KrylovVecs& kv, const AmgHierarchy& H, int nsys) {
-    const char* e = getenv("KNP_FUSE_RESTRICT");            // read per call: tests switch it inside one process
-    const bool on = !(e && atoi(e) == 0);
+    const bool on = env_flag("KNP_FUSE_RESTRICT", true);    // read per call: tests switch it inside one process
     return on && kv.bj_lmax > 0.0 && H.ready && H.ntiles > 0 && H.ncol == nsys && H.tile_cells * c->nd * sizeof(double) <= 65536;
 }
 
 static bool fuse_update_restrict(const knp_ctx* c, const AmgHierarchy& H) {
-    const char* e = getenv("KNP_FUSE_CG_RESTRICT");        // read per call: tests switch it inside one process
-    return !(e && atoi(e) == 0) && H.ready && H.ntiles > 0 && H.ncol == 1 && H.tile_cells * c->nd * sizeof(double) <= 65536;
+    // KNP_FUSE_CG_RESTRICT is read per call: tests switch it inside one process
+    return env_flag("KNP_FUSE_CG_RESTRICT", true) && H.ready && H.ntiles > 0 && H.ncol == 1 && H.tile_cells * c->nd * sizeof(double) <= 65536;
 }
 
 // power iteration for lambda_max(Binv A) of the batched KNP operator (inf-norm normalisation; max over the species)
@@ -1029,18 +634,49 @@ static int bj_lambda_max_impl(knp_ctx* c, KrylovVecs& kv, int iters, double* out
 }
 
 int knp_bj_lambda_max(knp_ctx* c, KrylovVecs& kv, int iters, double* out, bool emi) {
-    switch (c->nd) {
-        case 3: return emi ? bj_lambda_max_impl<3, true>(c, kv, iters, out) : bj_lambda_max_impl<3, false>(c, kv, iters, out);
-        case 4: return emi ? bj_lambda_max_impl<4, true>(c, kv, iters, out) : bj_lambda_max_impl<4, false>(c, kv, iters, out);
-        case 6: return emi ? bj_lambda_max_impl<6, true>(c, kv, iters, out) : bj_lambda_max_impl<6, false>(c, kv, iters, out);
-        case 10: return emi ? bj_lambda_max_impl<10, true>(c, kv, iters, out) : bj_lambda_max_impl<10, false>(c, kv, iters, out);
+    return dispatch_nd(c, nullptr, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        return emi ? bj_lambda_max_impl<NV, true>(c, kv, iters, out) : bj_lambda_max_impl<NV, false>(c, kv, iters, out);
+    });
+}
+
+// One PCG iteration's  x += alpha p ; r -= alpha w ; z = M^-1 r  with the partial sums r.z, z.z, ||r||_w^2 behind it (H = the EMI hierarchy,
+// or null: block-Jacobi alone).  Three sequences of launches:
+//   no DG-level Chebyshev step, tiles: update fused with stage 1 of the restriction of the new residual (KNP_FUSE_CG_RESTRICT=0: two passes)
+//   Chebyshev step, tiles:             update ; Chebyshev step fused with stage 1 of the restriction (KNP_FUSE_RESTRICT=0: two passes)
+//   otherwise:                         update ; Chebyshev step if there is one ; restriction
+// each followed by the V-cycle and k_prolong_dot, which forms the partial sums from the corrected z (without H: k_cg_update's own)
+template <int NV>
+static int emi_precondition_residual(knp_ctx* c, const VecDims& d, const KrylovVecs& kv, AmgHierarchy* H) {
+    const dim3 g((unsigned)grid_for(c->m.nc_owned)), b(KNP_BLOCK);
+    const bool cheb = kv.bj_lmax > 0.0;
+    int rc;
+    if (H && !cheb && fuse_update_restrict(c, *H)) {
+        if ((rc = amg_restrict_tiles_prepare(c, *H))) return rc;
+        hipLaunchKernelGGL(k_cg_update_restrict<NV>, dim3((unsigned)H->ntiles), dim3(256), sizeof(double) * H->tile_cells * NV, c->stream, d,
+                           c->scal, c->status, kv.p, kv.w, kv.binv, kv.x, kv.r, kv.z, H->tile_cells, (const int32_t*)H->tile_off,
+                           (const int32_t*)H->slot_ptr, (const uint16_t*)H->slot_idx, H->part);
+        if ((rc = amg_restrict_finish(c, *H))) return rc;
+    } else {
+        hipLaunchKernelGGL(k_cg_update<NV>, g, b, 0, c->stream, d, c->scal, c->status, kv.p, kv.w, kv.binv, kv.x, kv.r, kv.z, c->partial);
+        if (!H) return 0;
+        if (fuse_restrict(c, kv, *H, 1)) {
+            if ((rc = bj_cheb2<NV, true>(c, d, kv, kv.r, kv.z, true, H, 0.0))) return rc;
+        } else {
+            if (cheb && (rc = bj_cheb2<NV, true>(c, d, kv, kv.r, kv.z))) return rc;
+            if ((rc = amg_restrict_from_dg(c, *H, kv.r))) return rc;
+        }
     }
-    return -1;
+    if ((rc = amg_vcycle(c, *H))) return rc;
+    hipLaunchKernelGGL((k_prolong_dot<NV, 3>), g, b, 0, c->stream, d, c->status, 1, H->dg2cg, H->levels[0].x, kv.r, kv.z,
+                       (const double*)nullptr, (double*)nullptr, c->partial);
+    return 0;
 }
 
 template <int NV>
 static int pcg_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, int maxit, int check_every, int* niter, double* res) {
     VecDims d{c->m.nc_owned, c->m.nc, 1, nullptr, nullptr, kv.ivol, (kv.d8 && kv.ivol) ? 1 : 0};
+    const StopTest stop{rtol, atol, kv.r_abs, 0, d.d8};
     const dim3 g((unsigned)grid_for(c->m.nc_owned)), b(KNP_BLOCK);
     int rc;
     if ((rc = dist_apply(c, 0, kv.x, kv.coef, kv.w))) return rc;
@@ -1062,11 +698,11 @@ static int pcg_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, int ma
                            kv.v, kv.y, c->partial);
         HIPCHK(c, hipMemcpyAsync(kv.p, kv.z, sizeof(double) * c->m.nc * NV, hipMemcpyDeviceToDevice, c->stream));
     }
-    if ((rc = finalize(c, OP_CG_INIT, 1, 4, rtol, atol, 0, kv.r_abs, d.d8))) return rc;
+    if ((rc = finalize(c, OP_CG_INIT, 1, 4, stop))) return rc;
     if (kv.r_abs > 0.0) {               // ||x0||_A^2 = x0 . A x0: the scale of the energy-norm test (w = A x0 is still intact)
         hipLaunchKernelGGL(k_dot2<NV>, dim3(g.x, 1), b, 0, c->stream, d, kv.x, kv.w, (const double*)nullptr, (const double*)nullptr, c->partial,
                            c->status);
-        if ((rc = finalize(c, OP_CG_XA, 1, 1, rtol, atol, 0))) return rc;
+        if ((rc = finalize(c, OP_CG_XA, 1, 1, stop))) return rc;
     }
     int hs[2] = {0, 0};
     int it = 0;
@@ -1077,61 +713,31 @@ static int pcg_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, int ma
             if ((rc = dist_apply(c, 0, kv.p, kv.coef, kv.w))) return rc;
             hipLaunchKernelGGL(k_dot2<NV>, dim3(g.x, 1), b, 0, c->stream, d, kv.p, kv.w, (const double*)nullptr,
                                (const double*)nullptr, c->partial, c->status);
-            if ((rc = finalize(c, OP_CG_ALPHA, 1, 1, rtol, atol, 0))) return rc;
-            // no DG-level Chebyshev step: the update and stage 1 of the restriction of the new residual in one pass (KNP_FUSE_CG_RESTRICT=0: two)
-            const bool fuse_upd = H && !(kv.bj_lmax > 0.0) && fuse_update_restrict(c, *H);
-            if (fuse_upd) {
-                if ((rc = amg_restrict_tiles_prepare(c, *H))) return rc;
-                hipLaunchKernelGGL(k_cg_update_restrict<NV>, dim3((unsigned)H->ntiles), dim3(256), sizeof(double) * H->tile_cells * NV, c->stream, d,
-                                   c->scal, c->status, kv.p, kv.w, kv.binv, kv.x, kv.r, kv.z, H->tile_cells, (const int32_t*)H->tile_off,
-                                   (const int32_t*)H->slot_ptr, (const uint16_t*)H->slot_idx, H->part);
-                if ((rc = amg_restrict_finish(c, *H))) return rc;
-            } else {
-                hipLaunchKernelGGL(k_cg_update<NV>, g, b, 0, c->stream, d, c->scal, c->status, kv.p, kv.w, kv.binv, kv.x, kv.r, kv.z,
-                                   c->partial);
-            }
-            if (H) {
-                if (fuse_upd) {
-                    // restricted already
-                } else if (fuse_restrict(c, kv, *H, 1)) {
-                    if ((rc = bj_cheb2<NV, true>(c, d, kv, kv.r, kv.z, true, H, 0.0))) return rc;
-                } else {
-                    if (kv.bj_lmax > 0.0 && (rc = bj_cheb2<NV, true>(c, d, kv, kv.r, kv.z))) return rc;
-                    if ((rc = amg_restrict_from_dg(c, *H, kv.r))) return rc;
-                }
-                if ((rc = amg_vcycle(c, *H))) return rc;
-                hipLaunchKernelGGL((k_prolong_dot<NV, 3>), g, b, 0, c->stream, d, c->status, 1, H->dg2cg, H->levels[0].x, kv.r,
-                                   kv.z, (const double*)nullptr, (double*)nullptr, c->partial);
-            }
-            if ((rc = finalize(c, OP_CG_BETA, 1, 3, rtol, atol, 0, kv.r_abs, d.d8))) return rc;
+            if ((rc = finalize(c, OP_CG_ALPHA, 1, 1, stop))) return rc;
+            if ((rc = emi_precondition_residual<NV>(c, d, kv, H))) return rc;
+            if ((rc = finalize(c, OP_CG_BETA, 1, 3, stop))) return rc;
             hipLaunchKernelGGL(k_cg_p<NV>, g, b, 0, c->stream, d, c->scal, c->status, kv.z, kv.p);
         }
         it += chunk;
         if ((rc = poll_status(c, 1, hs))) return rc;
     }
     double hscal[KS_N];
-    HIPCHK(c, hipMemcpy(hscal, c->scal, sizeof(double) * KS_N, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hscal, krylov_scal(c), sizeof(double) * KS_N, hipMemcpyDeviceToHost));
     *niter = hs[1];
     c->last_it_emi = hs[1];
     // the norm the stopping test looked at: the true residual (order-8 density norm) with a residual target, else PETSc's preconditioned norm
     res[0] = kv.r_abs > 0.0 ? hscal[KS_CG_RN0] : hscal[KS_RES0];
     res[1] = kv.r_abs > 0.0 ? hscal[KS_RNORM] : hscal[KS_RES];
     res[2] = kv.r_abs > 0.0 ? hscal[KS_CG_EST] / sqrt(fmax(fmax(hscal[KS_CG_XA], hscal[KS_CG_SUM]), 1.0e-300)) : hscal[KS_BNORM];
-    if (hs[0] == 3) { c->err = "EMI PCG: NaN residual"; return -4; }
-    if (hs[0] != 1) { c->err = "EMI PCG did not converge"; return -3; }
+    if (hs[0] == KS_NAN) { c->err = "EMI PCG: NaN residual"; return -4; }
+    if (hs[0] != KS_CONVERGED) { c->err = "EMI PCG did not converge"; return -3; }
     return 0;
 }
 
 int pcg_solve(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, int maxit, int check_every, int* niter, double* res) {
     if (check_every < 1) check_every = 1;
-    switch (c->nd) {
-        case 3: return pcg_impl<3>(c, kv, rtol, atol, maxit, check_every, niter, res);
-        case 4: return pcg_impl<4>(c, kv, rtol, atol, maxit, check_every, niter, res);
-        case 6: return pcg_impl<6>(c, kv, rtol, atol, maxit, check_every, niter, res);
-        case 10: return pcg_impl<10>(c, kv, rtol, atol, maxit, check_every, niter, res);
-    }
-    c->err = "pcg: unsupported dofs per cell";
-    return -1;
+    return dispatch_nd(c, "pcg: unsupported dofs per cell",
+                       [&](auto nv) { return pcg_impl<decltype(nv)::value>(c, kv, rtol, atol, maxit, check_every, niter, res); });
 }
 
 // out_s += P_s V_s(P_s^T in_s) for every species s with an armed hierarchy (slot 1 + s).  The species' V-cycles are
@@ -1166,13 +772,12 @@ static int knp_coarse_correction(knp_ctx* c, const VecDims& d, const double* in,
     // (partitioned runs keep every species on the context's stream: the row-distributed level 0 exchanges its shared dofs on the
     // main communicator, whose calls must be enqueued in ONE order on every rank -- DESIGN.md section 6)
     const bool fork = na > 1 && !c->dist && c->amg[1 + active[0]].graph_tried && c->amg[1 + active[0]].graph_exec;
-    const bool fork_all = fork;
-    if (!fork_all)
+    if (!fork) {
         for (int i = 0; i < na; ++i) {
             const int s = active[i];
             if ((rc = amg_restrict_from_dg(c, c->amg[1 + s], in + (int64_t)s * d.nc * NV, nullptr, 0, t ? t + (int64_t)s * d.nc * NV : nullptr, ct))) return rc;
         }
-    if (fork) {
+    } else {
         while ((int)c->aux_streams.size() < na - 1) {
             hipStream_t st; hipEvent_t ev;
             HIPCHK(c, hipStreamCreate(&st));
@@ -1192,29 +797,53 @@ static int knp_coarse_correction(knp_ctx* c, const VecDims& d, const double* in,
             st = c->aux_streams[i - 1];
             HIPCHK(c, hipStreamWaitEvent(st, c->fork_event, 0));
         }
-        if (fork_all && (rc = amg_restrict_from_dg(c, H, in + (int64_t)s * d.nc * NV, st, 0, t ? t + (int64_t)s * d.nc * NV : nullptr, ct))) return rc;
+        if (fork && (rc = amg_restrict_from_dg(c, H, in + (int64_t)s * d.nc * NV, st, 0, t ? t + (int64_t)s * d.nc * NV : nullptr, ct))) return rc;
         if ((rc = amg_vcycle(c, H, st))) return rc;
-        if (fork_all || !st)
-            hipLaunchKernelGGL(k_prolong_add<NV>, g1, b, 0, st ? st : c->stream, d, c->status, s, H.dg2cg, H.levels[0].x,
-                               H.ncg, out + (int64_t)s * d.nc * NV);
+        hipLaunchKernelGGL(k_prolong_add<NV>, g1, b, 0, st ? st : c->stream, d, c->status, s, H.dg2cg, H.levels[0].x, H.ncg,
+                           out + (int64_t)s * d.nc * NV);
         if (st) HIPCHK(c, hipEventRecord(c->aux_events[i - 1], st));
     }
-    for (int i = 1; i < na; ++i) {
-        AmgHierarchy& H = c->amg[1 + active[i]];
-        if (!(fork && H.graph_exec)) continue;
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->aux_events[i - 1], 0));
-        if (!fork_all)
-            hipLaunchKernelGGL(k_prolong_add<NV>, g1, b, 0, c->stream, d, c->status, active[i], H.dg2cg, H.levels[0].x,
-                               H.ncg, out + (int64_t)active[i] * d.nc * NV);
+    for (int i = 1; i < na; ++i)
+        if (fork && c->amg[1 + active[i]].graph_exec) HIPCHK(c, hipStreamWaitEvent(c->stream, c->aux_events[i - 1], 0));
+    return 0;
+}
+
+// out (= Binv in on entry) <- M^-1 in for the batched KNP systems: the two-step Chebyshev block-Jacobi smoother when there is one
+// (kv.bj_lmax > 0), then the auxiliary-space coarse correction -- in the hybrid form on the residual the smoother's first step leaves,
+// and with the restriction done in the smoother's pass where the two can share it (fuse_restrict)
+template <int NV>
+static int knp_precondition(knp_ctx* c, const VecDims& d, const KrylovVecs& kv, const double* in, double* out) {
+    int rc;
+    const bool hyb = kv.bj_lmax > 0.0 && knp_hybrid();
+    const double ct = hyb ? 1.0 / bj_theta<false>(kv) : 0.0;
+    const bool fuse = (int)c->amg.size() > 1 && fuse_restrict(c, kv, c->amg[1], d.nsys);
+    if (kv.bj_lmax > 0.0 && (rc = bj_cheb2<NV, false>(c, d, kv, in, out, true, fuse ? &c->amg[1] : nullptr, ct))) return rc;
+    return knp_coarse_correction<NV>(c, d, in, out, hyb ? kv.tmp : nullptr, ct, fuse);
+}
+
+// end of a KNP solve: iteration counts and residual norms of every system out, the prediction for the next solve's status polls, and
+// the error text when a system did not converge
+static int knp_solve_epilogue(knp_ctx* c, int ns, const int* hs, int* niter, double* res, const char* method) {
+    double hscal[KNP_MAX_SYS * KS_N];
+    HIPCHK(c, hipMemcpy(hscal, krylov_scal(c), sizeof(double) * KS_N * ns, hipMemcpyDeviceToHost));
+    int bad = 0;
+    for (int s = 0; s < ns; ++s) {
+        const double* S = scal_row(hscal, s);
+        niter[s] = hs[2 * s + 1];
+        if (s == 0 || niter[s] > c->last_it_knp) c->last_it_knp = niter[s];
+        res[3 * s + 0] = S[KS_RES0];
+        res[3 * s + 1] = S[KS_RES];
+        res[3 * s + 2] = S[KS_BNORM];
+        if (hs[2 * s] != KS_CONVERGED) bad = hs[2 * s] ? hs[2 * s] : -1;
     }
+    if (bad) { c->err = std::string("KNP ") + method + " did not converge (status " + std::to_string(bad) + ")"; return -3; }
     return 0;
 }
 
 // BiCGStab's first iteration with p = v = 0 folded in: k_bi_init does not write the two zero vectors and the first k_bi_p does not
 // read them (same bits: r + beta (0 - omega 0) = r).  KNP_FUSE_BI_FIRST=0: zeros written and read as before.
 static bool bi_first_form() {
-    const char* e = getenv("KNP_FUSE_BI_FIRST");            // read per call: tests switch it inside one process
-    return !(e && atoi(e) == 0);
+    return env_flag("KNP_FUSE_BI_FIRST", true);             // read per call: tests switch it inside one process
 }
 
 template <int NV>
@@ -1222,14 +851,14 @@ static int bicgstab_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, i
                          int* niter, double* res) {
     const int ns = c->p.n_sys;
     VecDims d{c->m.nc_owned, c->m.nc, ns, kv.bj_idx, kv.bj_tab, kv.ivol, (kv.d8 && kv.ivol) ? 1 : 0};
-
+    const StopTest stop{rtol, atol, c->knp_early, min_it, d.d8};
     const dim3 g((unsigned)grid_for(c->m.nc_owned), (unsigned)ns), b(KNP_BLOCK);
     int rc;
     if ((rc = dist_apply(c, 1, kv.x, kv.coef, kv.w))) return rc;
     const bool first_form = bi_first_form();
     if (first_form) hipLaunchKernelGGL((k_bi_init<NV, false>), g, b, 0, c->stream, d, kv.b, kv.w, kv.r, kv.rhat, kv.p, kv.v, c->partial);
     else hipLaunchKernelGGL((k_bi_init<NV, true>), g, b, 0, c->stream, d, kv.b, kv.w, kv.r, kv.rhat, kv.p, kv.v, c->partial);
-    if ((rc = finalize(c, OP_BI_INIT, ns, 3, rtol, atol, min_it, 0.0, d.d8))) return rc;
+    if ((rc = finalize(c, OP_BI_INIT, ns, 3, stop))) return rc;
     int hs[2 * KNP_MAX_SYS];
     auto all_done = [&]() { for (int s = 0; s < ns; ++s) if (!hs[2 * s]) return false; return true; };
     if ((rc = poll_status(c, ns, hs))) return rc;
@@ -1241,41 +870,24 @@ static int bicgstab_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, i
                 hipLaunchKernelGGL((k_bi_p<NV, true>), g, b, 0, c->stream, d, c->scal, c->status, kv.r, kv.v, kv.binv, kv.p, kv.y);
             else
                 hipLaunchKernelGGL((k_bi_p<NV, false>), g, b, 0, c->stream, d, c->scal, c->status, kv.r, kv.v, kv.binv, kv.p, kv.y);
-            const bool hyb = kv.bj_lmax > 0.0 && knp_hybrid();
-            const double ct = hyb ? 1.0 / bj_theta<false>(kv) : 0.0;
-            const bool fuse = (int)c->amg.size() > 1 && fuse_restrict(c, kv, c->amg[1], ns);
-            if (kv.bj_lmax > 0.0 && (rc = bj_cheb2<NV, false>(c, d, kv, kv.p, kv.y, true, fuse ? &c->amg[1] : nullptr, ct))) return rc;
-            if ((rc = knp_coarse_correction<NV>(c, d, kv.p, kv.y, hyb ? kv.tmp : nullptr, ct, fuse))) return rc;
+            if ((rc = knp_precondition<NV>(c, d, kv, kv.p, kv.y))) return rc;
             if ((rc = dist_apply(c, 1, kv.y, kv.coef, kv.v))) return rc;
             hipLaunchKernelGGL(k_dot2<NV>, g, b, 0, c->stream, d, kv.rhat, kv.v, (const double*)nullptr, (const double*)nullptr,
                                c->partial, c->status);
-            if ((rc = finalize(c, OP_BI_ALPHA, ns, 1, rtol, atol, min_it))) return rc;
+            if ((rc = finalize(c, OP_BI_ALPHA, ns, 1, stop))) return rc;
             hipLaunchKernelGGL(k_bi_s<NV>, g, b, 0, c->stream, d, c->scal, c->status, kv.v, kv.binv, kv.r, kv.z);
-            if (kv.bj_lmax > 0.0 && (rc = bj_cheb2<NV, false>(c, d, kv, kv.r, kv.z, true, fuse ? &c->amg[1] : nullptr, ct))) return rc;
-            if ((rc = knp_coarse_correction<NV>(c, d, kv.r, kv.z, hyb ? kv.tmp : nullptr, ct, fuse))) return rc;
+            if ((rc = knp_precondition<NV>(c, d, kv, kv.r, kv.z))) return rc;
             if ((rc = dist_apply(c, 1, kv.z, kv.coef, kv.w))) return rc;
             hipLaunchKernelGGL(k_dot2<NV>, g, b, 0, c->stream, d, kv.w, kv.r, kv.w, kv.w, c->partial, c->status);
-            if ((rc = finalize(c, OP_BI_OMEGA, ns, 2, rtol, atol, min_it))) return rc;
+            if ((rc = finalize(c, OP_BI_OMEGA, ns, 2, stop))) return rc;
             hipLaunchKernelGGL(k_bi_x<NV>, g, b, 0, c->stream, d, c->scal, c->status, kv.y, kv.z, kv.w, kv.rhat, kv.x, kv.r,
                                c->partial);
-            if ((rc = finalize(c, OP_BI_RHO, ns, 2, rtol, atol, min_it, c->knp_early, d.d8))) return rc;
+            if ((rc = finalize(c, OP_BI_RHO, ns, 2, stop))) return rc;
         }
         it += chunk;
         if ((rc = poll_status(c, ns, hs))) return rc;
     }
-    double hscal[KNP_MAX_SYS * KS_N];
-    HIPCHK(c, hipMemcpy(hscal, c->scal, sizeof(double) * KS_N * ns, hipMemcpyDeviceToHost));
-    int bad = 0;
-    for (int s = 0; s < ns; ++s) {
-        niter[s] = hs[2 * s + 1];
-        if (s == 0 || niter[s] > c->last_it_knp) c->last_it_knp = niter[s];
-        res[3 * s + 0] = hscal[s * KS_N + KS_RES0];
-        res[3 * s + 1] = hscal[s * KS_N + KS_RES];
-        res[3 * s + 2] = hscal[s * KS_N + KS_BNORM];
-        if (hs[2 * s] != 1) bad = hs[2 * s] ? hs[2 * s] : -1;
-    }
-    if (bad) { c->err = "KNP BiCGStab did not converge (status " + std::to_string(bad) + ")"; return -3; }
-    return 0;
+    return knp_solve_epilogue(c, ns, hs, niter, res, "BiCGStab");
 }
 
 // ---- restarted GMRES (right preconditioning) ------------------------------------------------------------------------------------
@@ -1305,7 +917,7 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_gm_scale_binv(VecDims d, const in
                                                              const bjreal* __restrict__ binv, double* __restrict__ v, double* __restrict__ y) {
     const int s = blockIdx.y;
     if (status[2 * s]) return;
-    const double a = scal[s * KS_N + slot];
+    const double a = scal_row(scal, s)[slot];
     const int64_t c = (int64_t)blockIdx.x * KNP_BLOCK + threadIdx.x;
     if (c >= d.nc_owned) return;
     double vv[NV], yv[NV];
@@ -1350,7 +962,7 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_gm_update(VecDims d, const int* _
     const int64_t c = (int64_t)blockIdx.x * KNP_BLOCK + threadIdx.x;
     double acc[1] = {0.0};
     if (!status[2 * s] && c < d.nc_owned) {
-        const double* h = scal + KNP_GM_OFFSET + (int64_t)s * KNP_GM_STRIDE + (int64_t)(KNP_GM_MAX + 1) * j;
+        const double* h = &GmState(scal_gm(scal, s)).H(0, j);
         double wv[NV], vv[NV];
         ldv<NV>(SYS_PTR(w, s), c, wv);
         for (int i = jlo; i <= j; ++i) {
@@ -1374,8 +986,8 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_gm_lincomb(VecDims d, const int* 
     if (status[2 * s]) return;
     const int64_t c = (int64_t)blockIdx.x * KNP_BLOCK + threadIdx.x;
     if (c >= d.nc_owned) return;
-    const int k = (int)scal[s * KS_N + KS_GM_K];
-    const double* y = scal + KNP_GM_OFFSET + (int64_t)s * KNP_GM_STRIDE + (KNP_GM_MAX + 1) * KNP_GM_MAX + 3 * KNP_GM_MAX + 1;
+    const int k = (int)scal_row(scal, s)[KS_GM_K];
+    const double* y = GmState(scal_gm(scal, s)).y();
     double uv[NV], vv[NV];
     ldv<NV>(SYS_PTR(u, s), c, uv);
     for (int i = 0; i < k; ++i) {
@@ -1411,31 +1023,27 @@ static int gmres_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, int 
     const int64_t vstride = (int64_t)ns * c->m.nc * NV;
     double* V = kv.gm_V;
     double* Z = kv.gm_V + (int64_t)(m + 1) * vstride;      // Z_j = M^-1 V_j, kept (flexible-GMRES storage): the update x += Z y needs no further preconditioner application
+    const StopTest stop{rtol, atol, 0.0, min_it, d.d8};
     int rc;
-    const bool hyb = kv.bj_lmax > 0.0 && knp_hybrid();
-    const double ct = hyb ? 1.0 / bj_theta<false>(kv) : 0.0;
-    static const int trunc = getenv("KNP_GMRES_TRUNC") ? atoi(getenv("KNP_GMRES_TRUNC")) : 0;
-    // out = M^-1 in : cell-block-Jacobi (two-step Chebyshev) + auxiliary-space coarse correction, as in bicgstab_impl
+    static const int trunc = env_int("KNP_GMRES_TRUNC", 0);
+    // out = M^-1 in (knp_precondition behind this method's own block-Jacobi pass)
     // slot >= 0: `in` is the newest, still unnormalised basis vector; it is scaled by scal[slot] in the same pass
     auto precond = [&](double* in, double* out, int slot) -> int {
         if (slot >= 0) hipLaunchKernelGGL(k_gm_scale_binv<NV>, g, b, 0, c->stream, d, (const int*)c->status, (const double*)c->scal, slot, kv.binv, in, out);
         else hipLaunchKernelGGL(k_gm_binv<NV>, g, b, 0, c->stream, d, (const int*)c->status, kv.binv, (const double*)in, out);
-        int r;
-        const bool fuse = (int)c->amg.size() > 1 && fuse_restrict(c, kv, c->amg[1], ns);
-        if (kv.bj_lmax > 0.0 && (r = bj_cheb2<NV, false>(c, d, kv, in, out, true, fuse ? &c->amg[1] : nullptr, ct))) return r;
-        return knp_coarse_correction<NV>(c, d, in, out, hyb ? kv.tmp : nullptr, ct, fuse);
+        return knp_precondition<NV>(c, d, kv, in, out);
     };
     // r = b - A x into V_0 (unnormalised), norms of the true residual -> convergence test / next cycle
     auto residual = [&](int op) -> int {
         int r;
         if ((r = dist_apply(c, 1, kv.x, kv.coef, kv.w))) return r;
         hipLaunchKernelGGL(k_bi_init<NV>, g, b, 0, c->stream, d, kv.b, kv.w, V, kv.rhat, kv.p, kv.v, c->partial);
-        return finalize(c, op, ns, 3, rtol, atol, min_it, 0.0, d.d8);
+        return finalize(c, op, ns, 3, stop);
     };
     if ((rc = residual(OP_GM_INIT))) return rc;
     int hs[2 * KNP_MAX_SYS];
-    auto any_running = [&]() { for (int s = 0; s < ns; ++s) if (hs[2 * s] == 0) return true; return false; };
-    auto all_done = [&]() { for (int s = 0; s < ns; ++s) if (hs[2 * s] == 0 || hs[2 * s] == 4) return false; return true; };
+    auto any_running = [&]() { for (int s = 0; s < ns; ++s) if (hs[2 * s] == KS_RUNNING) return true; return false; };
+    auto all_done = [&]() { for (int s = 0; s < ns; ++s) if (hs[2 * s] == KS_RUNNING || hs[2 * s] == KS_CYCLE_DONE) return false; return true; };
     if ((rc = poll_status(c, ns, hs))) return rc;
     int it = 0;
     while (!all_done() && it < maxit) {
@@ -1456,48 +1064,30 @@ static int gmres_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, int 
                     const int cnt = std::min(8, j + 1 - j0);
                     hipLaunchKernelGGL(k_gm_dots<NV>, g, b, 0, c->stream, d, (const int*)c->status, (const double*)w, (const double*)V, vstride, j0,
                                        cnt, c->partial);
-                    if ((rc = finalize(c, OP_GM_H, ns, 8, rtol, atol, min_it, 0.0, 0, j0 | (j << 8) | (cnt << 16)))) return rc;
+                    if ((rc = finalize(c, OP_GM_H, ns, 8, stop, gm_aux_pack(j0, j, cnt)))) return rc;
                 }
                 hipLaunchKernelGGL(k_gm_update<NV>, g, b, 0, c->stream, d, (const int*)c->status, (const double*)c->scal, w, (const double*)V,
                                    vstride, j, jlo, c->partial);
-                if ((rc = finalize(c, OP_GM_NORM, ns, 1, rtol, atol, min_it, 0.0, 0, j | (m << 8) | (jlo << 16)))) return rc;
+                if ((rc = finalize(c, OP_GM_NORM, ns, 1, stop, gm_aux_pack(j, m, jlo)))) return rc;
             }
             it += chunk;
             if ((rc = poll_status(c, ns, hs))) return rc;
         }
         // x += M^-1 (V y) for every system that iterated in this cycle; then its true residual decides
-        hipLaunchKernelGGL(k_scalar_op, dim3(1), dim3(64), 0, c->stream, (int)OP_GM_SOLVE, ns, (const double*)(c->scal + KNP_MAX_SYS * KS_N),
-                           c->scal, c->status, rtol, atol, min_it, 0.0, 0, 0);
+        hipLaunchKernelGGL(k_scalar_op, dim3(1), dim3(64), 0, c->stream, (int)OP_GM_SOLVE, ns, (const double*)krylov_red(c), c->scal, c->status,
+                           stop, 0);
         hipLaunchKernelGGL(k_gm_lincomb<NV>, g, b, 0, c->stream, d, (const int*)c->status, (const double*)c->scal, (const double*)Z, vstride, kv.x);
         if ((rc = residual(OP_GM_RESTART))) return rc;
         if ((rc = poll_status(c, ns, hs))) return rc;
     }
-    double hscal[KNP_MAX_SYS * KS_N];
-    HIPCHK(c, hipMemcpy(hscal, c->scal, sizeof(double) * KS_N * ns, hipMemcpyDeviceToHost));
-    int bad = 0;
-    for (int s = 0; s < ns; ++s) {
-        niter[s] = hs[2 * s + 1];
-        if (s == 0 || niter[s] > c->last_it_knp) c->last_it_knp = niter[s];
-        res[3 * s + 0] = hscal[s * KS_N + KS_RES0];
-        res[3 * s + 1] = hscal[s * KS_N + KS_RES];
-        res[3 * s + 2] = hscal[s * KS_N + KS_BNORM];
-        if (hs[2 * s] != 1) bad = hs[2 * s] ? hs[2 * s] : -1;
-    }
-    if (bad) { c->err = "KNP GMRES did not converge (status " + std::to_string(bad) + ")"; return -3; }
-    return 0;
+    return knp_solve_epilogue(c, ns, hs, niter, res, "GMRES");
 }
 
 int gmres_solve(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, int maxit, int min_it, int check_every, int* niter, double* res) {
     if (check_every < 1) check_every = 1;
     if (!kv.gm_V || kv.gm_m < 2 || kv.gm_m > KNP_GM_MAX) { c->err = "gmres: no basis storage"; return -1; }
-    switch (c->nd) {
-        case 3: return gmres_impl<3>(c, kv, rtol, atol, maxit, min_it, check_every, niter, res);
-        case 4: return gmres_impl<4>(c, kv, rtol, atol, maxit, min_it, check_every, niter, res);
-        case 6: return gmres_impl<6>(c, kv, rtol, atol, maxit, min_it, check_every, niter, res);
-        case 10: return gmres_impl<10>(c, kv, rtol, atol, maxit, min_it, check_every, niter, res);
-    }
-    c->err = "gmres: unsupported dofs per cell";
-    return -1;
+    return dispatch_nd(c, "gmres: unsupported dofs per cell",
+                       [&](auto nv) { return gmres_impl<decltype(nv)::value>(c, kv, rtol, atol, maxit, min_it, check_every, niter, res); });
 }
 
 // partial sums of the load measure the stopping tests use (residual_measure: (|b_K| / vol_K)^8, or |b_K|^2 / vol_K without d8)
@@ -1522,18 +1112,15 @@ int load_measure(knp_ctx* c, const double* b, const float* ivol, bool d8, double
     const int ns = c->p.n_sys;
     VecDims d{c->m.nc_owned, c->m.nc, ns, nullptr, nullptr, ivol, (d8 && ivol) ? 1 : 0};
     const dim3 g((unsigned)grid_for(c->m.nc_owned), (unsigned)ns), blk(KNP_BLOCK);
-    switch (c->nd) {
-        case 3: hipLaunchKernelGGL(k_load_measure<3>, g, blk, 0, c->stream, d, b, c->partial); break;
-        case 4: hipLaunchKernelGGL(k_load_measure<4>, g, blk, 0, c->stream, d, b, c->partial); break;
-        case 6: hipLaunchKernelGGL(k_load_measure<6>, g, blk, 0, c->stream, d, b, c->partial); break;
-        case 10: hipLaunchKernelGGL(k_load_measure<10>, g, blk, 0, c->stream, d, b, c->partial); break;
-        default: c->err = "load_measure: unsupported dofs per cell"; return -1;
-    }
+    const int rc = dispatch_nd(c, "load_measure: unsupported dofs per cell", [&](auto nv) {
+        hipLaunchKernelGGL(k_load_measure<decltype(nv)::value>, g, blk, 0, c->stream, d, b, c->partial);
+        return 0;
+    });
+    if (rc) return rc;
     // second stage without the all-reduce and without a scalar recurrence behind it
     const int64_t nb = grid_for(c->m.nc_owned);
-    double* red = c->scal + KNP_MAX_SYS * KS_N;
-    hipLaunchKernelGGL((k_reduce<1, 8>), dim3(ns), dim3(KNP_REDUCE_BLOCK), 0, c->stream, c->partial, nb, ns, red, 0, c->scal, c->status, 0.0, 0.0, 0,
-                       0.0, 0, 0);
+    double* red = krylov_red(c);
+    hipLaunchKernelGGL((k_reduce<1, 8>), dim3(ns), dim3(KNP_REDUCE_BLOCK), 0, c->stream, c->partial, nb, ns, red, 0, c->scal, c->status, StopTest{}, 0);
     HIPCHK(c, hipGetLastError());
     double h[KNP_MAX_SYS * KNP_MAX_RED];
     HIPCHK(c, hipMemcpyAsync(h, red, sizeof(double) * (size_t)ns * KNP_MAX_RED, hipMemcpyDeviceToHost, c->stream));
@@ -1545,12 +1132,6 @@ int load_measure(knp_ctx* c, const double* b, const float* ivol, bool d8, double
 int bicgstab_solve(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, int maxit, int min_it, int check_every, int* niter,
                    double* res) {
     if (check_every < 1) check_every = 1;
-    switch (c->nd) {
-        case 3: return bicgstab_impl<3>(c, kv, rtol, atol, maxit, min_it, check_every, niter, res);
-        case 4: return bicgstab_impl<4>(c, kv, rtol, atol, maxit, min_it, check_every, niter, res);
-        case 6: return bicgstab_impl<6>(c, kv, rtol, atol, maxit, min_it, check_every, niter, res);
-        case 10: return bicgstab_impl<10>(c, kv, rtol, atol, maxit, min_it, check_every, niter, res);
-    }
-    c->err = "bicgstab: unsupported dofs per cell";
-    return -1;
+    return dispatch_nd(c, "bicgstab: unsupported dofs per cell",
+                       [&](auto nv) { return bicgstab_impl<decltype(nv)::value>(c, kv, rtol, atol, maxit, min_it, check_every, niter, res); });
 }

@@ -13,8 +13,36 @@ enum { KS_CG_XA = KS_RHO_OLD, KS_CG_EST = KS_OMEGA, KS_CG_SUM = KS_GM_T2, KS_CG_
 // restarted GMRES (gmres_solve): per system the Hessenberg matrix (column-major, leading dimension m + 1), the Givens rotations, the
 // rotated right-hand side g and the solution y of the small least-squares problem live behind the Krylov scalars in knp_ctx::scal
 #define KNP_GM_MAX 30
-#define KNP_GM_STRIDE ((KNP_GM_MAX + 1) * KNP_GM_MAX + 3 * KNP_GM_MAX + KNP_GM_MAX + 1 + 5)
-#define KNP_GM_OFFSET (KNP_MAX_SYS * KS_N + KNP_MAX_SYS * KNP_MAX_RED)      // doubles in front of the GMRES state in knp_ctx::scal
+// one system's GMRES state, H | cs | sn | g | y (+ 5 doubles of padding), seen through its base pointer (krylov_gm)
+struct GmLayout {
+    static constexpr int M = KNP_GM_MAX, LDH = M + 1;
+    static constexpr int CS = LDH * M, SN = CS + M, G = SN + M, Y = G + M + 1, SIZE = Y + M + 5;
+};
+template <typename T> struct GmState : GmLayout {        // T = double, or const double in the kernels that only read it
+    T* base;
+    __host__ __device__ explicit GmState(T* b) : base(b) {}
+    __host__ __device__ T& H(int i, int j) const { return base[i + LDH * j]; }
+    __host__ __device__ T* cs() const { return base + CS; }
+    __host__ __device__ T* sn() const { return base + SN; }
+    __host__ __device__ T* g() const { return base + G; }
+    __host__ __device__ T* y() const { return base + Y; }
+    // PCG: running average of log beta (scalar_op: OP_CG_BETA).  It borrows H(0, 0), free in a PCG solve
+    __host__ __device__ T& cg_log_beta() const { return base[0]; }
+};
+#define KNP_GM_STRIDE (GmLayout::SIZE)
+
+// knp_ctx::scal: KS_N scalars per system | reduction results, KNP_MAX_RED per system (also the all-reduce scratch of comm.hip) | GMRES state
+#define KNP_RED_OFFSET (KNP_MAX_SYS * KS_N)
+#define KNP_GM_OFFSET (KNP_RED_OFFSET + KNP_MAX_SYS * KNP_MAX_RED)      // doubles in front of the GMRES state in knp_ctx::scal
+#define KNP_SCAL_DOUBLES (KNP_GM_OFFSET + KNP_MAX_SYS * KNP_GM_STRIDE)  // the allocation (abi.hip)
+static_assert(KNP_GM_STRIDE == 1056 && KNP_GM_OFFSET == KNP_MAX_SYS * (KS_N + KNP_MAX_RED) &&
+              KNP_SCAL_DOUBLES == KNP_MAX_SYS * (KS_N + KNP_MAX_RED + GmLayout::SIZE), "regions of knp_ctx::scal");
+template <typename T> __host__ __device__ inline T* scal_row(T* scal, int s) { return scal + s * KS_N; }
+template <typename T> __host__ __device__ inline T* scal_red(T* scal) { return scal + KNP_RED_OFFSET; }
+template <typename T> __host__ __device__ inline T* scal_gm(T* scal, int s) { return scal + KNP_GM_OFFSET + s * KNP_GM_STRIDE; }
+inline double* krylov_scal(const knp_ctx* c, int s = 0) { return scal_row(c->scal, s); }
+inline double* krylov_red(const knp_ctx* c) { return scal_red(c->scal); }
+inline double* krylov_gm(const knp_ctx* c, int s) { return scal_gm(c->scal, s); }
 
 struct KrylovVecs {
     double *x, *b, *coef;                  // unknown, rhs, operator coefficient (kappa | dnphi)
@@ -30,6 +58,13 @@ struct KrylovVecs {
     double* gm_V = nullptr;                // GMRES: Krylov basis [gm_m + 1][nsys][nc*nd]
     int gm_m = 0;                          // GMRES: restart length (<= KNP_GM_MAX)
     double r_abs = 0.0;                    // PCG: > 0 -> error-controlled stop on the true residual and the energy-norm error estimate (krylov.hip: cg_converged)
+};
+
+// the stopping test of one solve, by value into the reductions' scalar recurrences (krylov_scalar.hpp); rabs: the residual target
+// of PCG (KrylovVecs::r_abs) or the early-stop factor of BiCGStab (knp_ctx::knp_early), norm8: order-8 density norms (VecDims::d8)
+struct StopTest {
+    double rtol, atol, rabs;
+    int min_it, norm8;
 };
 
 // sums over the owned cells of the load measure of the stopping tests, per species (krylov.hip: residual_measure); not all-reduced

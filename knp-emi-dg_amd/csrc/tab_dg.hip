@@ -680,7 +680,7 @@ static int need_tabs(knp_ctx* c, std::initializer_list<int> slots) {
     } while (0)
 
 bool p2_assembled() {
-    static const bool on = getenv("KNP_P2_ASSEMBLED") && atoi(getenv("KNP_P2_ASSEMBLED")) == 1;
+    static const bool on = env_int("KNP_P2_ASSEMBLED", 0) == 1;
     return on;
 }
 
