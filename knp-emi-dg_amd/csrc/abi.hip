@@ -338,7 +338,7 @@ int knp_ctx_create(knp_ctx** out, int device, int dim, int degree, int n_ions, i
             for (int64_t b = 0; b < long0; ++b) std::copy(lists[(size_t)b].begin(), lists[(size_t)b].end(), hsrc.begin() + b * hs);
             rc |= dev_alloc_copy(c, &m.hb_src, hsrc.data(), hsrc.size());
             rc |= dev_alloc_copy(c, &m.hb_loc, hloc.data(), hloc.size());
-            rc |= dev_zeros(c, &c->halo_ctr, 2 * 2 * 64 * 32);          // [2 operators][2 sets][64 queues], one 128-byte line per counter
+            rc |= dev_zeros(c, &c->halo_ctr, KNP_HALO_CTR_INTS);
             m.hb_stride = hs;
             m.hb_long0 = long0;
         }

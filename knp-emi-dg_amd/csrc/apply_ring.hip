@@ -506,8 +506,8 @@ static size_t ring_lds_bytes(const knp_ctx* c, int which) {
 // which 0: EMI, 1: KNP.  Structured 3D P1 meshes with class records, halo lists of at most 224 entries and (KNP) a material table for
 // at most two solved species; KNP_APPLY_RING=0 selects the thread-per-cell kernels of apply_p1.hip (A/B runs)
 bool ring_usable(const knp_ctx* c, int which) {
-    if (c->degree != 1 || c->m.dim != 3 || !c->m.cls || c->m.ncls > 32 || !c->m.hb_src || c->m.hb_stride <= 0 || c->m.hb_stride > RH) return false;
-    if (env_int("KNP_APPLY_RING", 1) == 0 || ring_lds_bytes(c, which) > 160 * 1024) return false;
+    if (c->degree != 1 || c->m.dim != 3 || !c->m.cls || c->m.ncls > CLS_MAX_LDS || !c->m.hb_src || c->m.hb_stride <= 0 || c->m.hb_stride > RH) return false;
+    if (env_int("KNP_APPLY_RING", 1) == 0 || ring_lds_bytes(c, which) > RING_MAX_LDS) return false;
     if (which == 0) return env_int("KNP_EMI_RING", 1) != 0;
     return c->nmat > 0 && c->p.n_sys <= 2 && env_int("KNP_APPLY_MAT", 1) != 0 && env_int("KNP_APPLY_HALO", 1) != 0;
 }

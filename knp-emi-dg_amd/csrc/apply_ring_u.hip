@@ -616,7 +616,7 @@ int64_t ring_u_cells(knp_ctx* c, int which) {
     if (c->degree != 1 || c->m.dim != 3 || c->m.cls || c->m.nc_owned < RB || c->m.nv >= (int64_t(1) << 31)) return 0;
     if (env_int("KNP_APPLY_RING_U", 1) == 0 || env_int("KNP_APPLY_RING", 1) == 0) return 0;
     if (which == 1 && !(c->nmat > 0 && c->p.n_sys <= 2 && env_int("KNP_APPLY_MAT", 1) != 0)) return 0;
-    if (ring_u_lds(c, which) > 160 * 1024) return 0;
+    if (ring_u_lds(c, which) > RING_MAX_LDS) return 0;
     RingUState& S = state_u(c);
     if (!S.tried) {
         S.tried = true;
@@ -639,15 +639,12 @@ int ring_u_knp_apply(knp_ctx* c, const MeshDev& m, const double* x, const double
     const RingUTables& T = state_u(c).T;
     const size_t lds = ring_u_lds(c, 1);
     const dim3 g = ring_grid(m, c->device, reserve_cus);
-    if (c->p.n_sys == 1) {
-        if (!grant_lds(k_knp_apply_ring_u<1>, lds)) { c->err = "hipFuncSetAttribute(k_knp_apply_ring_u) failed"; return -2; }
-        hipLaunchKernelGGL((k_knp_apply_ring_u<1>), g, dim3(RB + 64 * ULOADERS), lds, c->stream, m, T, x, gphi, y, ka, (const uint8_t*)c->mat,
+    return dispatch_nsys<2>(c->p.n_sys, [&](auto ns) {               // ring_u_cells admits one or two solved species
+        const auto kernel = k_knp_apply_ring_u<decltype(ns)::value>;
+        if (!grant_lds(kernel, lds)) { c->err = "hipFuncSetAttribute(k_knp_apply_ring_u) failed"; return -2; }
+        hipLaunchKernelGGL(kernel, g, dim3(RB + 64 * ULOADERS), lds, c->stream, m, T, x, gphi, y, ka, (const uint8_t*)c->mat,
                            (const uint8_t*)c->nmat4, (const double*)c->dtab);
-    } else {
-        if (!grant_lds(k_knp_apply_ring_u<2>, lds)) { c->err = "hipFuncSetAttribute(k_knp_apply_ring_u) failed"; return -2; }
-        hipLaunchKernelGGL((k_knp_apply_ring_u<2>), g, dim3(RB + 64 * ULOADERS), lds, c->stream, m, T, x, gphi, y, ka, (const uint8_t*)c->mat,
-                           (const uint8_t*)c->nmat4, (const double*)c->dtab);
-    }
-    HIPCHK(c, hipGetLastError());
-    return 0;
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    });
 }

@@ -338,9 +338,6 @@ int halo_exchange(knp_ctx* c, double* v, int nfields) {
 // input vector (pack kernel + grouped ncclSend/ncclRecv on the halo stream, through a communicator of its own so that it can
 // run next to an all-reduce of the solver's stream) overlaps the interior launch; the boundary launch waits for it.
 // Per apply and rank: 2 messages per peer and field (one each way), cells_on_the_cut x nd x 8 B each.
-int launch_emi_apply(knp_ctx* c, const double* x, const double* kappa, double* y);
-int launch_knp_apply(knp_ctx* c, const double* x, const double* dnphi, double* y);
-
 int dist_apply(knp_ctx* c, int which, double* x, const double* coef, double* y) {
     auto launch = [&]() { return which == 0 ? launch_emi_apply(c, x, coef, y) : launch_knp_apply(c, x, coef, y); };
     if (!c->dist) {

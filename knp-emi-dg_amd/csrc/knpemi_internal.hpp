@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <map>
 #include "amg.hpp"
@@ -54,6 +55,8 @@ struct MeshDev {
 #define KNP_CLS_EXT 32
 #define KNP_HALO_BLK 256
 #define KNP_MAX_MAT 16
+#define CLS_MAX_LDS 32          // most geometry classes whose records the LDS-staged and ring-staged applies keep in LDS
+#define KNP_HALO_CTR_INTS (2 * 2 * 64 * 32)   // knp_ctx::halo_ctr: [2 operators][2 sets][64 queues], one 128-byte line per counter (apply_p1_halo.hpp)
 
 struct Params {
     int n_ions = 0;                // total species, last one eliminated
@@ -99,7 +102,7 @@ struct knp_ctx {
     std::vector<uint16_t> h_cls, h_mat;
     std::vector<uint32_t> h_fflag;
     std::vector<uint8_t> h_mf_mask;  // [nf] 1 on membrane facets: what knp_rec_create checks the caller's facet sets against
-    int* halo_ctr = nullptr;       // [2 operators][2 sets][64 queues] block counters of the persistent halo-staged applies (apply_p1.hip)
+    int* halo_ctr = nullptr;       // [KNP_HALO_CTR_INTS] block counters of the persistent halo-staged applies (apply_p1_halo.hpp)
     int halo_flip[2] = {0, 0};
     double* rho = nullptr;         // [nc]
     double* fsrc = nullptr;        // [n_sys][nc] DG0 source on ECS cells, or null
@@ -193,6 +196,26 @@ inline int env_int(const char* name, int dflt) {
 }
 inline bool env_flag(const char* name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; }
 
+inline int64_t grid_for(int64_t n) { return (n + KNP_BLOCK - 1) / KNP_BLOCK; }
+
+// KERN<3> or KERN<2> by the mesh dimension, KNP_BLOCK threads per block
+#define DISPATCH_DIM(c, KERN, grid, ...)                                                         \
+    do {                                                                                         \
+        if ((c)->m.dim == 3) hipLaunchKernelGGL(KERN<3>, grid, dim3(KNP_BLOCK), 0, (c)->stream, __VA_ARGS__); \
+        else hipLaunchKernelGGL(KERN<2>, grid, dim3(KNP_BLOCK), 0, (c)->stream, __VA_ARGS__);    \
+        HIPCHK(c, hipGetLastError());                                                            \
+    } while (0)
+
+// f(std::integral_constant<int, NS>) for NS = n_sys in 1..MAXNS, the kernel instances the caller has; -1 for any other count
+template <int MAXNS, typename F> int dispatch_nsys(int n_sys, F&& f) {
+    static_assert(MAXNS >= 1 && MAXNS <= 4, "instances exist for at most four solved species");
+    if (n_sys == 1) return f(std::integral_constant<int, 1>());
+    if constexpr (MAXNS >= 2) if (n_sys == 2) return f(std::integral_constant<int, 2>());
+    if constexpr (MAXNS >= 3) if (n_sys == 3) return f(std::integral_constant<int, 3>());
+    if constexpr (MAXNS >= 4) if (n_sys == 4) return f(std::integral_constant<int, 4>());
+    return -1;
+}
+
 // ---- launchers implemented in the .hip files --------------------------------------------
 int launch_emi_apply(knp_ctx* c, const double* x, const double* kappa, double* y);
 int launch_knp_apply(knp_ctx* c, const double* x, const double* dnphi, double* y);
@@ -243,7 +266,6 @@ int halo_exchange(knp_ctx* c, double* v, int nfields);
 // launch; with one, interior cells are computed while the exchange is in flight on the halo stream / communicator (comm.hip)
 int dist_apply(knp_ctx* c, int which, double* x, const double* coef, double* y);
 
-int64_t grid_for(int64_t n);
 int launch_nernst_only(knp_ctx* c, const double* cc, const double* celim, double* E);
 void comm_destroy(knp_ctx* c);
 int allreduce_red(knp_ctx* c, double* red, int count);

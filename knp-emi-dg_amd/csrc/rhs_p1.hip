@@ -469,13 +469,6 @@ static IonArgs ion_args(knp_ctx* c) {
     return ia;
 }
 
-#define DISPATCH_DIM(c, KERN, grid, ...)                                                         \
-    do {                                                                                         \
-        if ((c)->m.dim == 3) hipLaunchKernelGGL(KERN<3>, grid, dim3(KNP_BLOCK), 0, (c)->stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL(KERN<2>, grid, dim3(KNP_BLOCK), 0, (c)->stream, __VA_ARGS__);    \
-        HIPCHK(c, hipGetLastError());                                                            \
-    } while (0)
-
 // DISPATCH_DIM for the kernels with a CLS flag: the coordinate path
 #define DISPATCH_DIM2(c, KERN, grid, ...)                                                        \
     do {                                                                                         \

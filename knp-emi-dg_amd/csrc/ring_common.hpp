@@ -88,6 +88,7 @@ __device__ __forceinline__ int64_t list_cell(const lds_int* L, int e, int hs) {
 }
 
 // ---- host side of the launches ----
+constexpr size_t RING_MAX_LDS = 160 * 1024;   // LDS per workgroup: the CU's 160 KB
 inline int device_cus(int device) {
     static int ncu = 0;
     if (!ncu) {

@@ -131,6 +131,22 @@ def test_abi_library_exports_every_declared_symbol():
     assert set(_abi.SIGNATURES) == declared
 
 
+def test_apply_plan_selects_the_asserted_kernel_families(tmp_path):
+    """csrc/apply_plan.hpp is the one definition of which kernel family an operator apply runs (the launchers walk it,
+    knp_apply_variant reports its head).  tools/apply_plan_check.cpp, plain host C++, checks it against the variant codes the GPU
+    parity / edge tests assert and checks the head / tail segments of a cell range."""
+    import shutil
+    import subprocess
+    cxx = shutil.which(os.environ.get("CXX", "g++"))
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path / "apply_plan_check")
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "knp-emi-dg_amd", "csrc"),
+                    os.path.join(ROOT, "tools", "apply_plan_check.cpp"), "-o", exe], check=True)
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert run.returncode == 0 and "apply plan ok" in run.stdout, run.stdout
+
+
 def test_product_never_imports_oracle():
     """The oracle is test infrastructure: nothing under knp-emi-dg_amd/ may import or execute it."""
     pkg = os.path.join(ROOT, "knp-emi-dg_amd")
