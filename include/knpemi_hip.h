@@ -304,6 +304,38 @@ int knp_rec_map_arm(knp_ctx* ctx, double t0);
 int knp_rec_map_read(knp_ctx* ctx, int64_t n, double* t_act, double* t_repol, double* peak, double* t_peak, int32_t* n_up);
 int knp_rec_destroy(knp_ctx* ctx);
 
+/* ---- checkpoint of the step-to-step state (csrc/state.hip; DESIGN.md section 4.3 lists every member saved or rebuilt).
+ * A snapshot is one host buffer: a 32-byte prologue (magic "KNPSTATE", version, block count, payload bytes), the block table
+ * (one knp_state_block per block) and the payloads at the table's offsets.  A block is [ncomp][count][width] elements:
+ *   KNP_SK_CELL_DOF        count = cells, width = values per cell; in the CALLER's cell numbering (knp_state_cell_order)
+ *   KNP_SK_FACET           count = facets (the caller's numbering is the device's)
+ *   KNP_SK_MEMBRANE_FACET  count = nodes of one membrane model or facets of the recorder's map, in the order they were created with
+ *   KNP_SK_OPAQUE          counters and small device buffers, no mesh meaning
+ * Device blocks are packed by one gather kernel per family into one staging buffer that crosses the bus in one copy through pinned
+ * memory; knp_state_load runs the scatter kernels the other way.  Neither goes through knp_upload, so the history counters of the
+ * extrapolated initial guesses, the ages of the lagged block inverses and their spectral bounds come back as saved; KAPPA is
+ * recomputed from the restored concentrations and the state-independent KNP block table is rebuilt before the inverses land.
+ *  knp_state_cell_order: order[d] = caller's id of device cell d (a permutation of 0..nc-1; null = identity, the default)
+ *  knp_state_describe  : writes up to cap table entries, returns the number of blocks (< 0: error); *bytes = size of a snapshot
+ *  knp_state_save      : bytes must be the size knp_state_describe reports
+ *  knp_state_load      : -8 when the buffer's block table differs from this context's (cell count, degree, ion count, membrane-model
+ *                        layout, recorder configuration): nothing has been touched then.  Call it after the last knp_set_params.
+ *  Both return -7 with a communicator active: snapshots of several ranks are not supported.
+ *  knp_state_timing    : device milliseconds of the pack kernels and of the bus copy of the last save or load */
+enum knp_state_kind { KNP_SK_OPAQUE = 0, KNP_SK_CELL_DOF = 1, KNP_SK_FACET = 2, KNP_SK_MEMBRANE_FACET = 3 };
+enum knp_state_type { KNP_ST_F64 = 0, KNP_ST_F32 = 1, KNP_ST_I32 = 2, KNP_ST_I64 = 3 };
+typedef struct knp_state_block {
+    int32_t id, kind, type, ncomp;
+    int64_t count, width;
+    int64_t offset;              /* bytes from the start of the snapshot */
+} knp_state_block;
+#define KNP_STATE_PROLOGUE 32
+int knp_state_cell_order(knp_ctx* ctx, const int64_t* order);
+int64_t knp_state_describe(knp_ctx* ctx, knp_state_block* out, int64_t cap, int64_t* bytes);
+int knp_state_save(knp_ctx* ctx, void* host_buf, size_t bytes);
+int knp_state_load(knp_ctx* ctx, const void* host_buf, size_t bytes);
+int knp_state_timing(knp_ctx* ctx, float* pack_ms, float* copy_ms);
+
 /* ---- membrane ODEs: batched device integrator replacing the per-facet LSODA loop of
  * MembraneModel.step_lsoda (membrane.py:84-119).  model: 1 = Hodgkin-Huxley + stimulus (examples/idealized-geometries/mm_hh.py),
  * 2 = without (mm_hh_no_stim.py), 3 = EMIx neuron (examples/emix-simulations/mm_hh.py), 4 = EMIx glia (mm_glial.py), 5 = passive

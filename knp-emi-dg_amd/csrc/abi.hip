@@ -384,6 +384,7 @@ void knp_ctx_destroy(knp_ctx* c) {
     if (c->fork_event) hipEventDestroy(c->fork_event);
     ode_destroy_all(c);
     rec_destroy(c);
+    state_destroy(c);
     tab_free(c);
     Fields* fl = g_fields[c];
     if (fl) {
@@ -1114,3 +1115,77 @@ int knp_halo_exchange(knp_ctx* c, int field) {
 }
 
 }  // extern "C"
+
+// ---- checkpoint: the step-to-step state this file owns (state.hip packs it) ----------------------------------
+// Saved: the fields one step hands to the next, both solution histories with their counters, the LAGGED block-Jacobi inverses with
+// their ages and spectral bounds (rebuilt from the current coefficients they would differ from the ones the uninterrupted run still
+// applies), the reference iteration counts that trigger a new bound, last_peclet and the residual target.
+enum { SB_PHI = 1, SB_C, SB_C_PREV, SB_C_ELIM, SB_PHI_M, SB_I_CH, SB_E, SB_HIST_EMI, SB_HIST_KNP, SB_BINV_EMI, SB_BINV_KNP, SB_COUNTERS, SB_REALS };
+#define SB_N_COUNTERS 11
+#define SB_N_REALS 4
+
+static void fields_apply_host(knp_ctx* c, int id, const char* data) {
+    Fields* f = F(c);
+    if (id == SB_COUNTERS) {
+        int64_t v[SB_N_COUNTERS];
+        memcpy(v, data, sizeof(v));
+        f->nh_emi = (int)v[0]; f->nh_knp = (int)v[1]; f->bj_age_emi = (int)v[2]; f->bj_age_knp = (int)v[3];
+        f->bj_lmax_age = (int)v[4]; f->bj_lmax_emi_age = (int)v[5]; f->it_ref_knp = (int)v[6]; f->it_ref_emi = (int)v[7];
+        f->bj_used_tab = (int)v[8]; c->last_it_emi = (int)v[9]; c->last_it_knp = (int)v[10];
+    } else if (id == SB_REALS) {
+        double v[SB_N_REALS];
+        memcpy(v, data, sizeof(v));
+        f->bj_lmax_knp = v[0]; f->bj_lmax_emi = v[1]; f->emi_r_abs = v[2]; c->last_peclet = (float)v[3];
+    }
+}
+
+int fields_state_blocks(knp_ctx* c, std::vector<StateBlk>& out) {
+    Fields* f = F(c);
+    const int64_t nc = c->m.nc, nf = c->m.nf;
+    const int nd = c->nd, ns = c->p.n_sys, ni = c->p.n_ions;
+    // the histories are allocated by the first solve that extrapolates: a snapshot holds them always (zeros and a counter of 0 before)
+    if (!f->hist_emi) { HIPCHK(c, hipMalloc((void**)&f->hist_emi, sizeof(double) * 2 * f->n[KNP_F_PHI])); HIPCHK(c, hipMemset(f->hist_emi, 0, sizeof(double) * 2 * f->n[KNP_F_PHI])); }
+    if (!f->hist_knp) { HIPCHK(c, hipMalloc((void**)&f->hist_knp, sizeof(double) * 2 * f->n[KNP_F_C])); HIPCHK(c, hipMemset(f->hist_knp, 0, sizeof(double) * 2 * f->n[KNP_F_C])); }
+    auto cell = [&](int id, int type, int ncomp, int width, void* dev) {
+        StateBlk b; b.id = id; b.kind = KNP_SK_CELL_DOF; b.type = type; b.ncomp = ncomp; b.count = nc; b.width = width; b.dev = dev;
+        out.push_back(b);
+    };
+    auto facet = [&](int id, int ncomp, void* dev) {
+        StateBlk b; b.id = id; b.kind = KNP_SK_FACET; b.type = KNP_ST_F64; b.ncomp = ncomp; b.count = nf; b.width = 1; b.dev = dev;
+        out.push_back(b);
+    };
+    cell(SB_PHI, KNP_ST_F64, 1, nd, f->f[KNP_F_PHI]);
+    cell(SB_C, KNP_ST_F64, ns, nd, f->f[KNP_F_C]);
+    cell(SB_C_PREV, KNP_ST_F64, ns, nd, f->f[KNP_F_C_PREV]);
+    cell(SB_C_ELIM, KNP_ST_F64, 1, nd, f->f[KNP_F_C_ELIM]);
+    facet(SB_PHI_M, 1, f->f[KNP_F_PHI_M]);
+    facet(SB_I_CH, ni, f->f[KNP_F_I_CH]);
+    facet(SB_E, ni, f->f[KNP_F_E]);
+    cell(SB_HIST_EMI, KNP_ST_F64, 2, nd, f->hist_emi);
+    cell(SB_HIST_KNP, KNP_ST_F64, 2 * ns, nd, f->hist_knp);
+    cell(SB_BINV_EMI, KNP_ST_F32, 1, nd * nd, f->binv_emi);
+    cell(SB_BINV_KNP, KNP_ST_F32, ns, nd * nd, f->binv_knp);
+    {
+        const int64_t v[SB_N_COUNTERS] = {f->nh_emi, f->nh_knp, f->bj_age_emi, f->bj_age_knp, f->bj_lmax_age, f->bj_lmax_emi_age, f->it_ref_knp,
+                                          f->it_ref_emi, f->bj_used_tab, c->last_it_emi, c->last_it_knp};
+        StateBlk b; b.id = SB_COUNTERS; b.kind = KNP_SK_OPAQUE; b.type = KNP_ST_I64; b.apply = fields_apply_host;
+        state_push_host(b, v, SB_N_COUNTERS);
+        out.push_back(b);
+    }
+    {
+        const double v[SB_N_REALS] = {f->bj_lmax_knp, f->bj_lmax_emi, f->emi_r_abs, (double)c->last_peclet};
+        StateBlk b; b.id = SB_REALS; b.kind = KNP_SK_OPAQUE; b.type = KNP_ST_F64; b.apply = fields_apply_host;
+        state_push_host(b, v, SB_N_REALS);
+        out.push_back(b);
+    }
+    return 0;
+}
+
+// A fresh context builds the drift-free KNP block table inside its first solve and uses the per-cell inverse array as scratch for it:
+// done here instead, BEFORE the saved inverses are scattered over that array, so that the first solve after a load finds the table
+// ready and the lagged inverses as the interrupted run left them.
+int fields_state_prepare_load(knp_ctx* c) {
+    Fields* f = F(c);
+    if (f->bj_tab_state == 0) return build_bj_table(c, f);
+    return 0;
+}

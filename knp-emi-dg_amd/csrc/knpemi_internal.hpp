@@ -276,5 +276,23 @@ int allreduce_sum_host(knp_ctx* c, double* host_values, int n);    // sum of n <
 // (same bits on every owner: added in rank order).  On the context's stream; 2 messages per peer (comm.hip)
 int interface_accumulate(knp_ctx* c, double* v, int64_t n, int ncol);
 int max_abs_diff(knp_ctx* c, const double* a, const double* b, int nsys, double* out);
+// ---- checkpoint (state.hip): every source file lists the step-to-step state it owns as blocks [ncomp][count][width]
+struct StateBlk {
+    int id = 0, kind = 0, type = 0, ncomp = 1;    // knp_state_kind / knp_state_type (include/knpemi_hip.h)
+    int64_t count = 0, width = 1;
+    void* dev = nullptr;                           // device array, or null: host values
+    std::vector<char> host;                        // host values as they are now (what a save writes)
+    void (*apply)(knp_ctx*, int id, const char* data) = nullptr;   // host values: takes a loaded block
+};
+int fields_state_blocks(knp_ctx* c, std::vector<StateBlk>& out);   // abi.hip: fields, solution histories, lagged inverses, counters
+int fields_state_prepare_load(knp_ctx* c);                         // abi.hip: builds what a first solve would build over restored arrays
+int ode_state_blocks(knp_ctx* c, std::vector<StateBlk>& out);      // ode.hip: state / parameter tables and step sizes of every model
+int rec_state_blocks(knp_ctx* c, std::vector<StateBlk>& out);      // record.hip: ring, row counter, map accumulators
+void state_destroy(knp_ctx* c);                                    // state.hip: staging buffers of the context
+template <typename T> inline void state_push_host(StateBlk& b, const T* v, int64_t n) {
+    b.count = n;
+    b.host.assign((const char*)v, (const char*)v + sizeof(T) * (size_t)n);
+}
+
 void rec_destroy(knp_ctx* c);       // record.hip: frees the context's time-series recorder, if any
 int ode_check_failed(knp_ctx* c);   // ode.hip: reads and clears the ODE failure flag (stream idle); sets c->err

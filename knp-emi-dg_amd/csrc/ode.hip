@@ -263,6 +263,25 @@ bool ode_state_table(knp_ctx* c, int handle, const double** states, int64_t* n, 
 
 static void rtc_unload_all(knp_ctx* c);
 
+// checkpoint (state.hip): per model the state and parameter tables and the last accepted step size of every node, in the node order
+// the model was created with (the caller's).  Block ids 1000 + 8 handle + {0, 1, 2}; the widths carry the model layout, so a snapshot
+// of other models does not load.  The stimulus mask and values are configuration: the host sends them again.
+int ode_state_blocks(knp_ctx* c, std::vector<StateBlk>& out) {
+    auto it = g_ode.find(c);
+    if (it == g_ode.end()) return 0;
+    for (size_t h = 0; h < it->second.size(); ++h) {
+        OdeSet& S = it->second[h];
+        void* dev[3] = {S.states, S.params, S.h};
+        const int width[3] = {S.ns, S.np, 1};
+        for (int q = 0; q < 3; ++q) {
+            StateBlk b;
+            b.id = 1000 + 8 * (int)h + q; b.kind = KNP_SK_MEMBRANE_FACET; b.type = KNP_ST_F64; b.count = S.n; b.width = width[q]; b.dev = dev[q];
+            out.push_back(b);
+        }
+    }
+    return 0;
+}
+
 void ode_destroy_all(knp_ctx* c) {
     rtc_unload_all(c);
     auto it = g_ode.find(c);

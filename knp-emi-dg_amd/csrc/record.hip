@@ -303,6 +303,39 @@ Recorder* rec_find(knp_ctx* c, const char* who) {
 
 }  // namespace
 
+// checkpoint (state.hip): the row buffer with its times, the device row counter, the map accumulators and the host-side counters.  The
+// sizes carry the configuration (capacity, channels, map facets): a snapshot of another recorder does not load.  Block ids 2000 + q.
+static void rec_apply_host(knp_ctx* c, int, const char* data) {
+    auto it = g_rec.find(c);
+    if (it == g_rec.end()) return;
+    int64_t v[3];
+    memcpy(v, data, sizeof(v));
+    it->second.rows_host = v[0]; it->second.map_k = v[1]; it->second.map_armed = v[2] != 0;
+}
+
+int rec_state_blocks(knp_ctx* c, std::vector<StateBlk>& out) {
+    auto it = g_rec.find(c);
+    if (it == g_rec.end()) return 0;
+    Recorder& R = it->second;
+    auto push = [&](int id, int kind, int type, int ncomp, int64_t count, int64_t width, void* dev) {
+        StateBlk b; b.id = id; b.kind = kind; b.type = type; b.ncomp = ncomp; b.count = count; b.width = width; b.dev = dev;
+        out.push_back(b);
+    };
+    push(2000, KNP_SK_OPAQUE, KNP_ST_F64, 1, R.capacity, R.n_ch + 1, R.buf);       // [capacity][n_ch] rows, then [capacity] times
+    push(2001, KNP_SK_OPAQUE, KNP_ST_I32, 1, 1, 1, R.count);
+    if (R.n_map) {
+        push(2002, KNP_SK_MEMBRANE_FACET, KNP_ST_F64, 1, R.n_map, 1, R.map_prev);
+        push(2003, KNP_SK_MEMBRANE_FACET, KNP_ST_F64, 4, R.n_map, 1, R.map_out);
+        push(2004, KNP_SK_MEMBRANE_FACET, KNP_ST_I32, 1, R.n_map, 1, R.map_out + 4 * R.n_map);
+        push(2005, KNP_SK_OPAQUE, KNP_ST_F64, 1, 2, 1, R.t_hist);
+    }
+    const int64_t v[3] = {R.rows_host, R.map_k, R.map_armed ? 1 : 0};
+    StateBlk b; b.id = 2006; b.kind = KNP_SK_OPAQUE; b.type = KNP_ST_I64; b.apply = rec_apply_host;
+    state_push_host(b, v, 3);
+    out.push_back(b);
+    return 0;
+}
+
 void rec_destroy(knp_ctx* c) {
     auto it = g_rec.find(c);
     if (it == g_rec.end()) return;

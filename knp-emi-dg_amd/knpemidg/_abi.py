@@ -125,6 +125,11 @@ SIGNATURES = {
     "knp_rec_add_map": (C.c_int, [_ctxp, C.c_int64, _i32p, C.c_double, C.c_double]),
     "knp_rec_map_arm": (C.c_int, [_ctxp, C.c_double]),
     "knp_rec_map_read": (C.c_int, [_ctxp, C.c_int64, _f64p, _f64p, _f64p, _f64p, _i32p]),
+    "knp_state_cell_order": (C.c_int, [_ctxp, _i64p]),
+    "knp_state_describe": (C.c_int64, [_ctxp, C.c_void_p, C.c_int64, _i64p]),
+    "knp_state_save": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t]),
+    "knp_state_load": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t]),
+    "knp_state_timing": (C.c_int, [_ctxp, _f32p, _f32p]),
 }
 
 _lib = None
@@ -469,6 +474,9 @@ class Device:
             raise KnpError("knp_ctx_create failed (%d): %s" % (rc, msg.decode() if msg else "?"))
         if self.n_interior != n_own:
             self._chk(self.lib.knp_set_interior(self.ctx, self.n_interior), "knp_set_interior")
+        if reorder and nc:
+            # checkpoints are written in the caller's cell numbering: the library permutes on the device (csrc/state.hip)
+            self._chk(self.lib.knp_state_cell_order(self.ctx, _p(np.ascontiguousarray(order, dtype=np.int64), _i64p)), "knp_state_cell_order")
         self.n_geometry_classes = 0
         _stamp("device: knp_ctx_create")
         self.nranks = 1
@@ -925,6 +933,38 @@ class Device:
     def rec_destroy(self):
         self._chk(self.lib.knp_rec_destroy(self.ctx), "knp_rec_destroy")
 
+    # -- checkpoint of the step-to-step state (csrc/state.hip; knpemidg/checkpoint.py reads and writes the files) ----------
+    def state_describe(self):
+        """(block table as a structured array of checkpoint.BLOCK_DTYPE, size of a snapshot in bytes)."""
+        from knpemidg.checkpoint import BLOCK_DTYPE
+        nbytes = C.c_int64(0)
+        n = int(self.lib.knp_state_describe(self.ctx, None, 0, C.byref(nbytes)))
+        if n < 0:
+            self._chk(n, "knp_state_describe")
+        table = np.zeros(n, dtype=BLOCK_DTYPE)
+        n2 = int(self.lib.knp_state_describe(self.ctx, table.ctypes.data_as(C.c_void_p), n, C.byref(nbytes)))
+        if n2 != n:
+            self._chk(n2 if n2 < 0 else -1, "knp_state_describe")
+        return table, int(nbytes.value)
+
+    def state_save(self):
+        """One snapshot (uint8 array: prologue, block table, payloads in the caller's numbering); synchronises."""
+        _, nbytes = self.state_describe()
+        buf = np.zeros(nbytes, dtype=np.uint8)
+        self._chk(self.lib.knp_state_save(self.ctx, buf.ctypes.data_as(C.c_void_p), nbytes), "knp_state_save")
+        return buf
+
+    def state_load(self, buf):
+        """Restore a snapshot of state_save; KnpError (-8) and an untouched context when its block table is not this context's."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        self._chk(self.lib.knp_state_load(self.ctx, buf.ctypes.data_as(C.c_void_p), buf.size), "knp_state_load")
+
+    def state_timing(self):
+        """(pack kernels ms, bus copy ms) of the last state_save / state_load, from HIP events."""
+        a, b = C.c_float(0), C.c_float(0)
+        self._chk(self.lib.knp_state_timing(self.ctx, C.byref(a), C.byref(b)), "knp_state_timing")
+        return a.value, b.value
+
 
 def _flushing(fn):
     def wrapped(self, *a, **k):
@@ -940,7 +980,7 @@ for _name in ("close", "set_params", "set_mms", "upload", "download", "copy_fiel
               "knp_apply", "emi_rhs", "knp_rhs", "emi_solve", "knp_solve", "step_updates", "picard_updates", "max_abs_diff",
               "nernst", "sync", "timer_begin", "timer_end", "bench_apply", "ode_table", "ode_step", "ode_set_stimulus",
               "amg_upload", "amg_interface", "halo_exchange", "knp_load_measure", "apply_timing_read", "comm_init", "set_interior", "rec_sample",
-              "rec_read", "rec_add_states", "rec_map_arm", "rec_map_read"):
+              "rec_read", "rec_add_states", "rec_map_arm", "rec_map_read", "state_save", "state_load"):
     setattr(Device, _name, _flushing(getattr(Device, _name)))
 
 

@@ -168,6 +168,23 @@ class MembraneModel:
         if self.on_device:
             self._dev.ode_table(self._handle, 1, self._parameters.shape, upload=self._parameters)
 
+    # --- checkpoint (Solver.save_checkpoint): a device-backed model's tables travel in the device snapshot (csrc/ode.hip), its time
+    # with the solver's host state; a host model brings its tables and step sizes itself
+    def host_state(self, prefix):
+        if self.on_device or not self.nodes:
+            return {}
+        out = {prefix + "states": self._states, prefix + "parameters": self._parameters}
+        if self._h is not None:
+            out[prefix + "h"] = np.asarray(self._h, dtype=np.float64)
+        return out
+
+    def load_host_state(self, prefix, arrays):
+        if self.on_device or prefix + "states" not in arrays:
+            return
+        self._states = np.asarray(arrays[prefix + "states"], dtype=np.float64).reshape(self._states.shape).copy()
+        self._parameters = np.asarray(arrays[prefix + "parameters"], dtype=np.float64).reshape(self._parameters.shape).copy()
+        self._h = np.asarray(arrays[prefix + "h"], dtype=np.float64).copy() if prefix + "h" in arrays else None
+
     # --- ODE <- PDE
     def set_state(self, which, u, locator=None):
         return self.__set_ODE('state', which, u, locator=locator)

@@ -392,6 +392,25 @@ class Recorder:
         self._rows.append(rows)
         self._waiting = 0
 
+    # -- checkpoint (Solver.save_checkpoint) ---------------------------------------------
+    def host_state(self, prefix):
+        """The rows already read back and the host's view of the device buffer; the buffer itself, its row counter and the map
+        accumulators travel in the device snapshot (csrc/record.hip), so saving reads nothing back and changes nothing."""
+        out = {prefix + "flags": np.asarray([self._waiting, int(self._armed), getattr(self, "n_channels", 0)], dtype=np.int64)}
+        if self._rows:
+            out[prefix + "rows"] = np.concatenate(self._rows)
+            out[prefix + "t"] = np.concatenate(self._t)
+        return out
+
+    def load_host_state(self, prefix, arrays):
+        flags = arrays.get(prefix + "flags")
+        if flags is None or int(flags[2]) != getattr(self, "n_channels", 0):
+            raise KnpError("checkpoint: the recorder layout differs (field 'recorder': %s channels in the file, %d here)"
+                           % ("no" if flags is None else int(flags[2]), getattr(self, "n_channels", 0)))
+        self._waiting, self._armed = int(flags[0]), bool(flags[1])
+        self._rows = [np.asarray(arrays[prefix + "rows"], dtype=np.float64)] if prefix + "rows" in arrays else []
+        self._t = [np.asarray(arrays[prefix + "t"], dtype=np.float64)] if prefix + "t" in arrays else []
+
     # -- results ------------------------------------------------------------------
     @property
     def rows(self):

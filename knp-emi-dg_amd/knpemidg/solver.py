@@ -51,6 +51,18 @@ def _f(v):
     return float(v)
 
 
+def _names(ode, what):
+    """State / parameter names of a model module in column order, or their count where the module has no name table."""
+    key = "STATE_IND" if what == "state" else "PARAM_IND"
+    table = getattr(ode, key, None)
+    if table is None:                                 # the built-in HH variants share the tables of models/_hh_core.py
+        fn = getattr(ode, "state_indices" if what == "state" else "parameter_indices", None)
+        table = getattr(sys.modules.get(getattr(fn, "__module__", None)), key, None)
+    if isinstance(table, dict):
+        return [str(x) for x in sorted(table, key=table.get)]
+    return int(len(ode.init_state_values() if what == "state" else ode.init_parameter_values()))
+
+
 class Solver:
     def __init__(self, params, ion_list, degree_emi=1, degree_knp=1, mms=None, sf=1):
         self.ion_list = ion_list
@@ -384,7 +396,12 @@ class Solver:
         if explicit is None and os.environ.get("KNP_EMI_CHEB") is not None:
             explicit = int(os.environ["KNP_EMI_CHEB"]) != 0                # the device reads the same variable as an override (csrc/abi.hip)
         self._emi_trial = None if explicit is not None else True
-        return True if explicit is None else bool(explicit)
+        recorded = (getattr(self, "_resume_header", None) or {}).get("emi_dg_chebyshev")
+        if explicit is None and recorded is not None:
+            self._emi_trial = None                                         # a resumed run keeps the choice its first part measured
+            explicit = bool(recorded)
+        self._emi_cheb_chosen = True if explicit is None else bool(explicit)
+        return self._emi_cheb_chosen
 
     def _emi_smoother_trial(self, solve):
         """Measured choice of the EMI DG-level smoother, on the FIRST EMI system of the run: the same right-hand side is solved from the
@@ -416,6 +433,7 @@ class Solver:
             print(" EMI DG-level smoother: Chebyshev step %.3f ms / decade, plain block-Jacobi %.3f ms / decade -> %s"
                   % (1e3 * on, 1e3 * off, "Chebyshev" if keep else "plain"))
         self._emi_trial = None
+        self._emi_cheb_chosen = bool(keep)
         if keep:                                                   # the last solve ran without the step: redo with the chosen one
             dev.set_emi_dg_smoother(True)
             dev.upload(_abi.F_PHI, phi0)
@@ -876,6 +894,7 @@ class Solver:
         t.assign(float(t + self.dt))
         if self.recorder is not None:
             self.recorder.sample(float(t))
+        self._k_done, self._t_done = k + 1, float(t)          # what a checkpoint written now continues from
         return
 
     # ------------------------------------------------------------------ Picard variant (solver.py:850-927)
@@ -902,6 +921,7 @@ class Solver:
         if self.recorder is not None:
             self.recorder.sample(float(t))
         self.picard_iters = getattr(self, "picard_iters", []) + [it]
+        self._k_done, self._t_done, self._picard = k + 1, float(t), True
         if self.verbose:
             print(f" Summary Picard: eps = {eps}, #iters = {it}")
         return
@@ -923,30 +943,41 @@ class Solver:
         if filename is None and (self.save_solver_stats or self.save_fields):
             print("Please specify filename when initiating Solver.solve_system_*() method")
             sys.exit(0)
+        # a resumed run writes a SECOND PART next to the files of the first: results_from<k>.h5 (with /step_offset = k; its vector_0 is the
+        # restored state) and solver_from<k>/; timeseries.h5 is written whole, the recorder carries the rows of the first part
+        k0 = int(getattr(self, "_resume_k", 0) or 0)
+        part = "_from%d" % k0 if k0 else ""
         if self.save_fields:
-            self.init_h5_savefile(filename + 'results.h5')                          # solver.py:978, 1063
+            self.init_h5_savefile(filename + 'results%s.h5' % part)                 # solver.py:978, 1063
+            if k0:
+                self.h5_file.write("/step_offset", np.asarray([k0], dtype=np.int64))
         if self.save_solver_stats:
-            self.init_solver_stats(filename + 'solver/')
+            self.init_solver_stats(filename + 'solver%s/' % part)
 
     # ------------------------------------------------------------------ solve_system_passive (solver.py:930-1011)
     def solve_system_passive(self, Tstop, t, solver_params, membrane_params, filename=None, save_fields=False,
-                             save_solver_stats=False):
+                             save_solver_stats=False, *, checkpoint_every=None, checkpoint_file=None, resume=None):
+        """checkpoint_every / checkpoint_file / resume: see solve_system_active."""
         self.filename = filename
         self.save_fields = save_fields
         self.save_solver_stats = save_solver_stats
         self._unpack_solver_params(solver_params)
         self.splitting_scheme = False
+        ckpt = self._checkpoint_args(checkpoint_every, checkpoint_file, resume)
         self.setup_varform_emi()
         self.setup_varform_knp()
         self.setup_solver_emi()
         self.setup_solver_knp()
+        k0 = self.load_checkpoint(resume, t=t) if resume is not None else 0
         self._check_output_args(filename)
-        if self.recorder is not None:
+        if self.recorder is not None and k0 == 0:
             self.recorder.arm(float(t))
-        for k in range(int(round(Tstop / float(self.dt)))):
+        for k in range(k0, int(round(Tstop / float(self.dt)))):
             self.solve_for_time_step(k, t)
             if (k % self.sf) == 0 and self.save_fields:
                 self.save_h5()
+            if ckpt is not None and (k + 1) % ckpt[0] == 0:
+                self.save_checkpoint(ckpt[1])
         if self.save_fields:
             self.close_h5()
         self._save_timeseries()
@@ -956,18 +987,25 @@ class Solver:
         return uh, self.ion_list[-1]['c']
 
     # ------------------------------------------------------------------ solve_system_active (solver.py:1014-1135)
-    def solve_system_active(self, Tstop, t, solver_params, filename=None, save_fields=False, save_solver_stats=False):
+    def solve_system_active(self, Tstop, t, solver_params, filename=None, save_fields=False, save_solver_stats=False, *,
+                            checkpoint_every=None, checkpoint_file=None, resume=None):
+        """checkpoint_every = N writes `checkpoint_file` (default <filename>checkpoint.h5) after every N-th completed step;
+        resume = path continues the run a checkpoint was written from: the setups run as usual, the state is loaded, `t` is set and
+        the loop runs from the stored step to round(Tstop / dt) (knpemidg/checkpoint.py).  All three default
+        to off: nothing is written and no step changes."""
         self.filename = filename
         self.save_fields = save_fields
         self.save_solver_stats = save_solver_stats
         self._unpack_solver_params(solver_params)
         self.splitting_scheme = True
+        ckpt = self._checkpoint_args(checkpoint_every, checkpoint_file, resume)
         self.setup_varform_emi()
         self.setup_varform_knp()
         self.setup_solver_emi()
         self.setup_solver_knp()
+        k0 = self.load_checkpoint(resume, t=t) if resume is not None else 0
         self._check_output_args(filename)
-        for k in range(int(round(Tstop / float(self.dt)))):
+        for k in range(k0, int(round(Tstop / float(self.dt)))):
             self.step_membrane_models(k)
             if k == 0 and self.recorder is not None:
                 # the time loop starts: with phi_M_init_type 'constant' PHI_M holds the membrane potential only from here on (it
@@ -976,12 +1014,136 @@ class Solver:
             self.solve_for_time_step(k, t)
             if (k % self.sf) == 0 and self.save_fields:
                 self.save_h5()
+            if ckpt is not None and (k + 1) % ckpt[0] == 0:
+                self.save_checkpoint(ckpt[1])
         if self.save_fields:
             self.close_h5()
         self._save_timeseries()
         if self.save_solver_stats:
             self.close_solver_stats()
         return
+
+    # ------------------------------------------------------------------ checkpoint / resume (no reference counterpart: knpemidg/checkpoint.py)
+    def _checkpoint_args(self, every, path, resume):
+        """(N, file) of the periodic checkpoints or None; with `resume`, reads the file's header before the setups run (the recorded
+        smoother choice replaces the first-step trial)."""
+        self._resume_header = None
+        self._resume_k = 0
+        if resume is not None:
+            from knpemidg import checkpoint
+            self._resume_header = checkpoint.read_checkpoint(resume)[0]
+        if every is None:
+            return None
+        if int(every) < 1:
+            raise _abi.KnpError("checkpoint_every must be a positive number of steps")
+        if path is None:
+            if self.filename is None:
+                raise _abi.KnpError("checkpoint_every needs checkpoint_file (or filename, for <filename>checkpoint.h5)")
+            path = self.filename + "checkpoint.h5"
+        return int(every), path
+
+    def _checkpoint_mode(self, picard=None):
+        if picard if picard is not None else getattr(self, "_picard", False):
+            return "picard"
+        return "splitting" if getattr(self, "splitting_scheme", True) else "passive"
+
+    def _checkpoint_header(self, picard=None):
+        """The fields a checkpoint is checked against (checkpoint.CHECKED_FIELDS) plus what a reader wants to know about the run."""
+        from knpemidg import checkpoint
+        models = [{"name": getattr(m['ode'].ode, "__name__", "ode").split(".")[-1], "tag": int(m['ode'].tag), "nodes": int(m['ode'].nodes),
+                   "on_device": bool(m['ode'].on_device), "states": _names(m['ode'].ode, "state"), "parameters": _names(m['ode'].ode, "parameter")}
+                  for m in self.mem_models]
+        sp = getattr(self, "solver_params", None)
+        ref = getattr(self, "_amg_refresh", None) or {}
+        return {
+            "dt": float(self.dt),
+            "ions": [[str(ion['name']), float(ion['z'])] for ion in self.ion_list],
+            "degrees": [int(self.degree_emi), int(self.degree_knp)],
+            "n_cells": int(self.mesh.num_cells()), "n_vertices": int(self.mesh.coords.shape[0]),
+            "mesh_hash": checkpoint.mesh_hash(self.mesh.coords, self.mesh.cells),
+            "mode": self._checkpoint_mode(picard),
+            "models": models,
+            "rtc_hash": [checkpoint.source_hash(getattr(m['ode'].ode, "HIP_RHS", None)) for m in self.mem_models],
+            "solver_params": {k: (v if isinstance(v, (bool, int, float, str, type(None))) else repr(v)) for k, v in sp._asdict().items()}
+            if hasattr(sp, "_asdict") else None,
+            "emi_dg_chebyshev": getattr(self, "_emi_cheb_chosen", None) if (self.use_amg and not getattr(self, "direct_emi", False)) else None,
+            "emi_trial_pending": getattr(self, "_emi_trial", None) is not None,
+            "amg_refresh": {"solves": int(ref.get("solves", 0)), "ref": ref.get("ref"), "high": int(ref.get("high", 0)),
+                            "refreshes": int(getattr(self, "amg_refreshes", 0))},
+        }
+
+    def save_checkpoint(self, path, t=None, k=None):
+        """Write the complete step-to-step state after the last completed step to one HDF5 file (knpemidg/checkpoint.py): the device
+        snapshot in the caller's numbering plus the host-side state of the solver, the membrane models and the recorder.  t, k default
+        to the end of the last step this solver took.  Written under a temporary name and renamed: never half a file at `path`."""
+        from knpemidg import checkpoint
+        if self.dev is None:
+            raise _abi.KnpError("save_checkpoint: no device context yet")
+        if getattr(self, "local_mesh", None) is not None or getattr(self, "nc_owned", None) is not None or self.dev.nranks > 1:
+            raise _abi.KnpError("save_checkpoint: not supported with several ranks (checkpoint a one-GPU run)")
+        header = self._checkpoint_header()
+        header["k"] = int(getattr(self, "_k_done", 0) if k is None else k)
+        header["t"] = float(getattr(self, "_t_done", 0.0) if t is None else t)
+        table, arrays = checkpoint.split_snapshot(self.dev.state_save())
+        extra = {"emi_niter": np.asarray(self.emi_niter, dtype=np.int64),
+                 "knp_niter": np.asarray(self.knp_niter, dtype=np.int64).reshape(len(self.knp_niter), max(self.N_ions, 1)),
+                 "emi_targets": np.asarray(self.emi_targets, dtype=np.float64),
+                 "picard_iters": np.asarray(getattr(self, "picard_iters", []), dtype=np.int64),
+                 "model_time": np.asarray([float(m['ode'].time) for m in self.mem_models], dtype=np.float64)}
+        if getattr(self, "_knp_bnorm", None) is not None:
+            extra["knp_bnorm"] = np.asarray(self._knp_bnorm, dtype=np.float64)
+        for i, m in enumerate(self.mem_models):
+            extra.update(m['ode'].host_state("model%d_" % i))
+        if self.recorder is not None:
+            extra.update(self.recorder.host_state("recorder_"))
+        return checkpoint.write_checkpoint(path, header, table, arrays, extra)
+
+    def load_checkpoint(self, path, t=None, picard=None):
+        """Restore a checkpoint into this solver AFTER its setup_* calls; returns the step index k to continue with and sets `t`.
+        The header is checked first (KnpError naming the first field that differs; the solver is untouched then), the state goes to
+        the device without passing the invalidating upload path, and the EMI hierarchy is rebuilt from the restored kappa.  picard:
+        pass True when solve_for_time_step_picard is driven by hand (the mode of a checkpoint is part of what is compared)."""
+        from knpemidg import checkpoint
+        if self.dev is None:
+            raise _abi.KnpError("load_checkpoint: no device context yet")
+        if getattr(self, "local_mesh", None) is not None or getattr(self, "nc_owned", None) is not None or self.dev.nranks > 1:
+            raise _abi.KnpError("load_checkpoint: not supported with several ranks (checkpoint a one-GPU run)")
+        header, table, arrays, extra = checkpoint.read_checkpoint(path)
+        checkpoint.check_header(header, dict(self._checkpoint_header(picard), format_version=checkpoint.FORMAT_VERSION), "checkpoint %s" % path)
+        checkpoint.check_table(table, self.dev.state_describe()[0], "checkpoint %s" % path)
+        amg = self.use_amg and not getattr(self, "direct_emi", False)
+        if amg and header.get("emi_dg_chebyshev") is not None and not header.get("emi_trial_pending"):
+            explicit = getattr(getattr(self, "solver_params", None), "emi_dg_chebyshev", None)
+            chosen = bool(header["emi_dg_chebyshev"]) if explicit is None else bool(explicit)
+            self.dev.set_emi_dg_smoother(chosen)               # before the state: a change of smoother drops the spectral bound
+            self._emi_cheb_chosen = chosen
+            self._emi_trial = None                             # no trial solves in a resumed run
+        self.dev.state_load(checkpoint.join_snapshot(table, arrays))
+        self.emi_niter = [int(v) for v in extra.get("emi_niter", [])]
+        self.knp_niter = [[int(v) for v in row] for row in extra.get("knp_niter", np.zeros((0, self.N_ions)))]
+        self.emi_targets = [float(v) for v in extra.get("emi_targets", [])]
+        if "picard_iters" in extra:
+            self.picard_iters = [int(v) for v in extra["picard_iters"]]
+        self._knp_bnorm = np.asarray(extra["knp_bnorm"], dtype=np.float64).copy() if "knp_bnorm" in extra else None
+        for i, m in enumerate(self.mem_models):
+            m['ode'].time = float(extra["model_time"][i])
+            m['ode'].load_host_state("model%d_" % i, extra)
+        if self.recorder is not None:
+            self.recorder.load_host_state("recorder_", extra)
+        ref = header.get("amg_refresh") or {}
+        self._amg_refresh = {"solves": int(ref.get("solves", 0)), "ref": ref.get("ref"), "high": int(ref.get("high", 0))}
+        if ref.get("refreshes"):
+            self.amg_refreshes = int(ref["refreshes"])
+        if amg:
+            self._drop_emi_helper()
+            self._setup_amg_emi()                              # from the restored kappa
+        self._k_done, self._t_done = int(header["k"]), float(header["t"])
+        self._resume_k = self._k_done
+        if header["mode"] == "picard":
+            self._picard = True
+        if t is not None:
+            t.assign(self._t_done)
+        return self._k_done
 
     def step_membrane_models(self, k):
         """ODE step of every membrane model + PDE<->ODE copies (solver.py:1076-1118)."""
