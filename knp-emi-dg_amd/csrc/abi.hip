@@ -172,6 +172,7 @@ int knp_ctx_create(knp_ctx** out, int device, int dim, int degree, int n_ions, i
     knp_ctx* c = new knp_ctx();
     c->device = device;
     c->degree = degree;
+    c->p2_assembled = degree != 1 && env_int("KNP_P2_ASSEMBLED", 0) == 1;
     const int NV = dim + 1;
     const int ND = degree == 1 ? NV : NV * (NV + 1) / 2;      // P2: vertices, then edges (a,b), a<b, lexicographic
     c->nd = ND;
@@ -828,7 +829,7 @@ static int build_bj_table(knp_ctx* c, Fields* f) {
     static const bool enabled = env_flag("KNP_BJ_TABLE", true);
     const int64_t nc = c->m.nc, n_own = c->m.nc_owned;
     if (!enabled || c->h_cls.size() != (size_t)nc || c->h_mat.size() != (size_t)nc || c->h_fflag.size() != (size_t)nc || c->p.splitting == 2 ||
-        c->p.n_sys > 4 || n_own == 0 || (c->degree != 1 && p2_assembled()))
+        c->p.n_sys > 4 || n_own == 0 || (c->degree != 1 && p2_assembled(c)))
         return 0;
     // key: class (16 bits) | material (8) | kind of each facet (4 x 2 bits)
     std::unordered_map<uint64_t, int> ids;

@@ -55,7 +55,7 @@ static int halo_reserve_cus(const knp_ctx* c) { return (c->dist && c->halo_strea
 static ApplyInputs apply_inputs(knp_ctx* c, int which, size_t* halo_lds = nullptr) {
     ApplyInputs in;
     in.degree = c->degree; in.dim = c->m.dim;
-    if (c->degree != 1) { in.p2_assembled = p2_assembled(); return in; }
+    if (c->degree != 1) { in.p2_assembled = p2_assembled(c); return in; }
     in.cls = c->m.cls != nullptr; in.ncls = c->m.ncls; in.ncls_max = CLS_MAX_LDS;
     in.n_sys = c->p.n_sys; in.hb_long0 = c->m.hb_long0;
     in.ring = ring_usable(c, which);
@@ -79,7 +79,7 @@ static KnpArgs make_knp_args(knp_ctx* c) {
 
 int launch_emi_apply(knp_ctx* c, const double* x, const double* kappa, double* y) {
     ApplyTimerScope t(c, 0);
-    if (c->degree != 1) return p2_assembled() ? tab_apply(c, 0, x, y) : p2_emi_apply(c, x, kappa, y);
+    if (c->degree != 1) return p2_assembled(c) ? tab_apply(c, 0, x, y) : p2_emi_apply(c, x, kappa, y);
     if (c->m.c_end - c->m.c_begin <= 0) return 0;
     ApplySegment seg[2];
     const int nseg = apply_segments(plan_apply(apply_inputs(c, 0), 0), c->m.c_begin, c->m.c_end, seg);
@@ -104,7 +104,7 @@ int launch_emi_apply(knp_ctx* c, const double* x, const double* kappa, double* y
 
 int launch_knp_apply(knp_ctx* c, const double* x, const double* gphi, double* y) {
     ApplyTimerScope t(c, 1);
-    if (c->degree != 1) return p2_assembled() ? tab_apply(c, 1, x, y) : p2_knp_apply(c, x, gphi, y);     // P2: gphi holds phi (launch_dnphi)
+    if (c->degree != 1) return p2_assembled(c) ? tab_apply(c, 1, x, y) : p2_knp_apply(c, x, gphi, y);     // P2: gphi holds phi (launch_dnphi)
     if (c->m.c_end - c->m.c_begin <= 0) return 0;
     const KnpArgs ka = make_knp_args(c);
     size_t halo_lds = 0;
@@ -144,14 +144,14 @@ int launch_knp_apply(knp_ctx* c, const double* x, const double* gphi, double* y)
 }
 
 int launch_emi_blockjacobi(knp_ctx* c, const double* kappa, bjreal* binv) {
-    if (c->degree != 1) return p2_assembled() ? tab_block_inverse(c, 0, binv) : p2_block_inverse(c, 0, kappa, binv);
+    if (c->degree != 1) return p2_assembled(c) ? tab_block_inverse(c, 0, binv) : p2_block_inverse(c, 0, kappa, binv);
     const double shift = 0.0;
     DISPATCH_DIM(c, k_emi_blockjacobi, dim3((unsigned)grid_for(c->m.nc_owned)), c->m, kappa, binv, c->p.C_phi, c->p.tau_emi, shift);
     return 0;
 }
 
 int launch_knp_blockjacobi(knp_ctx* c, const double* gphi, bjreal* binv) {
-    if (c->degree != 1) return p2_assembled() ? tab_block_inverse(c, 1, binv) : p2_block_inverse(c, 1, gphi, binv);
+    if (c->degree != 1) return p2_assembled(c) ? tab_block_inverse(c, 1, binv) : p2_block_inverse(c, 1, gphi, binv);
     const dim3 g((unsigned)grid_for(c->m.nc_owned), (unsigned)c->p.n_sys);
     DISPATCH_DIM(c, k_knp_blockjacobi, g, c->m, gphi, c->D, binv, make_knp_args(c));
     return 0;
@@ -169,7 +169,7 @@ int launch_dnphi(knp_ctx* c, const double* phi, double* gphi) {
     if (c->degree != 1) {
         // P2: the matrix-free apply evaluates the drift from phi itself; the "derived" field keeps the potential the KNP
         // solve is frozen at (the assembled variant integrates it into the cell blocks instead)
-        if (p2_assembled()) return tab_assemble_knp(c, phi);
+        if (p2_assembled(c)) return tab_assemble_knp(c, phi);
         HIPCHK(c, hipMemcpyAsync(gphi, phi, sizeof(double) * c->m.nc * c->nd, hipMemcpyDeviceToDevice, c->stream));
         return 0;
     }

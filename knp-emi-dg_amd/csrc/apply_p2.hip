@@ -21,7 +21,7 @@
 // facet neighbours of a Morton-ordered block are found.  FP64 vector FMAs: on MI355X the FP64 matrix rate equals the vector
 // rate, the facet contractions are 12 x 6 / 7 x 6 (padding to 16 x 16 x 4 MFMA tiles wastes > 40 %), and the sparse P2
 // gradient structure (4 of 40 entries per point) is exploited here; see DESIGN.md section 4b for the measured comparison.
-// The numpy restatement of exactly this formulation is tests/p2_formulation.py (checked against the oracle on the CPU).
+// The numpy restatement of exactly this formulation is tests/p2_formulation.py (checked against the oracle on the CPU: tests/test_p2_formulation_host.py).
 #include "../../include/knpemi_hip.h"
 #include "cell_geom.hpp"
 #include "p2_tables.hpp"

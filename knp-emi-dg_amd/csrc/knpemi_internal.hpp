@@ -85,6 +85,7 @@ struct KernelArgsIons {            // small by-value structs for kernels
 struct knp_ctx {
     int device = 0;
     int degree = 1;
+    bool p2_assembled = false;     // KNP_P2_ASSEMBLED=1 when the context was created: fixed for the context's life (its blocks exist or not)
     int nd = 0;                    // dofs per cell
     hipStream_t stream = nullptr;
     MeshDev m;
@@ -244,7 +245,7 @@ int tab_knp_rhs(knp_ctx* c, const double* cc, const double* cprev, const double*
 int tab_step_updates(knp_ctx* c, const double* cc, double* celim, const double* phi, double* phiM, double* E, bool do_celim);
 int tab_facet_trace(knp_ctx* c, const double* nodal, int side, double* out);
 void tab_free(knp_ctx* c);
-bool p2_assembled();                 // KNP_P2_ASSEMBLED=1: round-1 path (quadrature-assembled cell blocks) instead of the matrix-free applies
+inline bool p2_assembled(const knp_ctx* c) { return c->p2_assembled; }   // KNP_P2_ASSEMBLED=1: round-1 path (quadrature-assembled cell blocks) instead of the matrix-free applies
 
 // ring-staged P1 applies on structured 3D meshes (apply_ring.hip): loader wave + LDS-DMA ring + consumer waves
 bool ring_usable(const knp_ctx* c, int which);       // which: 0 EMI, 1 KNP

@@ -679,11 +679,6 @@ static int need_tabs(knp_ctx* c, std::initializer_list<int> slots) {
         HIPCHK(c, hipGetLastError());                                                                        \
     } while (0)
 
-bool p2_assembled() {
-    static const bool on = env_int("KNP_P2_ASSEMBLED", 0) == 1;
-    return on;
-}
-
 static int ensure_blocks(knp_ctx* c) {
     const size_t per = (size_t)c->m.nc * (c->m.dim + 2) * c->nd * c->nd;
     if (!c->blk_emi) HIPCHK(c, hipMalloc((void**)&c->blk_emi, sizeof(double) * per));
@@ -703,7 +698,7 @@ int tab_kappa(knp_ctx* c, const double* cc, const double* celim, double* kappa) 
     hipLaunchKernelGGL(k_tab_kappa, dim3((unsigned)grid_for(n)), dim3(KNP_BLOCK), 0, c->stream, c->m.nc, c->nd, cc, celim,
                        (const double*)c->D, ion_z(c), c->p.F, c->p.psi, kappa);
     HIPCHK(c, hipGetLastError());
-    if (!p2_assembled()) return 0;                       // matrix-free applies read kappa directly (apply_p2.hip)
+    if (!p2_assembled(c)) return 0;                       // matrix-free applies read kappa directly (apply_p2.hip)
     if (need_tabs(c, {KNP_TAB_CELL_STIFF, KNP_TAB_FACET_EMI, KNP_TAB_FACET_MEM}) || ensure_blocks(c)) return -1;
     TAB_DISPATCH(c, k_tab_assemble_emi, rows_grid(c, 128), dim3(128), c->m, c->tab[KNP_TAB_CELL_STIFF], c->tab[KNP_TAB_FACET_EMI],
                  c->tab[KNP_TAB_FACET_MEM], (const double*)kappa, c->p.tau_emi, c->p.C_phi, c->blk_emi);

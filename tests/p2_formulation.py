@@ -103,9 +103,14 @@ def _pair_matrix(T, coef, nv):
     return W
 
 
-def _frames(T, x, j):
-    """x in the facet frame of (runtime) local facet j[c]:  x[c, FRAME_SLOTS[j[c], s]]."""
-    return np.take_along_axis(x, T["FRAME_SLOTS"][j], axis=1)
+def _frames(T, x, j, i=None):
+    """x in the facet frame of (runtime) local facet j[c], gathered as the kernels' load_frame gathers the neighbour's dofs: slot s
+    reads cell dof nibble s of FRAME_PACKED[j[c]] (the own side indexes with FRAME_SLOTS, a compile-time table in the kernels).
+    T["FRAME_PACKED_OWN"] = {i: table}, if present, replaces the table for cells whose OWN local facet is i: the kernels are
+    instantiated per own facet, so each (i, j) is a code path of its own, and a test can break exactly one."""
+    packed = np.asarray(T.get("FRAME_PACKED_OWN", {}).get(i, T["FRAME_PACKED"]), dtype=np.uint64)
+    slots = (packed[:, None] >> (4 * np.arange(x.shape[1], dtype=np.uint64))[None, :]).astype(np.int64) & 15
+    return np.take_along_axis(x, slots[j], axis=1)
 
 
 def _dn_vertices(F, gnA, gnV, D, nfe):
@@ -160,8 +165,8 @@ def emi_apply(geo, T, x, kappa, tau, C_phi):
         nb, j = geo.nb[act, i], geo.nj[act, i]
         Fo = x[act][:, T["FRAME_SLOTS"][i]]
         Ko = kappa[act][:, T["FRAME_SLOTS"][i]]
-        Fn = _frames(T, x[nb], j)
-        Kn = _frames(T, kappa[nb], j)
+        Fn = _frames(T, x[nb], j, i)
+        Kn = _frames(T, kappa[nb], j, i)
         ju = Fo[:, 1:1 + nf] - Fn[:, 1:1 + nf]
         sqG = geo.sqG[act, i]
         area = sqG * D * geo.vol[act]
@@ -223,7 +228,7 @@ def knp_apply(geo, T, x, phi, Dk, z, psi_c, tau, dt):
             continue
         nb, j = geo.nb[act, i], geo.nj[act, i]
         Fo, Po = x[act][:, T["FRAME_SLOTS"][i]], phi[act][:, T["FRAME_SLOTS"][i]]
-        Fn, Pn = _frames(T, x[nb], j), _frames(T, phi[nb], j)
+        Fn, Pn = _frames(T, x[nb], j, i), _frames(T, phi[nb], j, i)
         Dc, D2 = Dk[act], Dk[nb]
         sqG = geo.sqG[act, i]
         area = sqG * D * geo.vol[act]

@@ -14,7 +14,7 @@ from common import synthetic_state, device_for, push_state, small_3d
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "idealized_geometries"))
 
-PROBLEMS = ["2D_P1", "axon_P1", "2D_P2", "box_P2", "emix_sub"]
+PROBLEMS = ["2D_P1", "axon_P1", "2D_P2", "box_P2", "emix_sub", "tissue_P2"]
 
 
 def _problem(name):
@@ -30,6 +30,10 @@ def _problem(name):
         m, s, f = make_mesh_2D(0); pb = ko.build_idealized(m, s.array(), f.array(), p=2, membrane_tags=(1,))
     elif name == "box_P2":
         m, s, f = small_3d((6, 3, 3)); pb = ko.build_idealized(m, s.array(), f.array(), p=2, membrane_tags=(1,))
+    elif name == "tissue_P2":               # all 16 (own facet, neighbour facet) pairs, no geometry classes: the P2 block-Jacobi inverses on them
+        import p2_meshes
+        m, s, f = p2_meshes.tissue_piece(); pb = ko.build_tortuosity(m, s.array(), f.array(), p=2)
+        volt = 1.0e3
     else:                                   # sliver cells: fp32 weights and 8th powers of the density norm matter
         import emix_sub
         m, s, f = emix_sub.emix_submesh(); pb = ko.build_tortuosity(m, s.array(), f.array())
