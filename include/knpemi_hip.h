@@ -428,6 +428,9 @@ int knp_host_truncate_prolongator(int64_t n, const int32_t* Pp, const int32_t* P
 
 /* ---- timing / sync ------------------------------------------------------------------------------ */
 int knp_sync(knp_ctx* ctx);
+/* Number of blocking waits of the host on the device the library has made through this context since it was created (stream and
+ * event synchronisations, blocking copies): a measure of the host round trips of a time step that does not depend on timing */
+long long knp_host_round_trips(knp_ctx* ctx);
 int knp_timer_begin(knp_ctx* ctx);         /* records a HIP event on the context's stream */
 int knp_timer_end(knp_ctx* ctx, float* ms);/* records, synchronises, returns elapsed ms */
 /* Launches `reps` back-to-back applies (which: 0 = EMI, 1 = KNP) on X -> Y and returns the average

@@ -102,7 +102,7 @@ template <typename T> int dev_alloc_copy(knp_ctx* c, T** dst, const T* src, size
     const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
     HIPCHK(c, hipMalloc((void**)dst, bytes + KNP_DMA_PAD));
     HIPCHK(c, hipMemset((char*)*dst + bytes, 0, KNP_DMA_PAD));
-    if (src && n) HIPCHK(c, hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+    if (src && n) HIPCHK(c, host_memcpy(c, *dst, src, n * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -363,10 +363,13 @@ int knp_ctx_create(knp_ctx** out, int device, int dim, int degree, int n_ions, i
     rc |= dev_zeros(c, &c->rho, nc);
     c->partial_blocks = grid_for(nc_owned) + 8;
     rc |= dev_zeros(c, &c->partial, (size_t)c->partial_blocks * KNP_MAX_SYS * KNP_MAX_RED);
-    rc |= dev_zeros(c, &c->scal, KNP_SCAL_DOUBLES);        // Krylov scalars, reduction results, GMRES state
-    if (!rc && hipMalloc((void**)&c->status, sizeof(int) * KNP_STATUS_WORDS) != hipSuccess) rc = -2;
-    if (!rc) hipMemset(c->status, 0, sizeof(int) * KNP_STATUS_WORDS);
-    if (!rc && hipHostMalloc(&c->pinned, 4096) != hipSuccess) rc = -2;
+    // the status block: status words | Krylov scalars, reduction results, GMRES state.  One allocation, so that a look is one copy
+    char* blk = nullptr;
+    rc |= dev_zeros(c, &blk, KNP_STATUS_BYTES + sizeof(double) * KNP_SCAL_DOUBLES);
+    c->status = (int*)blk;
+    c->scal = blk ? (double*)(blk + KNP_STATUS_BYTES) : nullptr;
+    if (!rc && hipHostMalloc(&c->pinned, KNP_PINNED_BYTES) != hipSuccess) rc = -2;
+    if (!rc) memset(c->pinned, 0, KNP_PINNED_BYTES);
     if (rc) { g_err = "device allocation failed: " + c->err; delete fl; delete c; return -2; }
     if (dev_alloc_copy(c, &fl->ivol, ivol.data(), ivol.size())) { g_err = "device allocation failed: " + c->err; delete fl; delete c; return -2; }
     g_fields[c] = fl;
@@ -400,7 +403,7 @@ void knp_ctx_destroy(knp_ctx* c) {
     hipFree(c->m.hb_src); hipFree(c->m.hb_loc);
     hipFree(c->m.cls); hipFree(c->m.cls_table); hipFree(c->m.cls_ext); hipFree(c->m.coords); hipFree(c->m.h); hipFree(c->m.cells); hipFree(c->m.nbr); hipFree(c->m.fflag); hipFree(c->m.cfacet); hipFree(c->m.mf);
     hipFree(c->mat); hipFree(c->nmat4); hipFree(c->dtab); hipFree(c->halo_ctr);
-    hipFree(c->D); hipFree(c->rho); hipFree(c->fsrc); hipFree(c->mms_C); hipFree(c->extra_emi); hipFree(c->extra_knp); hipFree(c->partial); hipFree(c->scal); hipFree(c->status); hipFree(c->gm_V);
+    hipFree(c->D); hipFree(c->rho); hipFree(c->fsrc); hipFree(c->mms_C); hipFree(c->extra_emi); hipFree(c->extra_knp); hipFree(c->partial); hipFree(c->status); /* c->scal: same allocation */ hipFree(c->gm_V);
     hipFree(c->halo_send_idx); hipFree(c->halo_sendbuf);
     if (c->pinned) hipHostFree(c->pinned);
     if (c->ev0) hipEventDestroy(c->ev0);
@@ -426,7 +429,7 @@ int knp_set_params(knp_ctx* c, double C_M, double dt, double Fc, double R, doubl
         if (z[i] == 0.0) { c->err = "ion valence z must be non-zero"; return -1; }
     }
     if (!(dt > 0.0)) { c->err = "dt must be positive"; return -1; }
-    HIPCHK(c, hipMemcpy(c->D, D, sizeof(double) * p.n_ions * c->m.nc, hipMemcpyHostToDevice));
+    HIPCHK(c, host_memcpy(c, c->D, D, sizeof(double) * p.n_ions * c->m.nc, hipMemcpyHostToDevice));
     if (g_fields.count(c)) F(c)->bj_tab_state = 0;                          // D / dt may have changed: rebuild the block-Jacobi table
     {   // distinct D tuples over the cells (any dimension / degree): one of the keys of the KNP block-Jacobi table
         const int64_t nc = c->m.nc;
@@ -478,18 +481,18 @@ int knp_set_params(knp_ctx* c, double C_M, double dt, double Fc, double R, doubl
             if (!c->mat) { HIPCHK(c, hipMalloc((void**)&c->mat, (size_t)nc + KNP_DMA_PAD)); HIPCHK(c, hipMemset(c->mat, 0, (size_t)nc + KNP_DMA_PAD)); }
             if (!c->nmat4) { HIPCHK(c, hipMalloc((void**)&c->nmat4, (size_t)nc * 4 + KNP_DMA_PAD)); HIPCHK(c, hipMemset(c->nmat4, 0, (size_t)nc * 4 + KNP_DMA_PAD)); }
             if (!c->dtab) HIPCHK(c, hipMalloc((void**)&c->dtab, sizeof(double) * KNP_MAX_IONS * KNP_MAX_MAT));
-            HIPCHK(c, hipMemcpy(c->mat, mat.data(), (size_t)nc, hipMemcpyHostToDevice));
-            HIPCHK(c, hipMemcpy(c->dtab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+            HIPCHK(c, host_memcpy(c, c->mat, mat.data(), (size_t)nc, hipMemcpyHostToDevice));
+            HIPCHK(c, host_memcpy(c, c->dtab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
             c->nmat = nm;
             int rcm = launch_neighbour_materials(c);
             if (rcm) return rcm;
         }
     }
-    if (rho) HIPCHK(c, hipMemcpy(c->rho, rho, sizeof(double) * c->m.nc, hipMemcpyHostToDevice));
+    if (rho) HIPCHK(c, host_memcpy(c, c->rho, rho, sizeof(double) * c->m.nc, hipMemcpyHostToDevice));
     else HIPCHK(c, hipMemset(c->rho, 0, sizeof(double) * c->m.nc));
     if (fsrc) {
         if (!c->fsrc) HIPCHK(c, hipMalloc((void**)&c->fsrc, sizeof(double) * p.n_sys * c->m.nc));
-        HIPCHK(c, hipMemcpy(c->fsrc, fsrc, sizeof(double) * p.n_sys * c->m.nc, hipMemcpyHostToDevice));
+        HIPCHK(c, host_memcpy(c, c->fsrc, fsrc, sizeof(double) * p.n_sys * c->m.nc, hipMemcpyHostToDevice));
     } else if (c->fsrc) {
         hipFree(c->fsrc);
         c->fsrc = nullptr;
@@ -515,11 +518,11 @@ int knp_set_geometry_classes(knp_ctx* c, int ncls, const uint16_t* cls, const do
         if (cls[k] >= ncls) { c->err = "geometry class id out of range"; return -1; }
     HIPCHK(c, hipMalloc((void**)&c->m.cls, sizeof(uint16_t) * c->m.nc + KNP_DMA_PAD));
     HIPCHK(c, hipMemset(c->m.cls, 0, sizeof(uint16_t) * c->m.nc + KNP_DMA_PAD));
-    HIPCHK(c, hipMemcpy(c->m.cls, cls, sizeof(uint16_t) * c->m.nc, hipMemcpyHostToDevice));
+    HIPCHK(c, host_memcpy(c, c->m.cls, cls, sizeof(uint16_t) * c->m.nc, hipMemcpyHostToDevice));
     c->h_cls.assign(cls, cls + c->m.nc);
     if (g_fields.count(c)) F(c)->bj_tab_state = 0;
     HIPCHK(c, hipMalloc((void**)&c->m.cls_table, sizeof(double) * (size_t)ncls * KNP_CLS_STRIDE));
-    HIPCHK(c, hipMemcpy(c->m.cls_table, table, sizeof(double) * (size_t)ncls * KNP_CLS_STRIDE, hipMemcpyHostToDevice));
+    HIPCHK(c, host_memcpy(c, c->m.cls_table, table, sizeof(double) * (size_t)ncls * KNP_CLS_STRIDE, hipMemcpyHostToDevice));
     // derived per-facet coefficients of the classed P1 applies, so that no lane recomputes what only depends on the class:
     //   [8 i + 0] gr = G_ii / L_i          [8 i + 1..3] G_{a_m i} - L_{a_m} gr  (neighbour's gradient through the own basis, cell_geom.hpp)
     //   [8 i + 4] (2 / (h + h')) sqrt(G_ii) D vol   [8 i + 5] -L_i D vol (the neighbour's D vol')   [8 i + 6] sqrt(G_ii) D vol   [8 i + 7] 0
@@ -547,7 +550,7 @@ int knp_set_geometry_classes(knp_ctx* c, int ncls, const uint16_t* cls, const do
     }
     hipFree(c->m.cls_ext); c->m.cls_ext = nullptr;
     HIPCHK(c, hipMalloc((void**)&c->m.cls_ext, sizeof(double) * ext.size()));
-    HIPCHK(c, hipMemcpy(c->m.cls_ext, ext.data(), sizeof(double) * ext.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, host_memcpy(c, c->m.cls_ext, ext.data(), sizeof(double) * ext.size(), hipMemcpyHostToDevice));
     c->m.ncls = ncls;
     return 0;
 }
@@ -565,7 +568,7 @@ int knp_set_source(knp_ctx* c, const double* src) {
         return 0;
     }
     if (!c->extra_knp) HIPCHK(c, hipMalloc((void**)&c->extra_knp, sizeof(double) * n));
-    HIPCHK(c, hipMemcpy(c->extra_knp, src, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIPCHK(c, host_memcpy(c, c->extra_knp, src, sizeof(double) * n, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -576,15 +579,15 @@ int knp_set_mms(knp_ctx* c, const double* C, const double* extra_emi, const doub
     c->mms_C = c->extra_emi = c->extra_knp = nullptr;
     if (C) {
         HIPCHK(c, hipMalloc((void**)&c->mms_C, sizeof(double) * ns * c->m.nc));
-        HIPCHK(c, hipMemcpy(c->mms_C, C, sizeof(double) * ns * c->m.nc, hipMemcpyHostToDevice));
+        HIPCHK(c, host_memcpy(c, c->mms_C, C, sizeof(double) * ns * c->m.nc, hipMemcpyHostToDevice));
     }
     if (extra_emi) {
         HIPCHK(c, hipMalloc((void**)&c->extra_emi, sizeof(double) * ndof));
-        HIPCHK(c, hipMemcpy(c->extra_emi, extra_emi, sizeof(double) * ndof, hipMemcpyHostToDevice));
+        HIPCHK(c, host_memcpy(c, c->extra_emi, extra_emi, sizeof(double) * ndof, hipMemcpyHostToDevice));
     }
     if (extra_knp) {
         HIPCHK(c, hipMalloc((void**)&c->extra_knp, sizeof(double) * ns * ndof));
-        HIPCHK(c, hipMemcpy(c->extra_knp, extra_knp, sizeof(double) * ns * ndof, hipMemcpyHostToDevice));
+        HIPCHK(c, host_memcpy(c, c->extra_knp, extra_knp, sizeof(double) * ns * ndof, hipMemcpyHostToDevice));
     }
     return 0;
 }
@@ -621,7 +624,7 @@ int knp_debug_table(knp_ctx* c, int which, void* out, int64_t nbytes) {
         memcpy(out, meta, sizeof(meta));
         return 0;
     }
-    if (n) HIPCHK(c, hipMemcpy(out, p, (size_t)n, hipMemcpyDeviceToHost));
+    if (n) HIPCHK(c, host_memcpy(c, out, p, (size_t)n, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -629,7 +632,7 @@ int knp_upload(knp_ctx* c, int field, const double* src, int64_t offset, int64_t
     if (chk_field(c, field)) return -1;
     if (offset < 0 || count < 0 || offset + count > F(c)->n[field]) { c->err = "upload range out of bounds"; return -1; }
     HIPCHK(c, hipMemcpyAsync(F(c)->f[field] + offset, src, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     // a caller-supplied state may be far from the one the lagged block-Jacobi inverses were built for
     if (field == KNP_F_C || field == KNP_F_C_ELIM || field == KNP_F_PHI || field == KNP_F_KAPPA) reset_lagged(F(c));
     if (field == KNP_F_PHI) { F(c)->nh_emi = 0; c->last_peclet = -1.0f; }   // a caller-supplied state is not a point of the solution history
@@ -641,7 +644,7 @@ int knp_download(knp_ctx* c, int field, double* dst, int64_t offset, int64_t cou
     if (chk_field(c, field)) return -1;
     if (offset < 0 || count < 0 || offset + count > F(c)->n[field]) { c->err = "download range out of bounds"; return -1; }
     HIPCHK(c, hipMemcpyAsync(dst, F(c)->f[field] + offset, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     return 0;
 }
 
@@ -865,7 +868,7 @@ static int build_bj_table(knp_ctx* c, Fields* f) {
     hipLaunchKernelGGL(k_bj_gather, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, nent, (const int32_t*)drep, ns, nc, nn,
                        (const bjreal*)f->binv_knp, f->bj_tab);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     hipFree(drep);
     f->bj_entries = nent;
     f->bj_tab_state = 1;
@@ -887,7 +890,7 @@ int knp_knp_solve(knp_ctx* c, double rtol, double atol, int maxit, int min_it, i
     if (use_tab && c->last_peclet < 0.0f) {
         int bits = 0;
         HIPCHK(c, hipMemcpyAsync(&bits, c->status + KNP_PECLET_SLOT, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, host_stream_sync(c, c->stream));
         memcpy(&c->last_peclet, &bits, sizeof(float));
     }
     if (use_tab && !(c->last_peclet <= pe_limit)) use_tab = false;
@@ -1016,10 +1019,10 @@ int knp_facet_trace(knp_ctx* c, int field, int species, int side, int slot) {
 
 int knp_sync(knp_ctx* c) {
     if (!c) return -1;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (ode_check_failed(c)) return -4;
-    return 0;
+    return sync_check_ode(c);
 }
+
+long long knp_host_round_trips(knp_ctx* c) { return c ? c->host_round_trips : -1; }
 
 int knp_timer_begin(knp_ctx* c) {
     if (!c) return -1;
@@ -1030,7 +1033,7 @@ int knp_timer_begin(knp_ctx* c) {
 int knp_timer_end(knp_ctx* c, float* ms) {
     if (!c || !ms) return -1;
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev1));
+    HIPCHK(c, host_event_sync(c, c->ev1));
     HIPCHK(c, hipEventElapsedTime(ms, c->ev0, c->ev1));
     return 0;
 }
@@ -1060,7 +1063,7 @@ int knp_bench_apply(knp_ctx* c, int which, int reps, float* avg_ms) {
     c->time_applies = was_timing;
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev1));
+    HIPCHK(c, host_event_sync(c, c->ev1));
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
     *avg_ms = ms / (float)reps;
@@ -1080,7 +1083,7 @@ int knp_apply_variant(knp_ctx* c, int which) {
 
 int knp_apply_timing_read(knp_ctx* c, int which, float* avg_ms, int* count) {
     if (!c || (which != 0 && which != 1) || !avg_ms || !count) return -1;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     double sum = 0.0;
     for (size_t i = 0; i < c->tev_used[which]; ++i) {
         float ms = 0.f;
@@ -1100,7 +1103,7 @@ int knp_set_interior(knp_ctx* c, int64_t n_interior) {
     if (n_interior < 0 || n_interior > c->m.nc_owned) { c->err = "set_interior: out of range"; return -1; }
     // every owned cell below n_interior must really be interior (checked once on the host copy of the neighbour table)
     std::vector<int32_t> nbr((size_t)c->m.nc_owned * (c->m.dim + 1));
-    HIPCHK(c, hipMemcpy(nbr.data(), c->m.nbr, sizeof(int32_t) * nbr.size(), hipMemcpyDeviceToHost));
+    HIPCHK(c, host_memcpy(c, nbr.data(), c->m.nbr, sizeof(int32_t) * nbr.size(), hipMemcpyDeviceToHost));
     for (int64_t k = 0; k < n_interior * (c->m.dim + 1); ++k)
         if (nbr[k] >= c->m.nc_owned) { c->err = "set_interior: a cell below n_interior has a ghost neighbour"; return -1; }
     c->m.n_interior = n_interior;

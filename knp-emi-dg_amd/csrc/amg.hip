@@ -22,7 +22,7 @@ int s_ncol = 1;
 
 template <typename T> int up(knp_ctx* c, T** dst, const T* src, size_t n) {
     HIPCHK(c, hipMalloc((void**)dst, (n ? n : 1) * sizeof(T)));
-    if (n) HIPCHK(c, hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+    if (n) HIPCHK(c, host_memcpy(c, *dst, src, n * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
 

@@ -161,7 +161,7 @@ int launch_neighbour_materials(knp_ctx* c) {
     const int64_t n = c->m.nc * 4;
     hipLaunchKernelGGL(k_neighbour_materials, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->m.nc, c->m.nbr, c->mat, c->nmat4);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     return 0;
 }
 

@@ -931,8 +931,8 @@ extern "C" int knp_probe_facet_contraction(knp_ctx* c, int variant, int64_t ncol
     HIPCHK(c, hipMalloc((void**)&in, sizeof(double) * 26 * ncol));
     HIPCHK(c, hipMalloc((void**)&out, sizeof(double) * 9 * ncol));
     HIPCHK(c, hipMalloc((void**)&tabs, sizeof(ProbeTabs)));
-    HIPCHK(c, hipMemcpy(in, in_host, sizeof(double) * 26 * ncol, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(tabs, &h, sizeof(ProbeTabs), hipMemcpyHostToDevice));
+    HIPCHK(c, host_memcpy(c, in, in_host, sizeof(double) * 26 * ncol, hipMemcpyHostToDevice));
+    HIPCHK(c, host_memcpy(c, tabs, &h, sizeof(ProbeTabs), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemset(out, 0, sizeof(double) * 9 * ncol));
     auto launch = [&]() {
         if (variant == 0)
@@ -945,12 +945,12 @@ extern "C" int knp_probe_facet_contraction(knp_ctx* c, int variant, int64_t ncol
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     for (int i = 0; i < reps; ++i) launch();
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev1));
+    HIPCHK(c, host_event_sync(c, c->ev1));
     HIPCHK(c, hipGetLastError());
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
     *avg_ms = ms / (float)reps;
-    HIPCHK(c, hipMemcpy(out_host, out, sizeof(double) * 9 * ncol, hipMemcpyDeviceToHost));
+    HIPCHK(c, host_memcpy(c, out_host, out, sizeof(double) * 9 * ncol, hipMemcpyDeviceToHost));
     hipFree(in); hipFree(out); hipFree(tabs);
     return 0;
 }

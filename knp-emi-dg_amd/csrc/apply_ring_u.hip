@@ -502,7 +502,7 @@ template <typename Tp> int up_u(knp_ctx* c, Tp** dst, const std::vector<Tp>& src
     const size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(Tp);
     HIPCHK(c, hipMalloc((void**)dst, bytes + 4096));                   // the DMA pieces read whole blocks past the last cell
     HIPCHK(c, hipMemset((char*)*dst + bytes, 0, 4096));
-    if (!src.empty()) HIPCHK(c, hipMemcpy(*dst, src.data(), src.size() * sizeof(Tp), hipMemcpyHostToDevice));
+    if (!src.empty()) HIPCHK(c, host_memcpy(c, *dst, src.data(), src.size() * sizeof(Tp), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -514,10 +514,10 @@ int build_tables_u(knp_ctx* c, RingUState& S) {
     std::vector<int32_t> cells((size_t)nc * 4), nbr((size_t)nc * 4);
     std::vector<uint32_t> fflag((size_t)nc);
     std::vector<double> h((size_t)nc);
-    HIPCHK(c, hipMemcpy(cells.data(), m.cells, sizeof(int32_t) * cells.size(), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(nbr.data(), m.nbr, sizeof(int32_t) * nbr.size(), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(fflag.data(), m.fflag, sizeof(uint32_t) * fflag.size(), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(h.data(), m.h, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+    HIPCHK(c, host_memcpy(c, cells.data(), m.cells, sizeof(int32_t) * cells.size(), hipMemcpyDeviceToHost));
+    HIPCHK(c, host_memcpy(c, nbr.data(), m.nbr, sizeof(int32_t) * nbr.size(), hipMemcpyDeviceToHost));
+    HIPCHK(c, host_memcpy(c, fflag.data(), m.fflag, sizeof(uint32_t) * fflag.size(), hipMemcpyDeviceToHost));
+    HIPCHK(c, host_memcpy(c, h.data(), m.h, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
     std::vector<int32_t> hsrc((size_t)nblk * UH, -1), vsrc((size_t)nblk * UV, 0);
     std::vector<uint16_t> hloc((size_t)no * 4, 0);
     std::vector<uint8_t> vloc((size_t)no * 8, 0);

@@ -59,14 +59,14 @@ int allreduce_max(knp_ctx* c, double* host_value) {
         HIPCHK(c, hipMemcpyAsync(d, host_value, sizeof(double), hipMemcpyHostToDevice, c->stream));
         int rc = shm_allreduce(c, d, 1, true);
         if (rc) return rc;
-        HIPCHK(c, hipMemcpy(host_value, d, sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(c, host_memcpy(c, host_value, d, sizeof(double), hipMemcpyDeviceToHost));
         return 0;
     }
     if (!c->comm) { c->err = "allreduce without communicator"; return -6; }
     HIPCHK(c, hipMemcpyAsync(d, host_value, sizeof(double), hipMemcpyHostToDevice, c->stream));
     NCCLCHK(c, ncclAllReduce(d, d, 1, ncclDouble, ncclMax, (ncclComm_t)c->comm, c->stream));
     HIPCHK(c, hipMemcpyAsync(host_value, d, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     return 0;
 }
 
@@ -77,7 +77,7 @@ int allreduce_max_word(knp_ctx* c, int* dev_word) {
     if (c->shm) {
         int bits = 0;
         HIPCHK(c, hipMemcpyAsync(&bits, dev_word, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, host_stream_sync(c, c->stream));
         float pe;
         memcpy(&pe, &bits, sizeof(pe));
         double v = pe;
@@ -85,7 +85,7 @@ int allreduce_max_word(knp_ctx* c, int* dev_word) {
         if (rc) return rc;
         pe = (float)v;
         memcpy(&bits, &pe, sizeof(pe));
-        HIPCHK(c, hipMemcpy(dev_word, &bits, sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(c, host_memcpy(c, dev_word, &bits, sizeof(int), hipMemcpyHostToDevice));
         return 0;
     }
     if (!c->comm) { c->err = "allreduce without communicator"; return -6; }
@@ -102,7 +102,7 @@ int allreduce_sum_host(knp_ctx* c, double* host_values, int n) {
     int rc = allreduce_red(c, d, n);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(host_values, d, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     return 0;
 }
 
@@ -171,7 +171,7 @@ static int shm_allreduce(knp_ctx* c, double* dev, int count, bool is_max) {
     ShmComm* s = (ShmComm*)c->shm;
     if ((uint64_t)count > s->red_cap) { c->err = "shm communicator: reduction longer than the slot (KNP_SHM_RED_DOUBLES)"; return -6; }
     HIPCHK(c, hipMemcpyAsync(s->red(s->rank), dev, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     int rc;
     if ((rc = shm_barrier(c, s))) return rc;
     s->tmp.assign(s->red(0), s->red(0) + count);                      // rank order: every rank forms the same sum bit for bit
@@ -182,7 +182,7 @@ static int shm_allreduce(knp_ctx* c, double* dev, int count, bool is_max) {
     }
     if ((rc = shm_barrier(c, s))) return rc;                          // nobody refills a slot that is still being read
     HIPCHK(c, hipMemcpyAsync(dev, s->tmp.data(), sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     return 0;
 }
 
@@ -203,7 +203,7 @@ static int shm_halo_exchange(knp_ctx* c, double* v, int nfields, hipStream_t st)
         HIPCHK(c, hipMemcpyAsync(s->out(s->rank) + c->halo_send_off[p] * KNP_MAX_SYS * NV, seg, sizeof(double) * nfields * n,
                                  hipMemcpyDeviceToHost, st));
     }
-    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, host_stream_sync(c, st));
     int rc;
     if ((rc = shm_barrier(c, s))) return rc;
     if (s->hdr()->fail.load(std::memory_order_acquire)) { c->err = "shm communicator: outbox too small on a rank (KNP_SHM_OUT_DOUBLES)"; return -6; }
@@ -221,7 +221,7 @@ static int shm_halo_exchange(knp_ctx* c, double* v, int nfields, hipStream_t st)
             HIPCHK(c, hipMemcpyAsync(v + (int64_t)f * stride + c->halo_recv_off[p] * NV, src + (int64_t)f * want * NV, sizeof(double) * want * NV,
                                      hipMemcpyHostToDevice, st));
     }
-    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, host_stream_sync(c, st));
     return shm_barrier(c, s);                                          // outboxes may be refilled
 }
 
@@ -264,7 +264,7 @@ static int shm_interface_exchange(knp_ctx* c, int ncol) {
     if (!fits) s->hdr()->fail.store(1, std::memory_order_release);
     else if (c->if_total)
         HIPCHK(c, hipMemcpyAsync(s->out(s->rank), c->if_send, sizeof(double) * c->if_total * ncol, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     int rc;
     if ((rc = shm_barrier(c, s))) return rc;
     if (s->hdr()->fail.load(std::memory_order_acquire)) {
@@ -285,7 +285,7 @@ static int shm_interface_exchange(knp_ctx* c, int ncol) {
         HIPCHK(c, hipMemcpyAsync(c->if_recv + c->if_off[p] * ncol, s->out(peer) + off * ncol, sizeof(double) * c->if_cnt[p] * ncol,
                                  hipMemcpyHostToDevice, c->stream));
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     return shm_barrier(c, s);                                          // outboxes may be refilled
 }
 
@@ -542,7 +542,7 @@ int knp_halo_tables(knp_ctx* c, int npeers, const int32_t* peers, const int64_t*
     hipFree(c->halo_sendbuf); c->halo_sendbuf = nullptr;
     if (total) {
         HIPCHK(c, hipMalloc((void**)&c->halo_send_idx, sizeof(int32_t) * total));
-        HIPCHK(c, hipMemcpy(c->halo_send_idx, send_cells, sizeof(int32_t) * total, hipMemcpyHostToDevice));
+        HIPCHK(c, host_memcpy(c, c->halo_send_idx, send_cells, sizeof(int32_t) * total, hipMemcpyHostToDevice));
         HIPCHK(c, hipMalloc((void**)&c->halo_sendbuf, sizeof(double) * total * KNP_MAX_SYS * c->nd));
     }
     if (c->shm) {                                                            // where each peer finds its message in this rank's outbox
@@ -591,18 +591,18 @@ int knp_amg_interface(knp_ctx* c, int64_t n_local, int npeers, const int32_t* pe
     c->if_send = c->if_recv = nullptr;
     if (total) {
         HIPCHK(c, hipMalloc((void**)&c->if_idx, sizeof(int32_t) * total));
-        HIPCHK(c, hipMemcpy(c->if_idx, idx, sizeof(int32_t) * total, hipMemcpyHostToDevice));
+        HIPCHK(c, host_memcpy(c, c->if_idx, idx, sizeof(int32_t) * total, hipMemcpyHostToDevice));
         HIPCHK(c, hipMalloc((void**)&c->if_send, sizeof(double) * total * KNP_MAX_SYS));
         HIPCHK(c, hipMalloc((void**)&c->if_recv, sizeof(double) * total * KNP_MAX_SYS));
     }
     if (nuniq) {
         const int64_t nacc = aptr[nuniq];
         HIPCHK(c, hipMalloc((void**)&c->if_uvtx, sizeof(int32_t) * nuniq));
-        HIPCHK(c, hipMemcpy(c->if_uvtx, uvtx, sizeof(int32_t) * nuniq, hipMemcpyHostToDevice));
+        HIPCHK(c, host_memcpy(c, c->if_uvtx, uvtx, sizeof(int32_t) * nuniq, hipMemcpyHostToDevice));
         HIPCHK(c, hipMalloc((void**)&c->if_aptr, sizeof(int32_t) * (nuniq + 1)));
-        HIPCHK(c, hipMemcpy(c->if_aptr, aptr, sizeof(int32_t) * (nuniq + 1), hipMemcpyHostToDevice));
+        HIPCHK(c, host_memcpy(c, c->if_aptr, aptr, sizeof(int32_t) * (nuniq + 1), hipMemcpyHostToDevice));
         HIPCHK(c, hipMalloc((void**)&c->if_asrc, sizeof(int32_t) * (nacc ? nacc : 1)));
-        HIPCHK(c, hipMemcpy(c->if_asrc, asrc, sizeof(int32_t) * nacc, hipMemcpyHostToDevice));
+        HIPCHK(c, host_memcpy(c, c->if_asrc, asrc, sizeof(int32_t) * nacc, hipMemcpyHostToDevice));
     }
     if (c->shm) {                                                            // where each peer finds its message in this rank's outbox
         ShmComm* s = (ShmComm*)c->shm;

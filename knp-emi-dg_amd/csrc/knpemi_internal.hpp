@@ -22,6 +22,8 @@ typedef float bjreal;
 #define KNP_ODE_FAIL_SLOT (2 * KNP_MAX_SYS)   // word of knp_ctx::status raised by k_ode_step (read back with the solver status)
 #define KNP_PECLET_SLOT (2 * KNP_MAX_SYS + 1)     // bits of a float: max over the owned cells of psi max|z| (max - min nodal phi), set by knp_update_dnphi
 #define KNP_STATUS_WORDS (2 * KNP_MAX_SYS + 2)
+#define KNP_STATUS_BYTES (sizeof(int) * KNP_STATUS_WORDS)   // knp_ctx::scal starts this far into the status block (abi.hip)
+#define KNP_PINNED_BYTES 4096
 
 // facet kinds stored in bits 2..3 of the per-(cell, local facet) flag byte
 enum : uint32_t { FK_SIPG = 0u, FK_MEMBRANE = 1u, FK_EXTERIOR = 2u, FK_INACTIVE = 3u };
@@ -122,9 +124,12 @@ struct knp_ctx {
     // Krylov workspace
     double* partial = nullptr;     // [grid][KNP_MAX_SYS][KNP_MAX_RED]
     int64_t partial_blocks = 0;
+    // status and scal are views into ONE device allocation (the status block: status words | Krylov scalars ...), so that a look
+    // fetches the status words and the systems' scalar rows with one copy (krylov.hip: status_look)
     double* scal = nullptr;        // device scalars
-    int* status = nullptr;         // device: per system {converged flag, iterations}, then the ODE failure flag
-    void* pinned = nullptr;        // host pinned mirror for status/scalars
+    int* status = nullptr;         // device: per system {converged flag, iterations}, then the ODE failure flag and the Peclet word
+    void* pinned = nullptr;        // host pinned mirror of the head of the status block: status words | scalar rows
+    long long host_round_trips = 0;   // blocking waits of the host on the device made through this context (knp_host_round_trips)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int emi_dg_cheb = -1;          // DG-level Chebyshev step of the EMI preconditioner: -1 default (on for degree 1), 0 / 1 (knp_set_emi_dg_smoother)
     int knp_krylov = 0;            // KNP Krylov method: 0 BiCGStab (default), 1 restarted GMRES (knp_set_knp_krylov)
@@ -196,6 +201,14 @@ inline int env_int(const char* name, int dflt) {
     return v ? atoi(v) : dflt;
 }
 inline bool env_flag(const char* name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; }
+
+// every blocking wait of the host goes through one of these three, which count it (knp_ctx::host_round_trips)
+inline hipError_t host_stream_sync(knp_ctx* c, hipStream_t s) { ++c->host_round_trips; return hipStreamSynchronize(s); }
+inline hipError_t host_event_sync(knp_ctx* c, hipEvent_t e) { ++c->host_round_trips; return hipEventSynchronize(e); }
+inline hipError_t host_memcpy(knp_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    ++c->host_round_trips;
+    return hipMemcpy(dst, src, bytes, kind);
+}
 
 inline int64_t grid_for(int64_t n) { return (n + KNP_BLOCK - 1) / KNP_BLOCK; }
 
@@ -297,3 +310,5 @@ template <typename T> inline void state_push_host(StateBlk& b, const T* v, int64
 
 void rec_destroy(knp_ctx* c);       // record.hip: frees the context's time-series recorder, if any
 int ode_check_failed(knp_ctx* c);   // ode.hip: reads and clears the ODE failure flag (stream idle); sets c->err
+int status_look(knp_ctx* c);        // krylov.hip: head of the status block -> c->pinned, one copy and one stream wait
+int sync_check_ode(knp_ctx* c);     // ode.hip: waits for the stream and checks the ODE failure flag (0, -2 HIP error, -4 ODE failure)

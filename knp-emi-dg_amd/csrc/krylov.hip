@@ -456,7 +456,7 @@ int max_abs_diff(knp_ctx* c, const double* a, const double* b, int nsys, double*
     HIPCHK(c, hipGetLastError());
     std::vector<double> h(nb);
     HIPCHK(c, hipMemcpyAsync(h.data(), c->partial, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     double m = 0.0;
     for (double v : h) m = v > m ? v : m;
     if (c->dist) {
@@ -513,9 +513,16 @@ static int finalize(knp_ctx* c, int op, int nsys, int nred, const StopTest& st, 
     return 0;
 }
 
+// One look at the device: the head of the status block (status words and every system's scalar row, KNP_LOOK_BYTES) to the pinned
+// mirror with one copy and one wait -- one host round trip
+int status_look(knp_ctx* c) {
+    HIPCHK(c, hipMemcpyAsync(c->pinned, c->status, KNP_LOOK_BYTES, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
+    return 0;
+}
+
 static int poll_status(knp_ctx* c, int nsys, int* host_status) {
-    HIPCHK(c, hipMemcpyAsync(c->pinned, c->status, sizeof(int) * KNP_STATUS_WORDS, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    { const int rc = status_look(c); if (rc) return rc; }
     for (int i = 0; i < 2 * nsys; ++i) host_status[i] = ((int*)c->pinned)[i];
     { int bits = ((int*)c->pinned)[KNP_PECLET_SLOT]; float pe; memcpy(&pe, &bits, sizeof(pe)); c->last_peclet = pe; }
     if (((int*)c->pinned)[KNP_ODE_FAIL_SLOT]) {      // raised by k_ode_step earlier in this time step (`assert success`, membrane.py:113)
@@ -535,6 +542,21 @@ static int poll_status(knp_ctx* c, int nsys, int* host_status) {
 // (profiles/r05_poll_tail.txt).  KNP_POLL_TAIL=0 restores the previous rule (every 2, every 1 for 1-2 iteration solves).
 static int poll_tail() {
     return env_int("KNP_POLL_TAIL", 1);                    // read per call: tests switch it inside one process
+}
+// The look behind a solve's init kernel is dropped when the previous solve of the kind iterated (predicted >= 1): a system that is
+// converged at entry is rare (KNP has an iteration floor, the EMI target test needs an iteration), every kernel and scalar
+// recurrence of an iteration either returns on a set status word or writes scratch only, and the first regular look sees whatever
+// the dropped one would have seen -- convergence at entry, the ODE failure word -- one chunk of no-op launches later.  Without a
+// prediction, and with maxit = 0 (no look would follow), the look stays.  KNP_POLL_FIRST=1 restores it everywhere.
+static bool skip_first_look(int predicted, int maxit) {
+    return predicted >= 1 && maxit > 0 && !env_flag("KNP_POLL_FIRST", false);   // read per call, like KNP_POLL_TAIL
+}
+// The scalar rows of the first ns systems at the end of a solve.  They were final when the last look ran and nothing was enqueued
+// since, so the look's host copy holds them.  KNP_FOLD_EPILOGUE=0 (read per call): a blocking copy of their own, as before.
+static int epilogue_scalars(knp_ctx* c, int ns, double* hscal) {
+    if (env_flag("KNP_FOLD_EPILOGUE", true)) { memcpy(hscal, look_scal(c), sizeof(double) * KS_N * ns); return 0; }
+    HIPCHK(c, host_memcpy(c, hscal, krylov_scal(c), sizeof(double) * KS_N * ns, hipMemcpyDeviceToHost));
+    return 0;
 }
 static inline int next_chunk(int it, int maxit, int check_every, int predicted) {
     int chunk = check_every;
@@ -706,7 +728,7 @@ static int pcg_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, int ma
     }
     int hs[2] = {0, 0};
     int it = 0;
-    if ((rc = poll_status(c, 1, hs))) return rc;
+    if (!skip_first_look(c->last_it_emi, maxit) && (rc = poll_status(c, 1, hs))) return rc;
     while (!hs[0] && it < maxit) {
         const int chunk = next_chunk(it, maxit, check_every, c->last_it_emi);
         for (int k = 0; k < chunk; ++k) {
@@ -722,7 +744,7 @@ static int pcg_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, int ma
         if ((rc = poll_status(c, 1, hs))) return rc;
     }
     double hscal[KS_N];
-    HIPCHK(c, hipMemcpy(hscal, krylov_scal(c), sizeof(double) * KS_N, hipMemcpyDeviceToHost));
+    if ((rc = epilogue_scalars(c, 1, hscal))) return rc;
     *niter = hs[1];
     c->last_it_emi = hs[1];
     // the norm the stopping test looked at: the true residual (order-8 density norm) with a residual target, else PETSc's preconditioned norm
@@ -825,7 +847,7 @@ static int knp_precondition(knp_ctx* c, const VecDims& d, const KrylovVecs& kv, 
 // the error text when a system did not converge
 static int knp_solve_epilogue(knp_ctx* c, int ns, const int* hs, int* niter, double* res, const char* method) {
     double hscal[KNP_MAX_SYS * KS_N];
-    HIPCHK(c, hipMemcpy(hscal, krylov_scal(c), sizeof(double) * KS_N * ns, hipMemcpyDeviceToHost));
+    { const int rc = epilogue_scalars(c, ns, hscal); if (rc) return rc; }
     int bad = 0;
     for (int s = 0; s < ns; ++s) {
         const double* S = scal_row(hscal, s);
@@ -859,9 +881,9 @@ static int bicgstab_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, i
     if (first_form) hipLaunchKernelGGL((k_bi_init<NV, false>), g, b, 0, c->stream, d, kv.b, kv.w, kv.r, kv.rhat, kv.p, kv.v, c->partial);
     else hipLaunchKernelGGL((k_bi_init<NV, true>), g, b, 0, c->stream, d, kv.b, kv.w, kv.r, kv.rhat, kv.p, kv.v, c->partial);
     if ((rc = finalize(c, OP_BI_INIT, ns, 3, stop))) return rc;
-    int hs[2 * KNP_MAX_SYS];
+    int hs[2 * KNP_MAX_SYS] = {0};
     auto all_done = [&]() { for (int s = 0; s < ns; ++s) if (!hs[2 * s]) return false; return true; };
-    if ((rc = poll_status(c, ns, hs))) return rc;
+    if (!skip_first_look(c->last_it_knp, maxit) && (rc = poll_status(c, ns, hs))) return rc;
     int it = 0;
     while (!all_done() && it < maxit) {
         const int chunk = next_chunk(it, maxit, check_every, c->last_it_knp);
@@ -1041,10 +1063,10 @@ static int gmres_impl(knp_ctx* c, KrylovVecs& kv, double rtol, double atol, int 
         return finalize(c, op, ns, 3, stop);
     };
     if ((rc = residual(OP_GM_INIT))) return rc;
-    int hs[2 * KNP_MAX_SYS];
+    int hs[2 * KNP_MAX_SYS] = {0};
     auto any_running = [&]() { for (int s = 0; s < ns; ++s) if (hs[2 * s] == KS_RUNNING) return true; return false; };
     auto all_done = [&]() { for (int s = 0; s < ns; ++s) if (hs[2 * s] == KS_RUNNING || hs[2 * s] == KS_CYCLE_DONE) return false; return true; };
-    if ((rc = poll_status(c, ns, hs))) return rc;
+    if (!skip_first_look(c->last_it_knp, maxit) && (rc = poll_status(c, ns, hs))) return rc;
     int it = 0;
     while (!all_done() && it < maxit) {
         // one restart cycle
@@ -1124,7 +1146,7 @@ int load_measure(knp_ctx* c, const double* b, const float* ivol, bool d8, double
     HIPCHK(c, hipGetLastError());
     double h[KNP_MAX_SYS * KNP_MAX_RED];
     HIPCHK(c, hipMemcpyAsync(h, red, sizeof(double) * (size_t)ns * KNP_MAX_RED, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     for (int s = 0; s < ns; ++s) out[s] = h[s * KNP_MAX_RED];
     return 0;
 }

@@ -40,6 +40,12 @@ static_assert(KNP_GM_STRIDE == 1056 && KNP_GM_OFFSET == KNP_MAX_SYS * (KS_N + KN
 template <typename T> __host__ __device__ inline T* scal_row(T* scal, int s) { return scal + s * KS_N; }
 template <typename T> __host__ __device__ inline T* scal_red(T* scal) { return scal + KNP_RED_OFFSET; }
 template <typename T> __host__ __device__ inline T* scal_gm(T* scal, int s) { return scal + KNP_GM_OFFSET + s * KNP_GM_STRIDE; }
+// A look (krylov.hip: status_look) copies the head of the status block to knp_ctx::pinned: the status words, then the scalar rows
+// of every system -- what the solve loops test and what the solves' epilogues report
+#define KNP_LOOK_BYTES (KNP_STATUS_BYTES + sizeof(double) * KNP_MAX_SYS * KS_N)
+static_assert(KNP_STATUS_BYTES % sizeof(double) == 0 && KNP_LOOK_BYTES <= KNP_PINNED_BYTES, "head of the status block in the pinned mirror");
+inline const int* look_status(const knp_ctx* c) { return (const int*)c->pinned; }
+inline const double* look_scal(const knp_ctx* c, int s = 0) { return scal_row((const double*)((const char*)c->pinned + KNP_STATUS_BYTES), s); }
 inline double* krylov_scal(const knp_ctx* c, int s = 0) { return scal_row(c->scal, s); }
 inline double* krylov_red(const knp_ctx* c) { return scal_red(c->scal); }
 inline double* krylov_gm(const knp_ctx* c, int s) { return scal_gm(c->scal, s); }

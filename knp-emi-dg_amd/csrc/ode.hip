@@ -239,11 +239,27 @@ double* knp_field_ptr(knp_ctx* c, int field, int64_t* n);   // abi.hip
 // a solve (krylov.hip: poll_status), a table download or knp_sync.  Call with the stream idle.
 int ode_check_failed(knp_ctx* c) {
     int fail = 0;
-    if (hipMemcpy(&fail, c->status + KNP_ODE_FAIL_SLOT, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    if (host_memcpy(c, &fail, c->status + KNP_ODE_FAIL_SLOT, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 0;
     if (!fail) return 0;
     hipMemset(c->status + KNP_ODE_FAIL_SLOT, 0, sizeof(int));
     c->err = "ODE integrator did not reach the end time";
     return 1;
+}
+
+// Wait for the stream, then check the ODE failure flag (knp_sync, the table transfers, a state save).  The flag rides to the host
+// in front of the wait (status_look): one round trip.  KNP_SYNC_ONE_TRIP=0 (read per call): the wait, then ode_check_failed's
+// blocking read of the word -- two.
+int sync_check_ode(knp_ctx* c) {
+    if (!env_flag("KNP_SYNC_ONE_TRIP", true)) {
+        HIPCHK(c, host_stream_sync(c, c->stream));
+        return ode_check_failed(c) ? -4 : 0;
+    }
+    int rc = status_look(c);
+    if (rc) return rc;
+    if (!((const int*)c->pinned)[KNP_ODE_FAIL_SLOT]) return 0;
+    hipMemset(c->status + KNP_ODE_FAIL_SLOT, 0, sizeof(int));
+    c->err = "ODE integrator did not reach the end time";
+    return -4;
 }
 
 static OdeSet* get_set(knp_ctx* c, int handle) {
@@ -293,7 +309,7 @@ void ode_destroy_all(knp_ctx* c) {
 static void rtc_unload_all(knp_ctx* c) {
     auto it = g_rtc.find(c);
     if (it == g_rtc.end()) return;
-    hipStreamSynchronize(c->stream);                // no launch of a registered kernel may still be in flight
+    host_stream_sync(c, c->stream);                // no launch of a registered kernel may still be in flight
     for (auto& R : it->second) hipModuleUnload(R.mod);
     g_rtc.erase(it);
 }
@@ -326,9 +342,9 @@ int knp_ode_create(knp_ctx* c, int model, int64_t n, const int32_t* facets, int 
     S.fail = c->status + KNP_ODE_FAIL_SLOT;
     HIPCHK(c, hipMemset(S.h, 0, m * sizeof(double)));
     if (n) {
-        HIPCHK(c, hipMemcpy(S.facet, facets, n * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(S.states, states, n * ns * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(S.params, params, n * np * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(c, host_memcpy(c, S.facet, facets, n * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(c, host_memcpy(c, S.states, states, n * ns * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(c, host_memcpy(c, S.params, params, n * np * sizeof(double), hipMemcpyHostToDevice));
     }
     g_ode[c].push_back(S);
     return (int)g_ode[c].size() - 1;
@@ -340,9 +356,8 @@ int knp_ode_table(knp_ctx* c, int handle, int what, int upload, double* host) {
     if (!S || !host) return -1;
     double* dev = what == 0 ? S->states : S->params;
     const size_t bytes = (size_t)S->n * (what == 0 ? S->ns : S->np) * sizeof(double);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (ode_check_failed(c)) return -4;
-    if (bytes) HIPCHK(c, hipMemcpy(upload ? (void*)dev : (void*)host, upload ? (void*)host : (void*)dev, bytes,
+    { const int rc_ = sync_check_ode(c); if (rc_) return rc_; }
+    if (bytes) HIPCHK(c, host_memcpy(c, upload ? (void*)dev : (void*)host, upload ? (void*)host : (void*)dev, bytes,
                                    upload ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
     return 0;
 }
@@ -375,7 +390,7 @@ int knp_ode_set_stimulus(knp_ctx* c, int handle, int n_entries, const int32_t* c
     if (n_entries && S->n) {
         if (!mask) { c->err = "ode_set_stimulus: mask missing"; return -1; }
         HIPCHK(c, hipMemcpyAsync(S->stim_mask, mask, (size_t)S->n, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, host_stream_sync(c, c->stream));
     }
     return 0;
 }

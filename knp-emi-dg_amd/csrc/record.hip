@@ -284,7 +284,7 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_rec_map(int64_t n, const int32_t*
 
 template <typename T> int rec_upload(knp_ctx* c, T** dst, const T* src, size_t n) {
     HIPCHK(c, hipMalloc((void**)dst, std::max<size_t>(n, 1) * sizeof(T)));
-    if (n) HIPCHK(c, hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+    if (n) HIPCHK(c, host_memcpy(c, *dst, src, n * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -339,7 +339,7 @@ int rec_state_blocks(knp_ctx* c, std::vector<StateBlk>& out) {
 void rec_destroy(knp_ctx* c) {
     auto it = g_rec.find(c);
     if (it == g_rec.end()) return;
-    hipStreamSynchronize(c->stream);
+    host_stream_sync(c, c->stream);
     rec_free(it->second);
     g_rec.erase(it);
 }
@@ -457,7 +457,7 @@ int knp_rec_add_states(knp_ctx* c, int64_t n_channels, const int64_t* chan_ptr, 
         if (!(std::fabs(wsum - 1.0) <= 1e-12)) { c->err = "knp_rec_add_states: the weights of channel " + std::to_string(s) + " do not sum to 1"; return -1; }
     }
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));        // nothing may still write into the row buffer that is replaced below
+    HIPCHK(c, host_stream_sync(c, c->stream));        // nothing may still write into the row buffer that is replaced below
     int64_t* d_ptr = nullptr;
     const double** d_src = nullptr;
     double *d_w = nullptr, *d_buf = nullptr;
@@ -494,7 +494,7 @@ int knp_rec_add_map(knp_ctx* c, int64_t n, const int32_t* facets, double thresho
             return -1;
         }
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     int32_t* d_facet = nullptr;
     double *d_prev = nullptr, *d_out = nullptr, *d_t = nullptr;
     int rc = rec_upload(c, &d_facet, facets, (size_t)n);
@@ -537,9 +537,9 @@ int knp_rec_map_read(knp_ctx* c, int64_t n, double* t_act, double* t_repol, doub
     if (!R.n_map) { c->err = "knp_rec_map_read: no map (knp_rec_add_map)"; return -1; }
     if (!R.map_armed) { c->err = "knp_rec_map_read: the map is not armed (knp_rec_map_arm)"; return -1; }
     if (n != R.n_map || !t_act || !t_repol || !peak || !t_peak || !n_up) { c->err = "knp_rec_map_read: outputs must hold one entry per map facet"; return -1; }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     const size_t nn = (size_t)n;
-    HIPCHK(c, hipMemcpy(R.map_host.data(), R.map_out, (4 * sizeof(double) + sizeof(int32_t)) * nn, hipMemcpyDeviceToHost));
+    HIPCHK(c, host_memcpy(c, R.map_host.data(), R.map_out, (4 * sizeof(double) + sizeof(int32_t)) * nn, hipMemcpyDeviceToHost));
     const double* h = R.map_host.data();
     std::memcpy(t_act, h, sizeof(double) * nn);
     std::memcpy(t_repol, h + nn, sizeof(double) * nn);
@@ -609,10 +609,10 @@ int knp_rec_read(knp_ctx* c, int64_t* n_rows, double* t_out, double* rows_out) {
     Recorder& R = it->second;
     *n_rows = 0;
     if (R.rows_host > 0 && (!t_out || !rows_out)) { c->err = "knp_rec_read: null output"; return -1; }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     if (R.rows_host == 0) return 0;
     // one device-to-host copy: the rows and, behind them, their times
-    HIPCHK(c, hipMemcpy(R.host.data(), R.buf, sizeof(double) * R.host.size(), hipMemcpyDeviceToHost));
+    HIPCHK(c, host_memcpy(c, R.host.data(), R.buf, sizeof(double) * R.host.size(), hipMemcpyDeviceToHost));
     const int64_t n = R.rows_host;
     std::memcpy(rows_out, R.host.data(), sizeof(double) * (size_t)(n * R.n_ch));
     std::memcpy(t_out, R.host.data() + R.capacity * R.n_ch, sizeof(double) * (size_t)n);

@@ -149,7 +149,7 @@ int knp_state_cell_order(knp_ctx* c, const int64_t* order) {
     if (!c) return -1;
     HIPCHK(c, hipSetDevice(c->device));
     StateCtx& S = g_state[c];
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     hipFree(S.rank);
     S.rank = nullptr;
     if (!order) return 0;
@@ -160,7 +160,7 @@ int knp_state_cell_order(knp_ctx* c, const int64_t* order) {
         rank[(size_t)order[d]] = (int32_t)d;
     }
     HIPCHK(c, hipMalloc((void**)&S.rank, sizeof(int32_t) * (size_t)(nc ? nc : 1)));
-    if (nc) HIPCHK(c, hipMemcpy(S.rank, rank.data(), sizeof(int32_t) * (size_t)nc, hipMemcpyHostToDevice));
+    if (nc) HIPCHK(c, host_memcpy(c, S.rank, rank.data(), sizeof(int32_t) * (size_t)nc, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -193,8 +193,7 @@ int knp_state_save(knp_ctx* c, void* host_buf, size_t bytes) {
     HIPCHK(c, hipEventRecord(S.ev[1], c->stream));
     HIPCHK(c, hipMemcpyAsync(S.pinned, S.staging, L.dev_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipEventRecord(S.ev[2], c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (ode_check_failed(c)) return -4;
+    { const int rc_ = sync_check_ode(c); if (rc_) return rc_; }
     HIPCHK(c, hipEventElapsedTime(&S.pack_ms, S.ev[0], S.ev[1]));
     HIPCHK(c, hipEventElapsedTime(&S.copy_ms, S.ev[1], S.ev[2]));
     char* out = (char*)host_buf;
@@ -253,7 +252,7 @@ int knp_state_load(knp_ctx* c, const void* host_buf, size_t bytes) {
     pack_all(c, L, S, false);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(S.ev[2], c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, host_stream_sync(c, c->stream));
     HIPCHK(c, hipEventElapsedTime(&S.copy_ms, S.ev[0], S.ev[1]));
     HIPCHK(c, hipEventElapsedTime(&S.pack_ms, S.ev[1], S.ev[2]));
     for (size_t i = 0; i < L.blocks.size(); ++i)

@@ -790,9 +790,9 @@ extern "C" int knp_set_tabulation(knp_ctx* c, int slot, int nloc, int nq, const 
     c->tab_mem[slot] = nullptr;
     HIPCHK(c, hipMalloc((void**)&c->tab_mem[slot], sizeof(double) * (nq + nB + ndB)));
     double* base = c->tab_mem[slot];
-    HIPCHK(c, hipMemcpy(base, w, sizeof(double) * nq, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(base + nq, B, sizeof(double) * nB, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(base + nq + nB, dB, sizeof(double) * ndB, hipMemcpyHostToDevice));
+    HIPCHK(c, host_memcpy(c, base, w, sizeof(double) * nq, hipMemcpyHostToDevice));
+    HIPCHK(c, host_memcpy(c, base + nq, B, sizeof(double) * nB, hipMemcpyHostToDevice));
+    HIPCHK(c, host_memcpy(c, base + nq + nB, dB, sizeof(double) * ndB, hipMemcpyHostToDevice));
     TabRule r;
     r.nq = nq; r.w = base; r.B = base + nq; r.dB = base + nq + nB;
     c->tab[slot] = r;

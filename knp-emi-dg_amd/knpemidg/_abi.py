@@ -64,6 +64,7 @@ SIGNATURES = {
     "knp_max_abs_diff": (C.c_int, [_ctxp, C.c_int, C.c_int, _f64p]),
     "knp_facet_trace": (C.c_int, [_ctxp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "knp_sync": (C.c_int, [_ctxp]),
+    "knp_host_round_trips": (C.c_longlong, [_ctxp]),
     "knp_timer_begin": (C.c_int, [_ctxp]),
     "knp_timer_end": (C.c_int, [_ctxp, C.POINTER(C.c_float)]),
     "knp_bench_apply": (C.c_int, [_ctxp, C.c_int, C.c_int, C.POINTER(C.c_float)]),
@@ -665,6 +666,10 @@ class Device:
 
     def sync(self):
         self._chk(self.lib.knp_sync(self.ctx), "knp_sync")
+
+    def host_round_trips(self):
+        """Blocking waits of the host on the device made through this context so far."""
+        return int(self.lib.knp_host_round_trips(self.ctx))
 
     def timer_begin(self):
         self._chk(self.lib.knp_timer_begin(self.ctx), "knp_timer_begin")
