@@ -290,7 +290,27 @@ int knp_facet_trace(knp_ctx* ctx, int field, int species, int side, int slot);
  *  knp_rec_map_arm : t_act = t_repol = NaN, n_up = 0, peak = prev = PHI_M now, t_peak = t0; asynchronous.  knp_rec_sample refuses to
  *                    sample an unarmed map.
  *  knp_rec_map_read: synchronises and copies t_act, t_repol, peak, t_peak, n_up ([n] each) in one device-to-host transfer; never
- *                    part of knp_rec_read */
+ *                    part of knp_rec_read
+ *
+ * Partition mode, for the ranks of a partitioned run (one context per rank; knpemidg/recorder.py: localize_tables).  Every rank holds
+ * the tables of what it OWNS -- a probe: the rank that owns its cell; a membrane facet: the rank that owns its first cell; a cell's
+ * volume: its owner -- with the weights of the GLOBAL sets, and writes its PARTIAL row with the same kernels and launches; nothing
+ * is communicated per sample.  The row layout above is unchanged.  The three calls below replace their namesakes (mixing the two
+ * families on one recorder fails); every other call is shared.  Without a communicator they work on the rank's part alone.
+ *  knp_rec_create_part    : as knp_rec_create, except: point_cell may be -1 (a probe another rank owns: its channels are an exact
+ *                    0.0 here); a set may be empty (0.0); inv_rvol[n_regions] = 1 / GLOBAL region volume (finite, >= 0) replaces
+ *                    the volume summed over this rank's cells.  Everything else -- cells in [0, nc_owned), membrane facets, region
+ *                    ids -- is validated as there, before anything is uploaded.
+ *  knp_rec_add_states_part: as knp_rec_add_states, except: a channel may be empty and its weights (each >= 0) sum to <= 1.
+ *  knp_rec_add_map_part   : n >= 0 membrane facets of this rank (caller's ids); facet i is entry positions[i] of the n_global >= 1
+ *                    entries of the global map (distinct, in [0, n_global)).  The per-sample kernels run on the rank's n facets.
+ *  knp_rec_read    : with a communicator, first sums the waiting rows over the ranks in place on the device -- one all-reduce of
+ *                    rows x channels doubles on the context's stream and main communicator (shm transport: in pieces of the
+ *                    reduction slot, summed in rank order, the same bits on every rank); the times are not reduced.  COLLECTIVE:
+ *                    every rank calls it after the same number of samples, with the same capacity.
+ *  knp_rec_map_read: n = n_global.  k_rec_map_spread (one thread per global entry) writes the rank's five arrays, n_up as a double,
+ *                    to their global positions in a staging buffer and 0.0 elsewhere, so that an owner's NaN survives; one
+ *                    all-reduce of 5 n_global doubles, one copy.  COLLECTIVE.  Every rank receives the whole map. */
 int knp_rec_create(knp_ctx* ctx, int64_t capacity, int64_t n_points, const int32_t* point_cell, const double* point_w,
                    int64_t n_sets, const int64_t* set_ptr, const int32_t* set_facet, const double* set_w,
                    int n_regions, const uint8_t* region, const double* vol);
@@ -303,6 +323,13 @@ int knp_rec_add_map(knp_ctx* ctx, int64_t n, const int32_t* facets, double thres
 int knp_rec_map_arm(knp_ctx* ctx, double t0);
 int knp_rec_map_read(knp_ctx* ctx, int64_t n, double* t_act, double* t_repol, double* peak, double* t_peak, int32_t* n_up);
 int knp_rec_destroy(knp_ctx* ctx);
+int knp_rec_create_part(knp_ctx* ctx, int64_t capacity, int64_t n_points, const int32_t* point_cell, const double* point_w,
+                        int64_t n_sets, const int64_t* set_ptr, const int32_t* set_facet, const double* set_w,
+                        int n_regions, const uint8_t* region, const double* vol, const double* inv_rvol);
+int knp_rec_add_states_part(knp_ctx* ctx, int64_t n_channels, const int64_t* chan_ptr, const int32_t* entry_handle,
+                            const int64_t* entry_row, const int32_t* entry_col, const double* entry_w);
+int knp_rec_add_map_part(knp_ctx* ctx, int64_t n_global, int64_t n, const int32_t* facets, const int64_t* positions, double threshold,
+                         double repolarisation);
 
 /* ---- checkpoint of the step-to-step state (csrc/state.hip; DESIGN.md section 4.3 lists every member saved or rebuilt).
  * A snapshot is one host buffer: a 32-byte prologue (magic "KNPSTATE", version, block count, payload bytes), the block table

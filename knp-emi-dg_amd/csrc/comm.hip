@@ -9,6 +9,7 @@
 #include "knpemi_internal.hpp"
 #include "krylov.hpp"
 #include <rccl/rccl.h>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -183,6 +184,25 @@ static int shm_allreduce(knp_ctx* c, double* dev, int count, bool is_max) {
     if ((rc = shm_barrier(c, s))) return rc;                          // nobody refills a slot that is still being read
     HIPCHK(c, hipMemcpyAsync(dev, s->tmp.data(), sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, host_stream_sync(c, c->stream));
+    return 0;
+}
+
+// sum over the ranks of a device array of any length, in place, on the solver's stream and main communicator (the recorder's rows
+// and map at a read: record.hip).  RCCL: one call.  shm: pieces of the reduction slot's capacity, each summed in rank order, so every
+// rank holds the same bits.  Every rank passes the same n.
+int allreduce_array(knp_ctx* c, double* dev, int64_t n) {
+    if (n < 0) { c->err = "allreduce_array: negative length"; return -1; }
+    if (!c->dist || n == 0) return 0;
+    if (c->shm) {
+        const int64_t cap = (int64_t)std::min<uint64_t>(((ShmComm*)c->shm)->red_cap, uint64_t(1) << 30);
+        for (int64_t off = 0; off < n; off += cap) {
+            int rc = shm_allreduce(c, dev + off, (int)std::min<int64_t>(cap, n - off), false);
+            if (rc) return rc;
+        }
+        return 0;
+    }
+    if (!c->comm) { c->err = "allreduce without communicator"; return -6; }
+    NCCLCHK(c, ncclAllReduce(dev, dev, (size_t)n, ncclDouble, ncclSum, (ncclComm_t)c->comm, c->stream));
     return 0;
 }
 

@@ -18,6 +18,14 @@
 // of the threshold, linearly interpolated between two samples), repolarisation time (first downward crossing after it), peak and
 // its time, number of upward crossings.  One more launch per sample, a pure stream without reductions; read back on request only
 // (knp_rec_map_read).
+//
+// Partition mode (knp_rec_create_part / knp_rec_add_states_part / knp_rec_add_map_part): every rank of a partitioned run holds the
+// tables of what it OWNS -- a probe whose cell another rank owns has cell -1, a set or a state channel may be empty, the weights are the
+// global ones and so sum to <= 1 per rank, inv_rvol comes from the caller (1 / GLOBAL region volume) -- and writes its partial row with
+// the same kernels.  Nothing is communicated per sample.  knp_rec_read sums the waiting rows over the ranks in place (allreduce_array,
+// comm.hip: one all-reduce of rows x n_ch doubles on the solver's stream); knp_rec_map_read spreads the rank's map arrays to their
+// global positions in a staging buffer (k_rec_map_spread: exact zeros elsewhere, so an owner's NaN survives), sums that and copies it
+// out once.  Still no floating-point atomics: the shm transport adds in rank order, so every rank reads the same bits.
 #include "../../include/knpemi_hip.h"
 #include "knpemi_internal.hpp"
 #include <algorithm>
@@ -63,6 +71,11 @@ struct Recorder {
     double* map_out = nullptr;      // t_act, t_repol, peak, t_peak [4][n_map], then n_up int32 [n_map]: one block, one transfer
     double* t_hist = nullptr;       // [2] times of the last two samples, next to the row counter: sampling never synchronises
     std::vector<double> map_host;
+    // partition mode
+    bool part = false;
+    int64_t n_map_glob = 0;         // entries of knp_rec_map_read's outputs (= n_map outside partition mode); non-zero = there is a map
+    int32_t* map_src = nullptr;     // [n_map_glob] position in this rank's map arrays, -1 = another rank's facet
+    double* map_stage = nullptr;    // [5][n_map_glob] t_act, t_repol, peak, t_peak, n_up as doubles
 };
 
 std::map<knp_ctx*, Recorder> g_rec;
@@ -101,10 +114,13 @@ __global__ __launch_bounds__(64) void k_rec_points(int64_t n_points, int nfld, i
     if (i >= n_points * nfld || row >= capacity) return;
     const int64_t p = i / nfld;
     const int q = (int)(i - p * nfld);
-    const double* u = F.f[q] + (int64_t)cell[p] * nd;
-    const double* wp = w + p * nd;
+    const int64_t cp = cell[p];
     double s = 0.0;
-    for (int a = 0; a < nd; ++a) s += wp[a] * u[a];
+    if (cp >= 0) {                                     // -1 (partition mode): another rank's probe, an exact zero here
+        const double* u = F.f[q] + cp * nd;
+        const double* wp = w + p * nd;
+        for (int a = 0; a < nd; ++a) s += wp[a] * u[a];
+    }
     rows[row * n_ch + i] = s;
 }
 
@@ -282,6 +298,19 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_rec_map(int64_t n, const int32_t*
     prev[i] = v1;
 }
 
+// partition mode, at a read: one thread per GLOBAL map entry.  The rank's four double arrays and n_up (as a double) go to the global
+// positions of the facets it owns, an exact 0.0 everywhere else; the sum over the ranks is then every owner's value, NaN included.
+__global__ __launch_bounds__(KNP_BLOCK) void k_rec_map_spread(int64_t n_glob, int64_t n_loc, const int32_t* __restrict__ src,
+                                                              const double* __restrict__ out, const int32_t* __restrict__ n_up,
+                                                              double* __restrict__ stage) {
+    const int64_t g = (int64_t)blockIdx.x * KNP_BLOCK + threadIdx.x;
+    if (g >= n_glob) return;
+    const int64_t j = src[g];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) stage[q * n_glob + g] = j >= 0 ? out[q * n_loc + j] : 0.0;
+    stage[4 * n_glob + g] = j >= 0 ? (double)n_up[j] : 0.0;
+}
+
 template <typename T> int rec_upload(knp_ctx* c, T** dst, const T* src, size_t n) {
     HIPCHK(c, hipMalloc((void**)dst, std::max<size_t>(n, 1) * sizeof(T)));
     if (n) HIPCHK(c, host_memcpy(c, *dst, src, n * sizeof(T), hipMemcpyHostToDevice));
@@ -293,6 +322,7 @@ void rec_free(Recorder& R) {
     hipFree(R.vol); hipFree(R.inv_rvol); hipFree(R.partials); hipFree(R.buf); hipFree(R.count);
     hipFree(R.st_ptr); hipFree(R.st_src); hipFree(R.st_w);
     hipFree(R.map_facet); hipFree(R.map_prev); hipFree(R.map_out); hipFree(R.t_hist);
+    hipFree(R.map_src); hipFree(R.map_stage);
 }
 
 Recorder* rec_find(knp_ctx* c, const char* who) {
@@ -344,11 +374,10 @@ void rec_destroy(knp_ctx* c) {
     g_rec.erase(it);
 }
 
-extern "C" {
-
-int knp_rec_create(knp_ctx* c, int64_t capacity, int64_t n_points, const int32_t* point_cell, const double* point_w, int64_t n_sets,
-                   const int64_t* set_ptr, const int32_t* set_facet, const double* set_w, int n_regions, const uint8_t* region,
-                   const double* vol) {
+// knp_rec_create (part = false: validation, uploads and launches as they always were) and knp_rec_create_part
+static int rec_create(knp_ctx* c, int64_t capacity, int64_t n_points, const int32_t* point_cell, const double* point_w, int64_t n_sets,
+                      const int64_t* set_ptr, const int32_t* set_facet, const double* set_w, int n_regions, const uint8_t* region,
+                      const double* vol, const double* inv_rvol, bool part) {
     if (!c) return -1;
     const MeshDev& m = c->m;
     const int nd = c->nd, n_ions = c->p.n_ions;
@@ -356,12 +385,14 @@ int knp_rec_create(knp_ctx* c, int64_t capacity, int64_t n_points, const int32_t
     if (capacity < 1 || capacity > (int64_t(1) << 24)) { c->err = "knp_rec_create: capacity out of range"; return -1; }
     if (n_points < 0 || n_sets < 0 || n_regions < 0) { c->err = "knp_rec_create: negative count"; return -1; }
     if (n_regions > KNP_REC_MAX_REGIONS) { c->err = "knp_rec_create: at most 16 regions"; return -1; }
-    if ((n_points && (!point_cell || !point_w)) || (n_sets && (!set_ptr || !set_facet || !set_w)) || (n_regions && (!region || !vol))) {
+    const bool sets_listed = n_sets && (!part || (set_ptr && set_ptr[n_sets] > 0));      // partition mode: every set may be empty here
+    if ((n_points && (!point_cell || !point_w)) || (n_sets && !set_ptr) || (sets_listed && (!set_facet || !set_w)) ||
+        (n_regions && (!region || !vol || (part && !inv_rvol)))) {
         c->err = "knp_rec_create: null table";
         return -1;
     }
     for (int64_t p = 0; p < n_points; ++p)
-        if (point_cell[p] < 0 || point_cell[p] >= m.nc_owned) {
+        if ((point_cell[p] < 0 && !(part && point_cell[p] == -1)) || point_cell[p] >= m.nc_owned) {
             c->err = "knp_rec_create: probe " + std::to_string(p) + " sits in cell " + std::to_string(point_cell[p]) + ", not an owned cell";
             return -1;
         }
@@ -369,7 +400,10 @@ int knp_rec_create(knp_ctx* c, int64_t capacity, int64_t n_points, const int32_t
     if (n_sets) {
         if (set_ptr[0] != 0) { c->err = "knp_rec_create: set_ptr must start at 0"; return -1; }
         for (int64_t s = 0; s < n_sets; ++s)
-            if (set_ptr[s + 1] <= set_ptr[s]) { c->err = "knp_rec_create: membrane set " + std::to_string(s) + " is empty"; return -1; }
+            if (part ? set_ptr[s + 1] < set_ptr[s] : set_ptr[s + 1] <= set_ptr[s]) {
+                c->err = "knp_rec_create: membrane set " + std::to_string(s) + (part ? " has a negative length" : " is empty");
+                return -1;
+            }
         n_sf = set_ptr[n_sets];
         for (int64_t i = 0; i < n_sf; ++i)
             if (set_facet[i] < 0 || set_facet[i] >= m.nf || !c->h_mf_mask[(size_t)set_facet[i]]) {
@@ -384,15 +418,25 @@ int knp_rec_create(knp_ctx* c, int64_t capacity, int64_t n_points, const int32_t
                 c->err = "knp_rec_create: cell " + std::to_string(k) + " has region id " + std::to_string((int)region[k]) + " >= n_regions";
                 return -1;
             }
-        for (int64_t k = 0; k < m.nc_owned; ++k)
-            if (region[k] != 255) rvol[region[k]] += vol[k];
-        for (int r = 0; r < n_regions; ++r) rvol[(size_t)r] = rvol[(size_t)r] > 0.0 ? 1.0 / rvol[(size_t)r] : 0.0;
+        if (part) {                                    // 1 / GLOBAL region volume: the ranks' partial means add up
+            for (int r = 0; r < n_regions; ++r) {
+                if (!(inv_rvol[r] >= 0.0) || !std::isfinite(inv_rvol[r])) {
+                    c->err = "knp_rec_create: inv_rvol of region " + std::to_string(r) + " must be finite and not negative";
+                    return -1;
+                }
+                rvol[(size_t)r] = inv_rvol[r];
+            }
+        } else {
+            for (int64_t k = 0; k < m.nc_owned; ++k)
+                if (region[k] != 255) rvol[region[k]] += vol[k];
+            for (int r = 0; r < n_regions; ++r) rvol[(size_t)r] = rvol[(size_t)r] > 0.0 ? 1.0 / rvol[(size_t)r] : 0.0;
+        }
     }
     HIPCHK(c, hipSetDevice(c->device));
     rec_destroy(c);                                    // one recorder per context: a second create replaces the first
 
     Recorder R;
-    R.capacity = capacity; R.n_points = n_points; R.n_sets = n_sets; R.n_regions = n_regions;
+    R.capacity = capacity; R.n_points = n_points; R.n_sets = n_sets; R.n_regions = n_regions; R.part = part;
     R.n_ch = n_points * (n_ions + 1) + n_sets * (1 + 2 * n_ions) + (int64_t)n_regions * (n_ions + 1);
     R.n_base = R.n_ch;
     R.n_blk = n_regions ? (m.nc_owned + KNP_BLOCK - 1) / KNP_BLOCK : 0;
@@ -420,20 +464,25 @@ int knp_rec_create(knp_ctx* c, int64_t capacity, int64_t n_points, const int32_t
     return 0;
 }
 
-int knp_rec_add_states(knp_ctx* c, int64_t n_channels, const int64_t* chan_ptr, const int32_t* entry_handle, const int64_t* entry_row,
-                       const int32_t* entry_col, const double* entry_w) {
+static int rec_add_states(knp_ctx* c, int64_t n_channels, const int64_t* chan_ptr, const int32_t* entry_handle, const int64_t* entry_row,
+                          const int32_t* entry_col, const double* entry_w, bool part) {
     if (!c) return -1;
     Recorder* Rp = rec_find(c, "knp_rec_add_states");
     if (!Rp) return -1;
     Recorder& R = *Rp;
+    if (part != R.part) { c->err = "knp_rec_add_states: the recorder was created in the other mode (knp_rec_create / knp_rec_create_part)"; return -1; }
     // ---- validation, all of it before the first upload: no entry may address anything outside its state table ------------------
     if (R.rows_host) { c->err = "knp_rec_add_states: samples are waiting (call it right after knp_rec_create)"; return -1; }
     if (n_channels < 1 || n_channels > (int64_t(1) << 20)) { c->err = "knp_rec_add_states: channel count out of range"; return -1; }
-    if (!chan_ptr || !entry_handle || !entry_row || !entry_col || !entry_w) { c->err = "knp_rec_add_states: null table"; return -1; }
+    if (!chan_ptr) { c->err = "knp_rec_add_states: null table"; return -1; }
     if (chan_ptr[0] != 0) { c->err = "knp_rec_add_states: chan_ptr must start at 0"; return -1; }
     for (int64_t s = 0; s < n_channels; ++s)
-        if (chan_ptr[s + 1] <= chan_ptr[s]) { c->err = "knp_rec_add_states: channel " + std::to_string(s) + " is empty"; return -1; }
+        if (part ? chan_ptr[s + 1] < chan_ptr[s] : chan_ptr[s + 1] <= chan_ptr[s]) {
+            c->err = "knp_rec_add_states: channel " + std::to_string(s) + (part ? " has a negative length" : " is empty");
+            return -1;
+        }
     const int64_t ne = chan_ptr[n_channels];
+    if ((ne || !part) && (!entry_handle || !entry_row || !entry_col || !entry_w)) { c->err = "knp_rec_add_states: null table"; return -1; }
     std::vector<const double*> src((size_t)ne);
     for (int64_t s = 0; s < n_channels; ++s) {
         double wsum = 0.0;
@@ -453,8 +502,11 @@ int knp_rec_add_states(knp_ctx* c, int64_t n_channels, const int64_t* chan_ptr, 
             }
             src[(size_t)i] = tab + entry_row[i] * ns + entry_col[i];
             wsum += entry_w[i];
+            if (part && !(entry_w[i] >= 0.0)) { c->err = where + "negative weight"; return -1; }
         }
-        if (!(std::fabs(wsum - 1.0) <= 1e-12)) { c->err = "knp_rec_add_states: the weights of channel " + std::to_string(s) + " do not sum to 1"; return -1; }
+        // partition mode: the weights are those of the global channel, of which this rank holds a part
+        if (part && !(wsum <= 1.0 + 1e-12)) { c->err = "knp_rec_add_states: the weights of channel " + std::to_string(s) + " sum to more than 1"; return -1; }
+        if (!part && !(std::fabs(wsum - 1.0) <= 1e-12)) { c->err = "knp_rec_add_states: the weights of channel " + std::to_string(s) + " do not sum to 1"; return -1; }
     }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, host_stream_sync(c, c->stream));        // nothing may still write into the row buffer that is replaced below
@@ -481,37 +533,91 @@ int knp_rec_add_states(knp_ctx* c, int64_t n_channels, const int64_t* chan_ptr, 
     return 0;
 }
 
-int knp_rec_add_map(knp_ctx* c, int64_t n, const int32_t* facets, double threshold, double repolarisation) {
+// knp_rec_add_map (part = false, n_glob = n) and knp_rec_add_map_part: n facets of this rank, facet i at position pos[i] of the
+// n_glob entries that knp_rec_map_read returns
+static int rec_add_map(knp_ctx* c, int64_t n_glob, int64_t n, const int32_t* facets, const int64_t* pos, double threshold, double repolarisation,
+                       bool part) {
     if (!c) return -1;
     Recorder* Rp = rec_find(c, "knp_rec_add_map");
     if (!Rp) return -1;
     Recorder& R = *Rp;
-    if (n < 1 || !facets) { c->err = "knp_rec_add_map: empty facet selection"; return -1; }
+    if (part != R.part) { c->err = "knp_rec_add_map: the recorder was created in the other mode (knp_rec_create / knp_rec_create_part)"; return -1; }
+    if (part ? (n_glob < 1 || n < 0 || n > n_glob || (n && (!facets || !pos))) : (n < 1 || !facets)) { c->err = "knp_rec_add_map: empty facet selection"; return -1; }
+    if (n_glob > (int64_t(1) << 30)) { c->err = "knp_rec_add_map: too many facets"; return -1; }
     if (!std::isfinite(threshold) || !std::isfinite(repolarisation)) { c->err = "knp_rec_add_map: thresholds must be finite"; return -1; }
     for (int64_t i = 0; i < n; ++i)
         if (facets[i] < 0 || facets[i] >= c->m.nf || !c->h_mf_mask[(size_t)facets[i]]) {
             c->err = "knp_rec_add_map: facet " + std::to_string(facets[i]) + " is not a membrane facet";
             return -1;
         }
+    std::vector<int32_t> src;
+    if (part) {
+        src.assign((size_t)n_glob, -1);
+        for (int64_t i = 0; i < n; ++i) {
+            if (pos[i] < 0 || pos[i] >= n_glob || src[(size_t)pos[i]] >= 0) {
+                c->err = "knp_rec_add_map: position " + std::to_string(pos[i]) + " of facet " + std::to_string(facets[i]) + " is outside the map or taken twice";
+                return -1;
+            }
+            src[(size_t)pos[i]] = (int32_t)i;
+        }
+    }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, host_stream_sync(c, c->stream));
-    int32_t* d_facet = nullptr;
-    double *d_prev = nullptr, *d_out = nullptr, *d_t = nullptr;
+    const size_t na = (size_t)std::max<int64_t>(n, 1);     // a rank may own no facet of the map
+    int32_t *d_facet = nullptr, *d_src = nullptr;
+    double *d_prev = nullptr, *d_out = nullptr, *d_t = nullptr, *d_stage = nullptr;
     int rc = rec_upload(c, &d_facet, facets, (size_t)n);
-    if (!rc && (hipMalloc((void**)&d_prev, sizeof(double) * (size_t)n) != hipSuccess ||
-                hipMalloc((void**)&d_out, (4 * sizeof(double) + sizeof(int32_t)) * (size_t)n) != hipSuccess ||
+    if (!rc && (hipMalloc((void**)&d_prev, sizeof(double) * na) != hipSuccess ||
+                hipMalloc((void**)&d_out, (4 * sizeof(double) + sizeof(int32_t)) * na) != hipSuccess ||
                 hipMalloc((void**)&d_t, 2 * sizeof(double)) != hipSuccess)) rc = -2;
+    if (!rc && part) {
+        rc = rec_upload(c, &d_src, src.data(), (size_t)n_glob);
+        if (!rc && hipMalloc((void**)&d_stage, 5 * sizeof(double) * (size_t)n_glob) != hipSuccess) rc = -2;
+    }
     if (rc) {
-        hipFree(d_facet); hipFree(d_prev); hipFree(d_out); hipFree(d_t);
+        hipFree(d_facet); hipFree(d_prev); hipFree(d_out); hipFree(d_t); hipFree(d_src); hipFree(d_stage);
         if (c->err.empty()) c->err = "knp_rec_add_map: device allocation failed";
         return -2;
     }
-    hipFree(R.map_facet); hipFree(R.map_prev); hipFree(R.map_out); hipFree(R.t_hist);
-    R.map_facet = d_facet; R.map_prev = d_prev; R.map_out = d_out; R.t_hist = d_t;
-    R.n_map = n; R.map_k = 0; R.map_armed = false;
+    hipFree(R.map_facet); hipFree(R.map_prev); hipFree(R.map_out); hipFree(R.t_hist); hipFree(R.map_src); hipFree(R.map_stage);
+    R.map_facet = d_facet; R.map_prev = d_prev; R.map_out = d_out; R.t_hist = d_t; R.map_src = d_src; R.map_stage = d_stage;
+    R.n_map = n; R.n_map_glob = n_glob; R.map_k = 0; R.map_armed = false;
     R.thr = threshold; R.thr_r = repolarisation;
-    R.map_host.assign((size_t)(4 * n + (n + 1) / 2), 0.0);
+    R.map_host.assign(part ? (size_t)(5 * n_glob) : (size_t)(4 * n + (n + 1) / 2), 0.0);
     return 0;
+}
+
+extern "C" {
+
+int knp_rec_create(knp_ctx* c, int64_t capacity, int64_t n_points, const int32_t* point_cell, const double* point_w, int64_t n_sets,
+                   const int64_t* set_ptr, const int32_t* set_facet, const double* set_w, int n_regions, const uint8_t* region,
+                   const double* vol) {
+    return rec_create(c, capacity, n_points, point_cell, point_w, n_sets, set_ptr, set_facet, set_w, n_regions, region, vol, nullptr, false);
+}
+
+int knp_rec_create_part(knp_ctx* c, int64_t capacity, int64_t n_points, const int32_t* point_cell, const double* point_w, int64_t n_sets,
+                        const int64_t* set_ptr, const int32_t* set_facet, const double* set_w, int n_regions, const uint8_t* region,
+                        const double* vol, const double* inv_rvol) {
+    return rec_create(c, capacity, n_points, point_cell, point_w, n_sets, set_ptr, set_facet, set_w, n_regions, region, vol, inv_rvol, true);
+}
+
+int knp_rec_add_states(knp_ctx* c, int64_t n_channels, const int64_t* chan_ptr, const int32_t* entry_handle, const int64_t* entry_row,
+                       const int32_t* entry_col, const double* entry_w) {
+    return rec_add_states(c, n_channels, chan_ptr, entry_handle, entry_row, entry_col, entry_w, false);
+}
+
+int knp_rec_add_states_part(knp_ctx* c, int64_t n_channels, const int64_t* chan_ptr, const int32_t* entry_handle, const int64_t* entry_row,
+                            const int32_t* entry_col, const double* entry_w) {
+    return rec_add_states(c, n_channels, chan_ptr, entry_handle, entry_row, entry_col, entry_w, true);
+}
+
+int knp_rec_add_map(knp_ctx* c, int64_t n, const int32_t* facets, double threshold, double repolarisation) {
+    return rec_add_map(c, n, n, facets, nullptr, threshold, repolarisation, false);
+}
+
+int knp_rec_add_map_part(knp_ctx* c, int64_t n_global, int64_t n, const int32_t* facets, const int64_t* positions, double threshold,
+                         double repolarisation) {
+    return rec_add_map(c, n_global, n, facets, positions, threshold, repolarisation, true);
 }
 
 int knp_rec_map_arm(knp_ctx* c, double t0) {
@@ -519,10 +625,11 @@ int knp_rec_map_arm(knp_ctx* c, double t0) {
     Recorder* Rp = rec_find(c, "knp_rec_map_arm");
     if (!Rp) return -1;
     Recorder& R = *Rp;
-    if (!R.n_map) { c->err = "knp_rec_map_arm: no map (knp_rec_add_map)"; return -1; }
+    if (!R.n_map_glob) { c->err = "knp_rec_map_arm: no map (knp_rec_add_map)"; return -1; }
     if (!std::isfinite(t0)) { c->err = "knp_rec_map_arm: the time must be finite"; return -1; }
-    hipLaunchKernelGGL(k_rec_map_arm, dim3((unsigned)((R.n_map + KNP_BLOCK - 1) / KNP_BLOCK)), dim3(KNP_BLOCK), 0, c->stream, R.n_map, R.map_facet,
-                       knp_field_ptr(c, KNP_F_PHI_M, nullptr), t0, R.t_hist, R.map_prev, R.map_out, reinterpret_cast<int32_t*>(R.map_out + 4 * R.n_map));
+    if (R.n_map)                                       // (partition mode: a rank may own no facet of the map)
+        hipLaunchKernelGGL(k_rec_map_arm, dim3((unsigned)((R.n_map + KNP_BLOCK - 1) / KNP_BLOCK)), dim3(KNP_BLOCK), 0, c->stream, R.n_map, R.map_facet,
+                           knp_field_ptr(c, KNP_F_PHI_M, nullptr), t0, R.t_hist, R.map_prev, R.map_out, reinterpret_cast<int32_t*>(R.map_out + 4 * R.n_map));
     HIPCHK(c, hipGetLastError());
     R.map_k = 0;
     R.map_armed = true;
@@ -534,11 +641,28 @@ int knp_rec_map_read(knp_ctx* c, int64_t n, double* t_act, double* t_repol, doub
     Recorder* Rp = rec_find(c, "knp_rec_map_read");
     if (!Rp) return -1;
     Recorder& R = *Rp;
-    if (!R.n_map) { c->err = "knp_rec_map_read: no map (knp_rec_add_map)"; return -1; }
+    if (!R.n_map_glob) { c->err = "knp_rec_map_read: no map (knp_rec_add_map)"; return -1; }
     if (!R.map_armed) { c->err = "knp_rec_map_read: the map is not armed (knp_rec_map_arm)"; return -1; }
-    if (n != R.n_map || !t_act || !t_repol || !peak || !t_peak || !n_up) { c->err = "knp_rec_map_read: outputs must hold one entry per map facet"; return -1; }
-    HIPCHK(c, host_stream_sync(c, c->stream));
+    if (n != R.n_map_glob || !t_act || !t_repol || !peak || !t_peak || !n_up) { c->err = "knp_rec_map_read: outputs must hold one entry per map facet"; return -1; }
     const size_t nn = (size_t)n;
+    if (R.part) {
+        // every rank's arrays at their global positions, zeros elsewhere; summed over the ranks; one copy.  Collective.
+        hipLaunchKernelGGL(k_rec_map_spread, dim3((unsigned)((n + KNP_BLOCK - 1) / KNP_BLOCK)), dim3(KNP_BLOCK), 0, c->stream, n, R.n_map,
+                           R.map_src, R.map_out, reinterpret_cast<const int32_t*>(R.map_out + 4 * R.n_map), R.map_stage);
+        HIPCHK(c, hipGetLastError());
+        int rc = allreduce_array(c, R.map_stage, 5 * n);
+        if (rc) return rc;
+        HIPCHK(c, host_stream_sync(c, c->stream));
+        HIPCHK(c, host_memcpy(c, R.map_host.data(), R.map_stage, 5 * sizeof(double) * nn, hipMemcpyDeviceToHost));
+        const double* h = R.map_host.data();
+        std::memcpy(t_act, h, sizeof(double) * nn);
+        std::memcpy(t_repol, h + nn, sizeof(double) * nn);
+        std::memcpy(peak, h + 2 * nn, sizeof(double) * nn);
+        std::memcpy(t_peak, h + 3 * nn, sizeof(double) * nn);
+        for (size_t i = 0; i < nn; ++i) n_up[i] = (int32_t)h[4 * nn + i];      // small whole numbers: exact
+        return 0;
+    }
+    HIPCHK(c, host_stream_sync(c, c->stream));
     HIPCHK(c, host_memcpy(c, R.map_host.data(), R.map_out, (4 * sizeof(double) + sizeof(int32_t)) * nn, hipMemcpyDeviceToHost));
     const double* h = R.map_host.data();
     std::memcpy(t_act, h, sizeof(double) * nn);
@@ -555,7 +679,7 @@ int knp_rec_sample(knp_ctx* c, double t) {
     if (it == g_rec.end()) { c->err = "knp_rec_sample: no recorder (knp_rec_create)"; return -1; }
     Recorder& R = it->second;
     if (R.rows_host >= R.capacity) { c->err = "knp_rec_sample: buffer full (knp_rec_read empties it)"; return -5; }
-    if (R.n_map && !R.map_armed) { c->err = "knp_rec_sample: the membrane map is not armed (knp_rec_map_arm)"; return -1; }
+    if (R.n_map_glob && !R.map_armed) { c->err = "knp_rec_sample: the membrane map is not armed (knp_rec_map_arm)"; return -1; }
     const MeshDev& m = c->m;
     const int n_ions = c->p.n_ions, n_sys = c->p.n_sys, nfld = n_ions + 1, nd = c->nd;
     const int64_t ndof = m.nc * nd;
@@ -589,10 +713,11 @@ int knp_rec_sample(knp_ctx* c, double t) {
     if (R.n_sch)
         hipLaunchKernelGGL(k_rec_states, dim3((unsigned)R.n_sch), dim3(KNP_BLOCK), 0, c->stream, R.st_ptr, R.st_src, R.st_w, R.count, R.capacity, R.n_ch,
                            R.n_base, rows);
-    if (R.n_map) {
-        hipLaunchKernelGGL(k_rec_map, dim3((unsigned)((R.n_map + KNP_BLOCK - 1) / KNP_BLOCK)), dim3(KNP_BLOCK), 0, c->stream, R.n_map, R.map_facet,
-                           knp_field_ptr(c, KNP_F_PHI_M, nullptr), R.thr, R.thr_r, t, R.t_hist, (int)(R.map_k & 1), R.count, R.capacity, R.map_prev,
-                           R.map_out, reinterpret_cast<int32_t*>(R.map_out + 4 * R.n_map));
+    if (R.n_map_glob) {
+        if (R.n_map)
+            hipLaunchKernelGGL(k_rec_map, dim3((unsigned)((R.n_map + KNP_BLOCK - 1) / KNP_BLOCK)), dim3(KNP_BLOCK), 0, c->stream, R.n_map, R.map_facet,
+                               knp_field_ptr(c, KNP_F_PHI_M, nullptr), R.thr, R.thr_r, t, R.t_hist, (int)(R.map_k & 1), R.count, R.capacity, R.map_prev,
+                               R.map_out, reinterpret_cast<int32_t*>(R.map_out + 4 * R.n_map));
         ++R.map_k;
     }
     hipLaunchKernelGGL(k_rec_finish, dim3(1), dim3(KNP_REC_FINISH_BLOCK), 0, c->stream, R.n_blk, R.n_regions, nfld, R.partials, R.inv_rvol, t, R.count,
@@ -611,6 +736,13 @@ int knp_rec_read(knp_ctx* c, int64_t* n_rows, double* t_out, double* rows_out) {
     if (R.rows_host > 0 && (!t_out || !rows_out)) { c->err = "knp_rec_read: null output"; return -1; }
     HIPCHK(c, host_stream_sync(c, c->stream));
     if (R.rows_host == 0) return 0;
+    if (R.part && c->dist) {
+        // partition mode: the waiting partial rows are summed over the ranks in place; every rank has taken the same number of samples,
+        // so every rank reaches this call with the same length.  The times are the same everywhere and are not reduced.
+        int rc = allreduce_array(c, R.buf, R.rows_host * R.n_ch);
+        if (rc) return rc;
+        HIPCHK(c, host_stream_sync(c, c->stream));
+    }
     // one device-to-host copy: the rows and, behind them, their times
     HIPCHK(c, host_memcpy(c, R.host.data(), R.buf, sizeof(double) * R.host.size(), hipMemcpyDeviceToHost));
     const int64_t n = R.rows_host;

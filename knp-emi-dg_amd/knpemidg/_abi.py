@@ -124,6 +124,10 @@ SIGNATURES = {
     "knp_rec_destroy": (C.c_int, [_ctxp]),
     "knp_rec_add_states": (C.c_int, [_ctxp, C.c_int64, _i64p, _i32p, _i64p, _i32p, _f64p]),
     "knp_rec_add_map": (C.c_int, [_ctxp, C.c_int64, _i32p, C.c_double, C.c_double]),
+    "knp_rec_create_part": (C.c_int, [_ctxp, C.c_int64, C.c_int64, _i32p, _f64p, C.c_int64, _i64p, _i32p, _f64p, C.c_int, C.POINTER(C.c_uint8), _f64p,
+                                      _f64p]),
+    "knp_rec_add_states_part": (C.c_int, [_ctxp, C.c_int64, _i64p, _i32p, _i64p, _i32p, _f64p]),
+    "knp_rec_add_map_part": (C.c_int, [_ctxp, C.c_int64, C.c_int64, _i32p, _i64p, C.c_double, C.c_double]),
     "knp_rec_map_arm": (C.c_int, [_ctxp, C.c_double]),
     "knp_rec_map_read": (C.c_int, [_ctxp, C.c_int64, _f64p, _f64p, _f64p, _f64p, _i32p]),
     "knp_state_cell_order": (C.c_int, [_ctxp, _i64p]),
@@ -872,10 +876,18 @@ class Device:
         self._chk(self.lib.knp_halo_exchange(self.ctx, field), "knp_halo_exchange")
 
     # -- time-series recorder (csrc/record.hip; knpemidg/recorder.py prepares the tables) ----------
-    def rec_create(self, capacity, point_cell, point_w, set_ptr, set_facet, set_w, n_regions, region, vol):
+    def rec_create(self, capacity, point_cell, point_w, set_ptr, set_facet, set_w, n_regions, region, vol, inv_rvol=None):
         """Cell-indexed arguments in the CALLER's cell order: point_cell [n_points], region uint8 [nc] (255 = not counted), vol [nc].
-        Returns the number of channels of a row."""
-        pc = np.ascontiguousarray(self.cell_rank[np.asarray(point_cell, dtype=np.int64)], dtype=np.int32)
+        Returns the number of channels of a row.  inv_rvol [n_regions] selects partition mode (knp_rec_create_part): this rank's part
+        of the global tables -- point_cell -1 for a probe another rank owns, sets that may be empty, 1 / GLOBAL region volume."""
+        pc = np.asarray(point_cell, dtype=np.int64)
+        if inv_rvol is not None:
+            known = (pc >= 0) & (pc < self.nc)          # -1 stays -1; anything else out of range is left for the library to refuse
+            pc = pc.copy()
+            pc[known] = self.cell_rank[pc[known]]
+            pc = np.ascontiguousarray(pc, dtype=np.int32)
+        else:
+            pc = np.ascontiguousarray(self.cell_rank[pc], dtype=np.int32)
         pw = np.ascontiguousarray(np.asarray(point_w, dtype=np.float64).reshape(len(pc), self.nd))
         sp = np.ascontiguousarray(set_ptr, dtype=np.int64)
         sf = np.ascontiguousarray(set_facet, dtype=np.int32)
@@ -886,9 +898,14 @@ class Device:
             reg = np.ascontiguousarray(np.asarray(region, dtype=np.uint8)[self.cell_order])
             vl = np.ascontiguousarray(np.asarray(vol, dtype=np.float64)[self.cell_order])
             assert reg.shape == vl.shape == (self.nc,)
-        self._chk(self.lib.knp_rec_create(self.ctx, int(capacity), len(pc), _p(pc, _i32p), _p(pw, _f64p), len(sp) - 1, _p(sp, _i64p),
-                                          _p(sf, _i32p), _p(sw, _f64p), int(n_regions), _p(reg, C.POINTER(C.c_uint8)), _p(vl, _f64p)),
-                  "knp_rec_create")
+        args = (self.ctx, int(capacity), len(pc), _p(pc, _i32p), _p(pw, _f64p), len(sp) - 1, _p(sp, _i64p), _p(sf, _i32p), _p(sw, _f64p),
+                int(n_regions), _p(reg, C.POINTER(C.c_uint8)), _p(vl, _f64p))
+        if inv_rvol is not None:
+            iv = np.ascontiguousarray(inv_rvol, dtype=np.float64)
+            assert iv.shape == (int(n_regions),)
+            self._chk(self.lib.knp_rec_create_part(*args, _p(iv, _f64p)), "knp_rec_create_part")
+        else:
+            self._chk(self.lib.knp_rec_create(*args), "knp_rec_create")
         self._rec_capacity = int(capacity)
         self._rec_channels = int(self.lib.knp_rec_channels(self.ctx))
         return self._rec_channels
@@ -898,30 +915,42 @@ class Device:
         self._chk(self.lib.knp_rec_sample(self.ctx, float(t)), "knp_rec_sample")
 
     def rec_read(self):
-        """(t [n], rows [n, channels]) of the samples since the last read; synchronises and empties the device buffer."""
+        """(t [n], rows [n, channels]) of the samples since the last read; synchronises and empties the device buffer.  In partition
+        mode with a communicator the rows are first summed over the ranks: a collective call."""
         n = C.c_int64(0)
         t = np.empty(self._rec_capacity)
         rows = np.empty((self._rec_capacity, self._rec_channels))
         self._chk(self.lib.knp_rec_read(self.ctx, C.byref(n), _p(t, _f64p), _p(rows, _f64p)), "knp_rec_read")
         return t[:n.value].copy(), rows[:n.value].copy()
 
-    def rec_add_states(self, chan_ptr, entry_handle, entry_row, entry_col, entry_w):
+    def rec_add_states(self, chan_ptr, entry_handle, entry_row, entry_col, entry_w, part=False):
         """State channels behind the region block (knp_rec_add_states): channel s = sum of entry_w * state table value over its
-        entries.  Returns the new number of channels of a row."""
+        entries.  Returns the new number of channels of a row.  part: knp_rec_add_states_part -- this rank's entries of the global
+        channels, which may be none, with the global weights."""
         cp = np.ascontiguousarray(chan_ptr, dtype=np.int64)
         eh = np.ascontiguousarray(entry_handle, dtype=np.int32)
         er = np.ascontiguousarray(entry_row, dtype=np.int64)
         ec = np.ascontiguousarray(entry_col, dtype=np.int32)
         ew = np.ascontiguousarray(entry_w, dtype=np.float64)
         assert cp.ndim == 1 and len(cp) >= 1 and eh.shape == er.shape == ec.shape == ew.shape == (int(cp[-1]),)
-        self._chk(self.lib.knp_rec_add_states(self.ctx, len(cp) - 1, _p(cp, _i64p), _p(eh, _i32p), _p(er, _i64p), _p(ec, _i32p),
-                                              _p(ew, _f64p)), "knp_rec_add_states")
+        fn = self.lib.knp_rec_add_states_part if part else self.lib.knp_rec_add_states
+        self._chk(fn(self.ctx, len(cp) - 1, _p(cp, _i64p), _p(eh, _i32p), _p(er, _i64p), _p(ec, _i32p), _p(ew, _f64p)),
+                  "knp_rec_add_states_part" if part else "knp_rec_add_states")
         self._rec_channels = int(self.lib.knp_rec_channels(self.ctx))
         return self._rec_channels
 
-    def rec_add_map(self, facets, threshold, repolarisation):
-        """Per-facet activation map of the given membrane facets (knp_rec_add_map); arm it before the first sample."""
+    def rec_add_map(self, facets, threshold, repolarisation, positions=None, n_global=None):
+        """Per-facet activation map of the given membrane facets (knp_rec_add_map); arm it before the first sample.  positions /
+        n_global: knp_rec_add_map_part -- `facets` are this rank's (possibly none), facet i is entry positions[i] of the n_global
+        entries that rec_map_read returns on every rank."""
         f = np.ascontiguousarray(facets, dtype=np.int32)
+        if positions is not None:
+            pos = np.ascontiguousarray(positions, dtype=np.int64)
+            assert pos.shape == f.shape
+            self._chk(self.lib.knp_rec_add_map_part(self.ctx, int(n_global), len(f), _p(f, _i32p), _p(pos, _i64p), float(threshold),
+                                                    float(repolarisation)), "knp_rec_add_map_part")
+            self._rec_map_n = int(n_global)
+            return
         self._chk(self.lib.knp_rec_add_map(self.ctx, len(f), _p(f, _i32p), float(threshold), float(repolarisation)), "knp_rec_add_map")
         self._rec_map_n = len(f)
 
@@ -929,7 +958,8 @@ class Device:
         self._chk(self.lib.knp_rec_map_arm(self.ctx, float(t0)), "knp_rec_map_arm")
 
     def rec_map_read(self):
-        """(activation time, repolarisation time, peak, peak time, upward crossings) per map facet; synchronises."""
+        """(activation time, repolarisation time, peak, peak time, upward crossings) per map facet; synchronises.  Partition mode:
+        the merged global map on every rank, a collective call."""
         n = getattr(self, "_rec_map_n", 0)
         out = [np.empty(n) for _ in range(4)] + [np.empty(n, dtype=np.int32)]
         self._chk(self.lib.knp_rec_map_read(self.ctx, n, *[_p(a, _f64p) for a in out[:4]], _p(out[4], _i32p)), "knp_rec_map_read")

@@ -11,6 +11,11 @@ Two optional additions serve the reference's other figure scripts (examples/rat-
 `membrane_states` appends the area-weighted means of ODE state columns (the gating variables n, m, h) over the membrane sets, read
 straight from the state tables on the device, and `membrane_map` keeps a per-facet activation map (activation and repolarisation
 time, peak, number of activations) from which `Recorder.conduction_velocity` follows.
+
+Partitioned runs (knpemidg/partition.py): the recorder is built from the GLOBAL mesh on every rank and `localize_tables` cuts out what
+the rank owns -- a probe belongs to the rank that owns its cell, a membrane facet to the rank that owns its first cell, a cell's
+volume to its owner -- with the global weights, so that the ranks' partial rows add up to the one-GPU row.  Nothing is communicated
+per sample; the partial rows are summed over the ranks when the device buffer is read, which makes every read a collective call.
 """
 import numpy as np
 
@@ -177,6 +182,113 @@ def first_upward_crossing(t, v, threshold):
     return float(t[k] + (threshold - v[k]) / (v[k + 1] - v[k]) * (t[k + 1] - t[k]))
 
 
+def _tag_model(models):
+    return {int(m.tag): k for k, m in enumerate(models)}
+
+
+def state_weights_global(mesh, facet_tags, set_facets, models, names):
+    """Per (set, state name), in channel order: (positions in the set of the facets whose model has the state, their area weights
+    renormalised over exactly those facets).  Decided by the facets' surface tags (models[k].tag) on the global tables, so every rank
+    of a partitioned run gets the same answer; ValueError naming the set and the state when no facet of the set has it."""
+    by_tag = _tag_model(models)
+    has = [{q: model_has_state(m.ode, q) for q in names} for m in models]
+    ft = np.asarray(facet_tags)
+    out = []
+    for s, facets in enumerate(set_facets):
+        facets = np.asarray(facets, dtype=np.int64)
+        areas = facet_areas(mesh, facets)
+        k_of = np.asarray([by_tag.get(int(t), -1) for t in ft[facets]], dtype=np.int64)
+        for q in names:
+            keep = np.nonzero([k >= 0 and has[k][q] for k in k_of])[0]
+            if not len(keep):
+                raise ValueError("membrane set %d: no facet of the set belongs to a membrane model with a state '%s'" % (s, q))
+            out.append((keep, areas[keep] / areas[keep].sum()))
+    return out
+
+
+class LocalTables:
+    """One rank's part of a global recorder's tables (`localize_tables`)."""
+
+
+def localize_tables(rec, loc):
+    """The tables of the global recorder `rec` (built on the global mesh, membrane sets resolved) as rank `loc.rank` records them;
+    `loc` is the rank's partition.LocalMesh.  Pure host work from the global mesh and the partition, the same on every rank.
+      point_owner [n_points]   owning rank of every probe = owner of its containing cell
+      point_cells [n_points]   local cell id, -1 for a probe another rank owns
+      facet_owner(f)           owning rank of global membrane facets = owner of facet_cells[f, 0] (amg.Dist0Space.facet_owner)
+      set_facets / set_weights / set_index   per set the owned facets (local ids, set order), their GLOBAL weights and their positions
+                               in the global set; a set may be empty here
+      region, vol [nc_local]   region id and volume of the local cells (the device counts the owned ones); inv_rvol [n_regions] =
+                               1 / global region volume; region_volume_owned [n_regions]
+      map_facets / map_pos     owned map facets (local ids) and their positions in rec.map_facets
+      facet_local(f)           local ids of global facets, -1 = not on this rank"""
+    mesh, part, rank = rec.mesh, loc.part, int(loc.rank)
+    if mesh is not part.mesh and mesh.num_cells() != part.mesh.num_cells():
+        raise ValueError("localize_tables: the recorder was not built on the partition's global mesh")
+    if rec.set_facets is None:
+        raise ValueError("localize_tables: the membrane sets are not resolved yet (membrane_tags)")
+    T = LocalTables()
+    T.rank, T.world = rank, int(part.world)
+    owner = np.asarray(part.owner)
+    first_cell = np.asarray(mesh.facet_cells)[:, 0]
+    f_g2l = np.full(mesh.num_facets(), -1, dtype=np.int64)
+    f_g2l[loc.facets_global] = np.arange(len(loc.facets_global))
+    T.facet_owner = lambda f: owner[first_cell[np.asarray(f, dtype=np.int64)]]
+    T.facet_local = lambda f: f_g2l[np.asarray(f, dtype=np.int64)]
+    # probes
+    T.point_owner = owner[rec.point_cells].astype(np.int64) if rec.n_points else np.zeros(0, dtype=np.int64)
+    T.point_cells = np.where(T.point_owner == rank, loc.g2l[rec.point_cells], -1).astype(np.int64) if rec.n_points \
+        else np.zeros(0, dtype=np.int64)
+    assert ((T.point_cells < loc.nc_owned)).all()
+    # membrane sets
+    T.set_facets, T.set_weights, T.set_index = [], [], []
+    for f, w in zip(rec.set_facets, rec.set_weights):
+        mine = np.nonzero(T.facet_owner(f) == rank)[0]
+        lf = f_g2l[f[mine]]
+        assert (lf >= 0).all()
+        T.set_index.append(mine)
+        T.set_facets.append(lf)
+        T.set_weights.append(np.asarray(w, dtype=np.float64)[mine])
+    # regions
+    T.region = np.ascontiguousarray(rec.region[loc.cells_global], dtype=np.uint8)
+    T.vol = np.ascontiguousarray(rec.vol[loc.cells_global], dtype=np.float64)
+    rvol = np.asarray([rec.vol[rec.region == r].sum() for r in range(rec.n_regions)], dtype=np.float64)
+    T.inv_rvol = np.where(rvol > 0.0, 1.0 / np.where(rvol > 0.0, rvol, 1.0), 0.0)
+    reg_own, vol_own = T.region[:loc.nc_owned], T.vol[:loc.nc_owned]
+    T.region_volume_owned = np.asarray([vol_own[reg_own == r].sum() for r in range(rec.n_regions)], dtype=np.float64)
+    # map
+    if rec.map_facets is not None:
+        T.map_pos = np.nonzero(T.facet_owner(rec.map_facets) == rank)[0].astype(np.int64)
+        T.map_facets = f_g2l[rec.map_facets[T.map_pos]]
+        assert (T.map_facets >= 0).all()
+    else:
+        T.map_pos = T.map_facets = None
+    return T
+
+
+def state_entries_local(rec, T, models):
+    """This rank's entry lists of the state channels (knp_rec_add_states_part): of every global channel (`state_weights_global`) the
+    facets the rank owns, with the global weights.  models: the rank's membrane models (local facet ids, `tag`)."""
+    by_tag = _tag_model(models)
+    chans = state_weights_global(rec.mesh, rec.facet_tags, rec.set_facets, models, rec.state_names)
+    ptr, eh, er, ec, ew = [0], [], [], [], []
+    n_names = len(rec.state_names)
+    for ch, (keep, w) in enumerate(chans):
+        f = rec.set_facets[ch // n_names][keep]
+        q = rec.state_names[ch % n_names]
+        for i in np.nonzero(T.facet_owner(f) == T.rank)[0]:
+            m = models[by_tag[int(rec.facet_tags[f[i]])]]
+            lf = int(T.facet_local(f[i]))
+            mf = np.asarray(m.facets, dtype=np.int64)
+            r = int(np.searchsorted(mf, lf))
+            if r >= len(mf) or mf[r] != lf:
+                raise KnpError("membrane_states: facet %d has no row in the state table of membrane tag %s on rank %d" % (int(f[i]), m.tag, T.rank))
+            eh.append(int(m.handle)); er.append(r); ec.append(int(m.ode.state_indices(q))); ew.append(float(w[i]))
+        ptr.append(len(eh))
+    return (np.asarray(ptr, dtype=np.int64), np.asarray(eh, dtype=np.int32), np.asarray(er, dtype=np.int64),
+            np.asarray(ec, dtype=np.int32), np.asarray(ew, dtype=np.float64))
+
+
 MAP_FIELDS = ("activation_time", "repolarisation_time", "peak", "peak_time", "n_activations")
 
 
@@ -200,11 +312,17 @@ class Recorder:
                   follow with `attach_states(models)` once the membrane models exist
     membrane_map  dict(threshold=0.0, repolarisation=None, tags=None): per-facet activation map, in the units of phi_M;
                   repolarisation None = the threshold, tags None = every membrane facet, else the facets with those surface tags
+    local_mesh    partitioned run: this rank's partition.LocalMesh; mesh, tags, points, facet ids and regions are then the GLOBAL
+                  ones, every rank makes the same call with the same capacity, and the results are the global ones on every rank.
+                  Reading is then COLLECTIVE -- `flush`, `rows` and every property derived from it (`t`, `points`, `membrane`,
+                  `regions`), `membrane_map`, `conduction_velocity` and `save` must be called by all ranks at the same point
     """
 
     def __init__(self, mesh, cell_tags, facet_tags, degree, ion_names, points=None, membrane_sets=None, regions=True, capacity=256,
-                 point_tags=None, membrane_tags=None, membrane_states=None, membrane_map=None):
+                 point_tags=None, membrane_tags=None, membrane_states=None, membrane_map=None, local_mesh=None):
         self.mesh = mesh
+        self.local_mesh = local_mesh
+        self.local = None               # LocalTables of a partitioned run, built by attach
         self.cell_tags = np.asarray(cell_tags)
         self.facet_tags = np.asarray(facet_tags)
         self.degree = int(degree)
@@ -326,10 +444,22 @@ class Recorder:
         state channels; they may follow later through `attach_states`."""
         if self.set_facets is None:
             self.resolve_sets(membrane_tags if membrane_tags is not None else [])
-        ptr = np.concatenate([[0], np.cumsum([len(f) for f in self.set_facets])]).astype(np.int64)
-        sf = np.concatenate(self.set_facets) if self.set_facets else np.zeros(0, dtype=np.int64)
-        sw = np.concatenate(self.set_weights) if self.set_facets else np.zeros(0)
-        self.n_channels = dev.rec_create(self.capacity, self.point_cells, self.point_w, ptr, sf, sw, self.n_regions, self.region, self.vol)
+        if self.local_mesh is not None:
+            # every host-side decision that can fail is taken on the global tables first, identically on every rank, so that no rank
+            # leaves its peers waiting in a collective
+            if self.state_names and models is not None:
+                state_weights_global(self.mesh, self.facet_tags, self.set_facets, models, self.state_names)
+            T = self.local = localize_tables(self, self.local_mesh)
+            ptr = np.concatenate([[0], np.cumsum([len(f) for f in T.set_facets])]).astype(np.int64)
+            sf = np.concatenate(T.set_facets) if T.set_facets else np.zeros(0, dtype=np.int64)
+            sw = np.concatenate(T.set_weights) if T.set_facets else np.zeros(0)
+            self.n_channels = dev.rec_create(self.capacity, T.point_cells, self.point_w, ptr, sf, sw, self.n_regions, T.region, T.vol,
+                                             inv_rvol=T.inv_rvol)
+        else:
+            ptr = np.concatenate([[0], np.cumsum([len(f) for f in self.set_facets])]).astype(np.int64)
+            sf = np.concatenate(self.set_facets) if self.set_facets else np.zeros(0, dtype=np.int64)
+            sw = np.concatenate(self.set_weights) if self.set_facets else np.zeros(0)
+            self.n_channels = dev.rec_create(self.capacity, self.point_cells, self.point_w, ptr, sf, sw, self.n_regions, self.region, self.vol)
         n_ions = len(self.ion_names)
         self.n_base = self.n_points * (n_ions + 1) + self.n_sets * (1 + 2 * n_ions) + self.n_regions * (n_ions + 1)
         assert self.n_channels == self.n_base
@@ -337,7 +467,11 @@ class Recorder:
         self._waiting = 0
         self._states_on_device = False
         if self._map_spec is not None:
-            dev.rec_add_map(self.map_facets, self._map_spec["threshold"], self._map_spec["repolarisation"])
+            if self.local is not None:
+                dev.rec_add_map(self.local.map_facets, self._map_spec["threshold"], self._map_spec["repolarisation"],
+                                positions=self.local.map_pos, n_global=len(self.map_facets))
+            else:
+                dev.rec_add_map(self.map_facets, self._map_spec["threshold"], self._map_spec["repolarisation"])
             self._armed = False
         if self.state_names and models is not None:
             self.attach_states(models)
@@ -353,9 +487,13 @@ class Recorder:
             if getattr(m, "handle", None) is None:
                 raise KnpError("membrane_states: the state tables of membrane tag %s are not on the device (KNP_HOST_ODE=1, or a model "
                                "without a device implementation)" % getattr(m, "tag", "?"))
-        areas = [facet_areas(self.mesh, f) for f in self.set_facets]
-        self.state_entry_lists = state_entries(self.set_facets, areas, models, self.state_names)
-        self.n_channels = self.dev.rec_add_states(*self.state_entry_lists)
+        if self.local is not None:
+            self.state_entry_lists = state_entries_local(self, self.local, models)
+            self.n_channels = self.dev.rec_add_states(*self.state_entry_lists, part=True)
+        else:
+            areas = [facet_areas(self.mesh, f) for f in self.set_facets]
+            self.state_entry_lists = state_entries(self.set_facets, areas, models, self.state_names)
+            self.n_channels = self.dev.rec_add_states(*self.state_entry_lists)
         assert self.n_channels == self.n_base + self.n_sets * len(self.state_names)
         self._states_on_device = True
 
@@ -384,6 +522,7 @@ class Recorder:
         self._waiting += 1
 
     def flush(self):
+        """Read the waiting rows back.  Partitioned run: the rows are summed over the ranks on the way -- collective."""
         if self.dev is None or not self._waiting:
             return
         t, rows = self.dev.rec_read()
@@ -414,7 +553,8 @@ class Recorder:
     # -- results ------------------------------------------------------------------
     @property
     def rows(self):
-        """All samples so far, [n_steps, n_channels] in the row layout of include/knpemi_hip.h."""
+        """All samples so far, [n_steps, n_channels] in the row layout of include/knpemi_hip.h.  Partitioned run: the global rows,
+        the same bits on every rank; collective while rows wait on the device (see `flush`)."""
         self.flush()
         if not self._rows:
             return np.zeros((0, getattr(self, "n_channels", 0)))
@@ -449,7 +589,8 @@ class Recorder:
     @property
     def membrane_map(self):
         """The per-facet map as it stands: facets (caller's ids), activation_time, repolarisation_time (NaN = not yet), peak,
-        peak_time, n_activations.  Synchronises and reads the device arrays in one transfer."""
+        peak_time, n_activations.  Synchronises and reads the device arrays in one transfer.  Partitioned run: the merged global
+        map with global facet ids on every rank; collective."""
         if self._map_spec is None:
             raise KnpError("no membrane map was asked for (record(membrane_map=...))")
         if self.dev is None or not self._armed:
@@ -466,7 +607,8 @@ class Recorder:
         method "map": t = area-weighted mean of the map's per-facet activation times over the set (every facet of both sets must be
         in the map).  method "set_mean": t = first upward crossing of `threshold` (default: the map's, else 0) by the recorded
         set-mean phi_M, linearly interpolated between steps -- the reference's definition at sub-step resolution.  distance defaults
-        to the distance between the area-weighted centroids.  NaN when either set has not (entirely) activated."""
+        to the distance between the area-weighted centroids.  NaN when either set has not (entirely) activated.  Partitioned run:
+        collective (it reads the map or the rows)."""
         if distance is None:
             distance = float(np.linalg.norm(self.set_centroid(set_b) - self.set_centroid(set_a)))
         if method == "map":
@@ -498,9 +640,17 @@ class Recorder:
     def save(self, path):
         """/timeseries/t, /timeseries/points/<name>, /timeseries/membrane/<name>, /timeseries/regions/<name> ([n_steps, n_items]) plus
         the probe coordinates and cells, the facets and weights of every membrane set and the region tags; with a map,
-        /membrane_map/{facets, activation_time, repolarisation_time, peak, peak_time, n_activations, threshold, repolarisation}."""
+        /membrane_map/{facets, activation_time, repolarisation_time, peak, peak_time, n_activations, threshold, repolarisation}.
+        Partitioned run: collective; every rank takes part in the reads, rank 0 alone writes the file (the others return None)."""
         import os
         from knpemidg.h5lite import H5Writer
+        if self.local_mesh is not None:
+            self.flush()
+            m_all = self.membrane_map if self._map_spec is not None and self._armed else None
+            if int(self.local_mesh.rank) != 0:
+                return None
+        else:
+            m_all = None
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         with H5Writer(path) as w:
             w.write("/timeseries/t", self.t)
@@ -518,7 +668,7 @@ class Recorder:
             if self.n_regions:
                 w.write("/regions/tags", np.asarray(self.region_tags, dtype=np.int64))
             if self._map_spec is not None and self._armed:
-                m = self.membrane_map
+                m = m_all if m_all is not None else self.membrane_map
                 w.write("/membrane_map/facets", m["facets"].astype(np.int64))
                 for name in MAP_FIELDS[:4]:
                     w.write("/membrane_map/" + name, m[name])

@@ -284,19 +284,30 @@ class Solver:
                          given surface tags) the interpolated activation and repolarisation times, the peak and its time and the
                          number of activations (Recorder.membrane_map; plot_surface / get_velocity of the same script).  Armed by
                          the time loops of solve_system_active / solve_system_passive; call Recorder.arm(t0) when stepping by hand.
-        Without the last two arguments the recorder issues the same device calls and rows as before."""
+        Without the last two arguments the recorder issues the same device calls and rows as before.
+
+        Partitioned solvers (partition.distribute_solver): every rank makes the same call, with the same capacity, in the GLOBAL
+        mesh's terms -- coordinates, global facet ids or boxes, a global region array (S.global_mesh_tuple is the global mesh).  Each
+        rank records what it owns (a probe: the owner of its cell; a membrane facet: the owner of its first cell; a cell: its owner)
+        without any communication per sample; the partial rows are summed over the ranks when the buffer is read.  The Recorder's
+        results are the global ones on every rank, and reading them (flush, rows, t, points, membrane, regions, membrane_map,
+        conduction_velocity, save) is collective.  Rank 0 alone writes timeseries.h5."""
         from knpemidg.recorder import Recorder
         if membrane_states and not self.use_device_ode:
             raise _abi.KnpError("Solver.record: membrane_states read the ODE state tables on the device; with KNP_HOST_ODE=1 they "
                                 "live on the host")
-        if getattr(self, "local_mesh", None) is not None or getattr(self, "nc_owned", None) is not None:
-            raise _abi.KnpError("Solver.record: partitioned solvers (distribute_solver) are not supported; record on a one-GPU run")
+        loc, gmt = getattr(self, "local_mesh", None), getattr(self, "global_mesh_tuple", None)
+        if (loc is None or gmt is None) and (loc is not None or getattr(self, "nc_owned", None) is not None):
+            raise _abi.KnpError("Solver.record: a partitioned solver needs its LocalMesh and the global mesh (local_mesh, "
+                                "global_mesh_tuple: partition.distribute_solver sets them)")
         if getattr(self, "mesh", None) is None:
             raise _abi.KnpError("Solver.record: call setup_domain first")
         mtags = self.membrane_tags if self.dev is not None else None
-        rec = Recorder(self.mesh, self.subdomains.array(), self.surfaces.array(), self.degree_knp, [ion['name'] for ion in self.ion_list],
+        mesh, sub, surf = (self.mesh, self.subdomains, self.surfaces) if loc is None else gmt
+        tags = lambda f: np.asarray(f.array() if hasattr(f, "array") else f)
+        rec = Recorder(mesh, tags(sub), tags(surf), self.degree_knp, [ion['name'] for ion in self.ion_list],
                        points=points, membrane_sets=membrane_sets, regions=regions, capacity=capacity, point_tags=point_tags,
-                       membrane_tags=mtags, membrane_states=membrane_states, membrane_map=membrane_map)
+                       membrane_tags=mtags, membrane_states=membrane_states, membrane_map=membrane_map, local_mesh=loc)
         if self.dev is not None:
             rec.attach(self.dev, models=[m['ode'] for m in self.mem_models] if self.mem_models else None)
         self.recorder = rec
