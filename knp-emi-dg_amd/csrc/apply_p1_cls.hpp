@@ -124,14 +124,7 @@ __global__ __launch_bounds__(BLK) void k_emi_apply_cls_staged(MeshDev m, const d
     if (!valid) return;
     const lds_double* rec = TO_LDS(s_tab) + cls * 11;
     CellGeom<D> K;
-    K.vol = rec[0];
-    {
-        int q = 1;
-#pragma unroll
-        for (int a = 0; a < NV; ++a)
-#pragma unroll
-            for (int b = a; b < NV; ++b) { K.G[a][b] = rec[q]; K.G[b][a] = rec[q]; ++q; }
-    }
+    class_gram<D>(rec, K);
     StageView<D> st{TO_LDS(s_x), TO_LDS(s_k), nullptr, nullptr, c0,
                     (unsigned)((m.c_end - c0 < BLK) ? (m.c_end - c0) : BLK), nullptr, rec, TO_LDS(s_ext) + cls * (KNP_CLS_EXT + 1)};
     {
@@ -282,14 +275,7 @@ __global__ __launch_bounds__(BLK) void k_knp_apply_cls_staged(MeshDev m, const d
     if (!valid) return;
     const lds_double* rec = TO_LDS(s_tab) + cls * KNP_CLS_STRIDE;
     CellGeom<D> K;
-    K.vol = rec[0];
-    {
-        int q = 1;
-#pragma unroll
-        for (int a = 0; a < NV; ++a)
-#pragma unroll
-            for (int b = a; b < NV; ++b) { K.G[a][b] = rec[q]; K.G[b][a] = rec[q]; ++q; }
-    }
+    class_gram<D>(rec, K);
     KnpStage<D, NS, BLK> st{TO_LDS(s_x), TO_LDS(s_g), TO_LDS(s_D), rec, c0,
                             (unsigned)((m.c_end - c0 < BLK) ? (m.c_end - c0) : BLK)};
     // volume terms (same as knp_cell)

@@ -25,13 +25,7 @@
 
 // vol + Gram matrix of the cell's class, straight from the (L1/L2-resident) table into registers
 __device__ __forceinline__ void load_class_gram(const double* __restrict__ table, unsigned cls, CellGeom<3>& K) {
-    const double* rec = table + (size_t)cls * KNP_CLS_STRIDE;
-    K.vol = rec[0];
-    int q = 1;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = a; b < 4; ++b) { K.G[a][b] = rec[q]; K.G[b][a] = rec[q]; ++q; }
+    class_gram<3>(table + (size_t)cls * KNP_CLS_STRIDE, K);
 }
 
 // The blocks of one workgroup.  The block range is cut into nq contiguous chunks, nq/8 per XCD (XCD = blockIdx.x & 7,

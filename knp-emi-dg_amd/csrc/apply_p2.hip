@@ -427,12 +427,7 @@ template <int ND> __device__ __forceinline__ void store_cellvec(double* __restri
 template <int D, bool CLS> __device__ __forceinline__ void cell_geometry_p2(const MeshDev& m, int64_t c, const lds_double* rec, CellGeom<D>& K) {
     constexpr int NV = D + 1;
     if (CLS) {
-        K.vol = rec[0];
-        int q = 1;
-#pragma unroll
-        for (int a = 0; a < NV; ++a)
-#pragma unroll
-            for (int b = a; b < NV; ++b) { K.G[a][b] = rec[q]; K.G[b][a] = rec[q]; ++q; }
+        class_gram<D>(rec, K);
     } else {
         int verts[NV];
         load_cell_ints<D>(m.cells, c, verts);

@@ -19,6 +19,7 @@
 // [256, 480) = halo list entries.
 #include "cell_geom.hpp"
 #include "ring_common.hpp"
+#include "ring_facet.hpp"
 #include <algorithm>
 #include <cstdlib>
 #include <map>
@@ -41,14 +42,10 @@ __device__ __forceinline__ void dma_list(const MeshDev& m, int64_t b, unsigned d
     const int off = lane * 4 < m.hb_stride ? lane * 4 : 0;
     glds16(m.hb_src + b * m.hb_stride + off, dst);
 }
-// ---- geometry-class record in LDS: [0] vol, [1..10] Gram (upper triangle), [11 + 8 i ..] the derived facet coefficients of cls_ext ----
-__device__ __forceinline__ void class_gram(const lds_double* rec, CellGeom<3>& K) {
-    K.vol = rec[0];
-    int q = 1;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = a; b < 4; ++b) { K.G[a][b] = rec[q]; K.G[b][a] = rec[q]; ++q; }
+// ---- geometry-class records in LDS: [0] vol, [1..10] Gram (upper triangle), [11 + 8 i ..] the derived facet coefficients of cls_ext ----
+template <int NTHREADS> __device__ __forceinline__ void stage_class_records(const MeshDev& m, double* s_cls) {
+    for (int i = threadIdx.x; i < m.ncls * 11; i += NTHREADS) s_cls[(i / 11) * RCLS + (i % 11)] = m.cls_table[(i / 11) * KNP_CLS_STRIDE + (i % 11)];
+    for (int i = threadIdx.x; i < m.ncls * KNP_CLS_EXT; i += NTHREADS) s_cls[(i / KNP_CLS_EXT) * RCLS + 11 + (i % KNP_CLS_EXT)] = m.cls_ext[i];
 }
 
 // ================================================================================================================================
@@ -64,73 +61,9 @@ template <int NS> struct KnpRing {
     static_assert(NDATA <= 63, "vmcnt is a 6-bit counter");
 };
 
-template <int NS, int I>
-__device__ __forceinline__ void knp_facet_ring(const CellGeom<3>& K, uint32_t flags, unsigned loc, unsigned dsel, const double (*xv)[4],
-                                               const double (*gx)[4], const double* gp, const double* Dk, const double* hvD,
-                                               const double* zpsi, double tau,
-                                               const lds_double* X, const lds_double* G, const lds_double* sD, const lds_double* ft,
-                                               double (*y)[4]) {
-    constexpr int D = 3, NV = 4;
-    const uint32_t fb = (flags >> (8 * I)) & 0xffu;
-    if (((fb >> 2) & 3u) != FK_SIPG) return;
-    const unsigned j = fb & 3u;
-    // class-level coefficients (MeshDev::cls_ext): gr = G_II / L_I, cf = neighbour-gradient weights, penalty and upwind factors
-    const double gr = ft[8 * I], pen_geo = ft[8 * I + 4], nLI_DV = ft[8 * I + 5];
-    double cf[D];
-#pragma unroll
-    for (int mm = 0; mm < D; ++mm) cf[mm] = ft[8 * I + 1 + mm];
-    double gp_nb;
-    {   // the 16-byte half that holds component j of the neighbour's gphi row: own rows (swizzled image) or the halo's [entry][2]
-        typedef double __attribute__((ext_vector_type(2))) vdouble2;
-        typedef __attribute__((address_space(3))) vdouble2 lds_vdouble2;
-        const unsigned idx = loc < (unsigned)RB ? loc * NV + 2u * (((j >> 1) ^ (loc >> 3)) & 1u) : (unsigned)(RB * NV) + (loc - RB) * 2u;
-        const vdouble2 g2 = *(const lds_vdouble2*)(G + idx);
-        gp_nb = (j & 1u) ? g2.y : g2.x;
-    }
-    const double DV = (double)D * K.vol;
-    const double up_own = fmax(-gp[I], 0.0) * DV;
-    const double up_nb = fmax(-gp_nb, 0.0) * nLI_DV;
-    const double penA = tau * pen_geo;
-    const double hv = 0.5 * K.vol;
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        double xr[NV], xf[D];
-        lds_row(X + (unsigned)k * (RENT * NV), loc, xr);
-        const double xap = pick_apex<D>(xr, (int)j);
-#pragma unroll
-        for (int mm = 0; mm < D; ++mm) xf[mm] = pick_facet<D>(xr, mm, (int)j);
-        const double Dn = sD[(unsigned)k * KNP_MAX_MAT + dsel];
-        const double s_own = gx[k][I];                                             // (G x)_I = grad(u) . g_I, from the cell term
-        double s_nb = xap * gr;
-#pragma unroll
-        for (int mm = 0; mm < D; ++mm) s_nb = fma(xf[mm], cf[mm], s_nb);
-        // penalty and upwind weights of the two traces:  D (pen - z psi un),  written so that each costs one FMA and one product
-        const double zp = zpsi[k];
-        const double c_own = Dk[k] * fma(-zp, up_own, penA);
-        const double c_nb = Dn * fma(-zp, up_nb, penA);
-        double sdu = 0.0, w[D], sw = 0.0;
-#pragma unroll
-        for (int mm = 0; mm < D; ++mm) {
-            const double xo = xv[k][mm + (mm >= I)];
-            sdu += xo - xf[mm];
-            w[mm] = fma(c_own, xo, -c_nb * xf[mm]);
-            sw += w[mm];
-        }
-        const double t1m = fma(FacetConst<D>::mass, sw, hv * fma(Dk[k], s_own, Dn * s_nb));
-        const double t2 = hvD[k] * sdu;
-#pragma unroll
-        for (int a = 0; a < NV; ++a) y[k][a] = fma(K.G[a][I], t2, y[k][a]);
-#pragma unroll
-        for (int mm = 0; mm < D; ++mm) y[k][mm + (mm >= I)] += fma(FacetConst<D>::mass, w[mm], t1m);
-    }
-}
-
 // per-cell topology bytes of a block, DMA'd by the loaders next to the nodal rows: flag bytes (4 B / cell), hb_loc (8 B), neighbour
 // materials (4 B), class (2 B), material (1 B).  The device arrays are padded by 4 KB (abi.hip), so whole blocks can be read past nc.
 struct CellMeta { uint32_t flags, nm; uint2 lw; unsigned cls, mymat; };
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-typedef __attribute__((address_space(3))) uint16_t lds_u16;
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
 __device__ __forceinline__ CellMeta read_meta(const char* meta, unsigned t, bool knp) {
     CellMeta q;
     q.flags = ((const lds_u32*)(meta + META_F))[t];
@@ -165,8 +98,7 @@ __global__ __launch_bounds__(RB * NG + 64 * RLOADERS) void k_knp_apply_ring(Mesh
     const int lane = threadIdx.x & 63;
     const RingWalk w(m);
     if (w.blk(0) < 0) return;
-    for (int i = threadIdx.x; i < m.ncls * 11; i += NTHREADS) s_cls[(i / 11) * RCLS + (i % 11)] = m.cls_table[(i / 11) * KNP_CLS_STRIDE + (i % 11)];
-    for (int i = threadIdx.x; i < m.ncls * KNP_CLS_EXT; i += NTHREADS) s_cls[(i / KNP_CLS_EXT) * RCLS + 11 + (i % KNP_CLS_EXT)] = m.cls_ext[i];
+    stage_class_records<NTHREADS>(m, s_cls);
     if (threadIdx.x < NS * KNP_MAX_MAT) s_D[threadIdx.x] = dtab[threadIdx.x];
     if (wave >= 4 * NG) {
         // ------------------------------------------------ loaders ------------------------------------------------
@@ -218,23 +150,7 @@ __global__ __launch_bounds__(RB * NG + 64 * RLOADERS) void k_knp_apply_ring(Mesh
                 }
             }
         };
-        // all but this loader's share of the youngest block have landed (its list piece, issued before that share, included)
-        auto wait_older = [&]() {
-            if (lw == 0) wait_vm<N0>(); else if (lw == 1) wait_vm<N1>(); else if (lw == 2) wait_vm<N2>(); else wait_vm<N3>();
-        };
-        list_dma(0); list_dma(1);
-        wait_vm<0>();
-        ring_barrier();                                                // A: every loader sees lists 0 and 1
-        data_dma(0);
-        list_dma(2);
-        if (w.blk(1) >= 0) { data_dma(1); wait_older(); } else wait_vm<0>();
-        ring_barrier();                                                // B: block 0 and list 2 have landed
-        for (int64_t n = 0; w.blk(n) >= 0; ++n) {
-            list_dma(n + 3);
-            if (w.blk(n + 2) >= 0) { data_dma(n + 2); wait_older(); }  // block n + 2 stays in flight; list n + 3, block n + 1 have landed
-            else wait_vm<0>();
-            ring_barrier();
-        }
+        load_two_ahead_counted<false, N0, N1, N2, N3>(w, lw, list_dma, data_dma);
         return;
     }
     // ------------------------------------------------ consumers ------------------------------------------------
@@ -244,7 +160,7 @@ __global__ __launch_bounds__(RB * NG + 64 * RLOADERS) void k_knp_apply_ring(Mesh
 #pragma unroll
     for (int k = 0; k < KS; ++k) zpsi[k] = ka.z[k0 + k] * ka.psi;
     ring_barrier();                                                    // A: class / material tables staged
-    ring_barrier();                                                    // B
+    ring_barrier();                                                    // B, then one per block (load_two_ahead_counted)
     for (int64_t n = 0;; ++n) {
         const int64_t b = w.blk(n);
         if (b < 0) break;
@@ -257,7 +173,7 @@ __global__ __launch_bounds__(RB * NG + 64 * RLOADERS) void k_knp_apply_ring(Mesh
             const lds_double* rec = TO_LDS(s_cls) + cur.cls * RCLS;
             const lds_double* sD = TO_LDS(s_D) + k0 * KNP_MAX_MAT;
             CellGeom<3> K;
-            class_gram(rec, K);
+            class_gram<3>(rec, K);
             double xv[KS][NV], y[KS][NV], gp[NV], Dk[KS];
             lds_row(G, t, gp);
 #pragma unroll
@@ -265,32 +181,14 @@ __global__ __launch_bounds__(RB * NG + 64 * RLOADERS) void k_knp_apply_ring(Mesh
                 lds_row(X + k * (RENT * NV), t, xv[k]);
                 Dk[k] = sD[k * KNP_MAX_MAT + cur.mymat];
             }
-            const double mw = ka.inv_dt * K.vol / 20.0;
             double gx[KS][NV], hvD[KS];
-#pragma unroll
-            for (int k = 0; k < KS; ++k) hvD[k] = 0.5 * K.vol * Dk[k];
-#pragma unroll
-            for (int k = 0; k < KS; ++k) {
-                double sx = 0.0;
-#pragma unroll
-                for (int a = 0; a < NV; ++a) sx += xv[k][a];
-                const double drift = zpsi[k] * Dk[k] * K.vol * sx / (double)NV;
-                const double dv = Dk[k] * K.vol;
-#pragma unroll
-                for (int a = 0; a < NV; ++a) {
-                    double sacc = 0.0;
-#pragma unroll
-                    for (int bb = 0; bb < NV; ++bb) sacc = fma(xv[k][bb], K.G[bb][a], sacc);
-                    gx[k][a] = sacc;
-                    y[k][a] = fma(mw, sx + xv[k][a], fma(dv, sacc, drift * gp[a]));
-                }
-            }
-            const lds_double* ft = rec + 11;
+            knp_cell_term<KS>(K, xv, gp, Dk, zpsi, ka.inv_dt, gx, hvD, y);
+            const ClassCoef ft{rec + 11};
             if (!(dbg & 2)) {
-            knp_facet_ring<KS, 0>(K, cur.flags, cur.lw.x & 0xffffu, cur.nm & 0xffu, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, ft, y);
-            knp_facet_ring<KS, 1>(K, cur.flags, cur.lw.x >> 16, (cur.nm >> 8) & 0xffu, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, ft, y);
-            knp_facet_ring<KS, 2>(K, cur.flags, cur.lw.y & 0xffffu, (cur.nm >> 16) & 0xffu, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, ft, y);
-            knp_facet_ring<KS, 3>(K, cur.flags, cur.lw.y >> 16, cur.nm >> 24, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, ft, y);
+            knp_facet_ring<KS, 0, RENT * NV>(K, cur.flags, cur.lw.x & 0xffffu, ft, cur.nm & 0xffu, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, y);
+            knp_facet_ring<KS, 1, RENT * NV>(K, cur.flags, cur.lw.x >> 16, ft, (cur.nm >> 8) & 0xffu, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, y);
+            knp_facet_ring<KS, 2, RENT * NV>(K, cur.flags, cur.lw.y & 0xffffu, ft, (cur.nm >> 16) & 0xffu, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, y);
+            knp_facet_ring<KS, 3, RENT * NV>(K, cur.flags, cur.lw.y >> 16, ft, cur.nm >> 24, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, y);
             }
 #pragma unroll
             for (int k = 0; k < KS; ++k) store_nodal<3>(yout + (int64_t)(k0 + k) * m.nc * NV, c, y[k]);
@@ -308,71 +206,6 @@ struct EmiRing {
     static constexpr int SLOT = META0 + META_EMI;
     static constexpr int NDATA = 8 + 8 + 2 * RHX + 4;
 };
-
-template <int I>
-__device__ __forceinline__ void emi_facet_ring(const CellGeom<3>& K, uint32_t flags, unsigned loc, const double* xv, const double* gx,
-                                               const double* kv, double C_phi, double tau, const lds_double* X, const lds_double* KA,
-                                               const lds_double* ft, double* y) {
-    constexpr int D = 3, NV = 4;
-    const uint32_t fb = (flags >> (8 * I)) & 0xffu;
-    const uint32_t kind = (fb >> 2) & 3u;
-    if (kind >= FK_EXTERIOR) return;
-    const unsigned j = fb & 3u;
-    double xr[NV], kr[NV], xf[D], knf[D];
-    lds_row(X, loc, xr);
-    lds_row(KA, loc, kr);
-    const double xap = pick_apex<D>(xr, (int)j);
-#pragma unroll
-    for (int mm = 0; mm < D; ++mm) {
-        xf[mm] = pick_facet<D>(xr, mm, (int)j);
-        knf[mm] = pick_facet<D>(kr, mm, (int)j);
-    }
-    double du[D], sdu = 0.0;
-#pragma unroll
-    for (int mm = 0; mm < D; ++mm) {
-        du[mm] = xv[mm + (mm >= I)] - xf[mm];
-        sdu += du[mm];
-    }
-    const double sqG_DV = ft[8 * I + 6];                                  // sqrt(G_II) D vol = facet area
-    if (kind == FK_MEMBRANE) {
-        const double w = C_phi * sqG_DV * FacetConst<D>::mass;
-#pragma unroll
-        for (int mm = 0; mm < D; ++mm) y[mm + (mm >= I)] = fma(w, sdu + du[mm], y[mm + (mm >= I)]);
-        return;
-    }
-    const double gr = ft[8 * I];
-    const double s_own = gx[I];                                            // (G x)_I from the cell term
-    double s_nb = xap * gr;
-#pragma unroll
-    for (int mm = 0; mm < D; ++mm) s_nb = fma(xf[mm], ft[8 * I + 1 + mm], s_nb);
-    double kf[D], sk = 0.0, skn = 0.0, q = 0.0;
-#pragma unroll
-    for (int mm = 0; mm < D; ++mm) {
-        kf[mm] = kv[mm + (mm >= I)];
-        sk += kf[mm];
-        skn += knf[mm];
-        q = fma(kf[mm], sdu + du[mm], q);
-    }
-    const double hm = 0.5 * (double)D * K.vol * FacetConst<D>::mass;
-    q *= hm;
-#pragma unroll
-    for (int a = 0; a < NV; ++a) y[a] = fma(K.G[a][I], q, y[a]);
-    const double pw = tau * ft[8 * I + 4] * FacetConst<D>::trip;
-    double kb[D], skb = 0.0, skd = 0.0;
-#pragma unroll
-    for (int mm = 0; mm < D; ++mm) {
-        kb[mm] = 0.5 * (kf[mm] + knf[mm]);
-        skb += kb[mm];
-        skd = fma(kb[mm], du[mm], skd);
-    }
-    const double bs = fma(skb, sdu, skd);
-#pragma unroll
-    for (int mm = 0; mm < D; ++mm) {
-        const double t1 = hm * fma(s_own, sk + kf[mm], s_nb * (skn + knf[mm]));
-        const double t3 = pw * (bs + fma(kb[mm], sdu, du[mm] * fma(2.0, kb[mm], skb)));
-        y[mm + (mm >= I)] += t1 + t3;
-    }
-}
 
 // Two consumer groups of four waves, STAGGERED by half a block: a block is worked on during two barrier intervals (first half: own
 // rows, cell term, facets 0 and 1; second half: facets 2 and 3, store), group n % 2 starts block n in interval n, so every SIMD
@@ -392,8 +225,7 @@ __global__ __launch_bounds__(2 * RB + 64 * RLOADERS) void k_emi_apply_ring(MeshD
     const int lane = threadIdx.x & 63;
     const RingWalk w(m);
     if (w.blk(0) < 0) return;
-    for (int i = threadIdx.x; i < m.ncls * 11; i += NTHREADS) s_cls[(i / 11) * RCLS + (i % 11)] = m.cls_table[(i / 11) * KNP_CLS_STRIDE + (i % 11)];
-    for (int i = threadIdx.x; i < m.ncls * KNP_CLS_EXT; i += NTHREADS) s_cls[(i / KNP_CLS_EXT) * RCLS + 11 + (i % KNP_CLS_EXT)] = m.cls_ext[i];
+    stage_class_records<NTHREADS>(m, s_cls);
     if (wave >= 8) {
         // loaders (see k_knp_apply_ring):  0: x rows + the lists   1: kappa rows   2: x halo rows + flag / class bytes   3: kappa halo rows + hb_loc
         const int lw = wave - 8;
@@ -422,32 +254,17 @@ __global__ __launch_bounds__(2 * RB + 64 * RLOADERS) void k_emi_apply_ring(MeshD
                 }
             }
         };
-        auto wait_older = [&]() {
-            if (lw == 0) wait_vm<N0>(); else if (lw == 1) wait_vm<N1>(); else if (lw == 2) wait_vm<N2>(); else wait_vm<N3>();
-        };
-        list_dma(0); list_dma(1);
-        wait_vm<0>();
-        ring_barrier();
-        data_dma(0);
-        list_dma(2);
-        if (w.blk(1) >= 0) { data_dma(1); wait_older(); } else wait_vm<0>();
-        ring_barrier();
-        for (int64_t n = 0;; ++n) {                                    // interval n: block n's first half, block n - 1's second half
-            if (w.blk(n) < 0) { wait_vm<0>(); ring_barrier(); break; } // the last interval has second halves only
-            list_dma(n + 3);
-            if (w.blk(n + 2) >= 0) { data_dma(n + 2); wait_older(); }
-            else wait_vm<0>();
-            ring_barrier();
-        }
+        load_two_ahead_counted<true, N0, N1, N2, N3>(w, lw, list_dma, data_dma);   // interval n: block n's first half, block n - 1's second half
         return;
     }
     const unsigned t = threadIdx.x & (RB - 1);
     const int g = wave >> 2;
-    ring_barrier();
-    ring_barrier();
+    ring_barrier();                                                    // A: class tables staged
+    ring_barrier();                                                    // B, then one per interval, the closing one included (load_two_ahead_counted)
     CellGeom<3> K;
     double xv[NV], kv[NV], yv[NV], gx[NV];
-    const lds_double *X = nullptr, *KA = nullptr, *ft = nullptr;
+    const lds_double *X = nullptr, *KA = nullptr;
+    ClassCoef ft{nullptr};
     CellMeta cur;
     cur.flags = 0; cur.lw = make_uint2(0u, 0u); cur.cls = 0; cur.nm = 0; cur.mymat = 0;
     int64_t ccur = -1;
@@ -464,29 +281,18 @@ __global__ __launch_bounds__(2 * RB + 64 * RLOADERS) void k_emi_apply_ring(MeshD
                     X = (const lds_double*)slot;
                     KA = (const lds_double*)(slot + R::XB);
                     const lds_double* rec = TO_LDS(s_cls) + cur.cls * RCLS;
-                    ft = rec + 11;
-                    class_gram(rec, K);
+                    ft.ft = rec + 11;
+                    class_gram<3>(rec, K);
                     lds_row(X, t, xv);
                     lds_row(KA, t, kv);
-                    double kbar = 0.0;
-#pragma unroll
-                    for (int a = 0; a < NV; ++a) kbar += kv[a];
-                    kbar *= K.vol / (double)NV;
-#pragma unroll
-                    for (int a = 0; a < NV; ++a) {
-                        double sa = 0.0;
-#pragma unroll
-                        for (int bb = 0; bb < NV; ++bb) sa = fma(xv[bb], K.G[bb][a], sa);
-                        gx[a] = sa;
-                        yv[a] = kbar * sa;
-                    }
-                    emi_facet_ring<0>(K, cur.flags, cur.lw.x & 0xffffu, xv, gx, kv, C_phi, tau, X, KA, ft, yv);
-                    emi_facet_ring<1>(K, cur.flags, cur.lw.x >> 16, xv, gx, kv, C_phi, tau, X, KA, ft, yv);
+                    emi_cell_term(K, xv, kv, gx, yv);
+                    emi_facet_ring<0>(K, cur.flags, cur.lw.x & 0xffffu, ft, xv, gx, kv, C_phi, tau, X, KA, yv);
+                    emi_facet_ring<1>(K, cur.flags, cur.lw.x >> 16, ft, xv, gx, kv, C_phi, tau, X, KA, yv);
                 }
             }
         } else if (n >= 1 && valid) {                                  // second half of block n - 1
-            emi_facet_ring<2>(K, cur.flags, cur.lw.y & 0xffffu, xv, gx, kv, C_phi, tau, X, KA, ft, yv);
-            emi_facet_ring<3>(K, cur.flags, cur.lw.y >> 16, xv, gx, kv, C_phi, tau, X, KA, ft, yv);
+            emi_facet_ring<2>(K, cur.flags, cur.lw.y & 0xffffu, ft, xv, gx, kv, C_phi, tau, X, KA, yv);
+            emi_facet_ring<3>(K, cur.flags, cur.lw.y >> 16, ft, xv, gx, kv, C_phi, tau, X, KA, yv);
             store_nodal<3>(yout, ccur, yv);
         }
         ring_barrier();

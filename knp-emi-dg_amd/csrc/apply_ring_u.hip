@@ -19,6 +19,7 @@
 // bytes of a 137-byte operator; recomputing costs FP64 issue slots, which the loaders' stream leaves free.
 #include "cell_geom.hpp"
 #include "ring_common.hpp"
+#include "ring_facet.hpp"
 #include <algorithm>
 #include <cstdlib>
 #include <map>
@@ -70,100 +71,14 @@ template <int NS> struct KnpU {
     static constexpr int SLOT = MA + 1024;
 };
 
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-
-// ---- consumer side: geometry from the staged coordinates -------------------------------------------------------------------------
-__device__ __forceinline__ void lds_vertex(const lds_double* co, unsigned v, double* X) {
-    typedef double __attribute__((ext_vector_type(2))) vdouble2;
-    typedef __attribute__((address_space(3))) vdouble2 lds_vdouble2;
-    const vdouble2 a = *(const lds_vdouble2*)(co + 4 * v);
-    X[0] = a.x; X[1] = a.y; X[2] = co[4 * v + 2];
-}
-
-// what the facet terms need from the geometry of facet I (MeshDev::cls_ext holds the same numbers per class on structured meshes):
-// gr = G_II / L_I, cf = the neighbour-gradient weights G_{a_m I} - L_{a_m} gr, the penalty and neighbour-volume factors
-struct FacetCoef { double gr, cf[3], pen_geo, nLI_DV, sqG_DV; };
-template <int I> __device__ __forceinline__ void facet_coef(const CellGeom<3>& K, const lds_double* co, unsigned vapex, double hinv, FacetCoef& f) {
-    double Xo[3], L[4];
-    lds_vertex(co, vapex, Xo);
-    apex_bary<3>(K, Xo, L);
-    const double gr = K.G[I][I] * fast_rcp(L[I]);
-    f.gr = gr;
-#pragma unroll
-    for (int mm = 0; mm < 3; ++mm) f.cf[mm] = fma(-L[mm + (mm >= I)], gr, K.G[mm + (mm >= I)][I]);
-    const double DV = 3.0 * K.vol;
-    f.sqG_DV = fast_sqrt(K.G[I][I]) * DV;
-    f.pen_geo = hinv * f.sqG_DV;
-    f.nLI_DV = -L[I] * DV;
-}
-
-// ================================================================================================================================
-// EMI:  y = A(kappa) x      (forms and notation: apply_p1.hip, emi_facet_cls; arithmetic of apply_ring.hip: emi_facet_ring)
-// ================================================================================================================================
-template <int I>
-__device__ __forceinline__ void emi_facet_u(const CellGeom<3>& K, uint32_t flags, unsigned loc, unsigned vapex, double hinv, const double* xv,
-                                            const double* gx, const double* kv, double C_phi, double tau, const lds_double* X,
-                                            const lds_double* KA, const lds_double* co, double* y) {
-    constexpr int D = 3, NV = 4;
-    const uint32_t fb = (flags >> (8 * I)) & 0xffu;
-    const uint32_t kind = (fb >> 2) & 3u;
-    if (kind >= FK_EXTERIOR) return;
-    const unsigned j = fb & 3u;
-    double xr[NV], kr[NV], xf[D], knf[D];
-    lds_row(X, loc, xr);
-    lds_row(KA, loc, kr);
-    const double xap = pick_apex<D>(xr, (int)j);
-#pragma unroll
-    for (int mm = 0; mm < D; ++mm) {
-        xf[mm] = pick_facet<D>(xr, mm, (int)j);
-        knf[mm] = pick_facet<D>(kr, mm, (int)j);
-    }
-    double du[D], sdu = 0.0;
-#pragma unroll
-    for (int mm = 0; mm < D; ++mm) {
-        du[mm] = xv[mm + (mm >= I)] - xf[mm];
-        sdu += du[mm];
-    }
-    if (kind == FK_MEMBRANE) {
-        const double w = C_phi * (fast_sqrt(K.G[I][I]) * (3.0 * K.vol)) * FacetConst<D>::mass;       // facet area = sqrt(G_II) D vol
-#pragma unroll
-        for (int mm = 0; mm < D; ++mm) y[mm + (mm >= I)] = fma(w, sdu + du[mm], y[mm + (mm >= I)]);
-        return;
-    }
-    FacetCoef fc;
-    facet_coef<I>(K, co, vapex, hinv, fc);
-    const double s_own = gx[I];                                            // (G x)_I from the cell term
-    double s_nb = xap * fc.gr;
-#pragma unroll
-    for (int mm = 0; mm < D; ++mm) s_nb = fma(xf[mm], fc.cf[mm], s_nb);
-    double kf[D], sk = 0.0, skn = 0.0, q = 0.0;
-#pragma unroll
-    for (int mm = 0; mm < D; ++mm) {
-        kf[mm] = kv[mm + (mm >= I)];
-        sk += kf[mm];
-        skn += knf[mm];
-        q = fma(kf[mm], sdu + du[mm], q);
-    }
-    const double hm = 0.5 * (double)D * K.vol * FacetConst<D>::mass;
-    q *= hm;
-#pragma unroll
-    for (int a = 0; a < NV; ++a) y[a] = fma(K.G[a][I], q, y[a]);
-    const double pw = tau * fc.pen_geo * FacetConst<D>::trip;
-    double kb[D], skb = 0.0, skd = 0.0;
-#pragma unroll
-    for (int mm = 0; mm < D; ++mm) {
-        kb[mm] = 0.5 * (kf[mm] + knf[mm]);
-        skb += kb[mm];
-        skd = fma(kb[mm], du[mm], skd);
-    }
-    const double bs = fma(skb, sdu, skd);
-#pragma unroll
-    for (int mm = 0; mm < D; ++mm) {
-        const double t1 = hm * fma(s_own, sk + kf[mm], s_nb * (skn + knf[mm]));
-        const double t3 = pw * (bs + fma(kb[mm], sdu, du[mm] * fma(2.0, kb[mm], skb)));
-        y[mm + (mm >= I)] += t1 + t3;
-    }
+// ---- consumer side: geometry from the staged coordinates; vl0 = the positions of the cell's four vertices in co, one byte each ----
+__device__ __forceinline__ void cell_geometry_staged(const lds_double* co, uint32_t vl0, CellGeom<3>& K) {
+    double Xc[4][3];
+    lds_vertex(co, vl0 & 0xffu, Xc[0]);
+    lds_vertex(co, (vl0 >> 8) & 0xffu, Xc[1]);
+    lds_vertex(co, (vl0 >> 16) & 0xffu, Xc[2]);
+    lds_vertex(co, vl0 >> 24, Xc[3]);
+    cell_geometry_from<3>(Xc, K);
 }
 
 // loaders of both kernels: the lists of block n (halo list: two pieces, vertex list: one) into list buffer n & 1
@@ -180,6 +95,9 @@ __device__ __forceinline__ void dma_coords_u(const double* __restrict__ coords, 
     }
 }
 
+// ================================================================================================================================
+// EMI:  y = A(kappa) x      (forms and notation: apply_p1.hip, emi_facet_cls; arithmetic: ring_facet.hpp)
+// ================================================================================================================================
 __global__ __launch_bounds__(RB + 64 * ULOADERS) void k_emi_apply_ring_u(MeshDev m, RingUTables T, const double* __restrict__ x,
                                                                        const double* __restrict__ kappa, double* __restrict__ yout, double C_phi,
                                                                        double tau) {
@@ -226,23 +144,12 @@ __global__ __launch_bounds__(RB + 64 * ULOADERS) void k_emi_apply_ring_u(MeshDev
                 }
             }
         };
-        list_dma(0); list_dma(1);
-        wait_vm<0>();
-        ring_barrier();                                                // A: every loader sees lists 0 and 1
-        data_dma(0);
-        wait_vm<0>();
-        ring_barrier();                                                // B: block 0 has landed
-        for (int64_t n = 0; w.blk(n) >= 0; ++n) {
-            list_dma(n + 2);                                           // into the buffer block n's gathers read in the last interval
-            if (w.blk(n + 1) >= 0) data_dma(n + 1);
-            wait_vm<0>();
-            ring_barrier();
-        }
+        load_one_ahead_drained(w, list_dma, data_dma);
         return;
     }
     const unsigned t = threadIdx.x & (RB - 1);
-    ring_barrier();
-    ring_barrier();
+    ring_barrier();                                                    // A
+    ring_barrier();                                                    // B, then one per block (load_one_ahead_drained)
     for (int64_t n = 0;; ++n) {
         const int64_t b = w.blk(n);
         if (b < 0) break;
@@ -256,34 +163,16 @@ __global__ __launch_bounds__(RB + 64 * ULOADERS) void k_emi_apply_ring_u(MeshDev
             const uint32_t vl0 = ((const lds_u32*)(slot + R::VL))[2 * t], vl1 = ((const lds_u32*)(slot + R::VL))[2 * t + 1];
             const uint32_t lw0 = ((const lds_u32*)(slot + R::HL))[2 * t], lw1 = ((const lds_u32*)(slot + R::HL))[2 * t + 1];
             CellGeom<3> K;
-            {
-                double Xc[4][3];
-                lds_vertex(co, vl0 & 0xffu, Xc[0]);
-                lds_vertex(co, (vl0 >> 8) & 0xffu, Xc[1]);
-                lds_vertex(co, (vl0 >> 16) & 0xffu, Xc[2]);
-                lds_vertex(co, vl0 >> 24, Xc[3]);
-                cell_geometry_from<3>(Xc, K);
-            }
+            cell_geometry_staged(co, vl0, K);
             double xv[NV], kv[NV], yv[NV], gx[NV], hi[NV];
             lds_row(X, t, xv);
             lds_row(KA, t, kv);
             lds_row((const lds_double*)(slot + R::HI), t, hi);
-            double kbar = 0.0;
-#pragma unroll
-            for (int a = 0; a < NV; ++a) kbar += kv[a];
-            kbar *= K.vol / (double)NV;
-#pragma unroll
-            for (int a = 0; a < NV; ++a) {
-                double sa = 0.0;
-#pragma unroll
-                for (int bb = 0; bb < NV; ++bb) sa = fma(xv[bb], K.G[bb][a], sa);
-                gx[a] = sa;
-                yv[a] = kbar * sa;
-            }
-            emi_facet_u<0>(K, flags, lw0 & 0xffffu, vl1 & 0xffu, hi[0], xv, gx, kv, C_phi, tau, X, KA, co, yv);
-            emi_facet_u<1>(K, flags, lw0 >> 16, (vl1 >> 8) & 0xffu, hi[1], xv, gx, kv, C_phi, tau, X, KA, co, yv);
-            emi_facet_u<2>(K, flags, lw1 & 0xffffu, (vl1 >> 16) & 0xffu, hi[2], xv, gx, kv, C_phi, tau, X, KA, co, yv);
-            emi_facet_u<3>(K, flags, lw1 >> 16, vl1 >> 24, hi[3], xv, gx, kv, C_phi, tau, X, KA, co, yv);
+            emi_cell_term(K, xv, kv, gx, yv);
+            emi_facet_ring<0>(K, flags, lw0 & 0xffffu, CoordCoef{co, vl1 & 0xffu, hi[0]}, xv, gx, kv, C_phi, tau, X, KA, yv);
+            emi_facet_ring<1>(K, flags, lw0 >> 16, CoordCoef{co, (vl1 >> 8) & 0xffu, hi[1]}, xv, gx, kv, C_phi, tau, X, KA, yv);
+            emi_facet_ring<2>(K, flags, lw1 & 0xffffu, CoordCoef{co, (vl1 >> 16) & 0xffu, hi[2]}, xv, gx, kv, C_phi, tau, X, KA, yv);
+            emi_facet_ring<3>(K, flags, lw1 >> 16, CoordCoef{co, vl1 >> 24, hi[3]}, xv, gx, kv, C_phi, tau, X, KA, yv);
             store_nodal<3>(yout, c, yv);
         }
         ring_barrier();                                                // the loaders refill this slot in their next interval
@@ -291,64 +180,8 @@ __global__ __launch_bounds__(RB + 64 * ULOADERS) void k_emi_apply_ring_u(MeshDev
 }
 
 // ================================================================================================================================
-// KNP:  y_k = A_k x_k for all solved species (forms and notation: apply_p1.hip, k_knp_apply_halo; arithmetic of knp_facet_ring)
+// KNP:  y_k = A_k x_k for all solved species (forms and notation: apply_p1.hip, k_knp_apply_halo; arithmetic: ring_facet.hpp)
 // ================================================================================================================================
-template <int NS, int I>
-__device__ __forceinline__ void knp_facet_u(const CellGeom<3>& K, uint32_t flags, unsigned loc, unsigned vapex, double hinv, unsigned dsel,
-                                            const double (*xv)[4], const double (*gx)[4], const double* gp, const double* Dk, const double* hvD,
-                                            const double* zpsi, double tau, const lds_double* X, const lds_double* G, const lds_double* sD,
-                                            const lds_double* co, double (*y)[4]) {
-    constexpr int D = 3, NV = 4;
-    const uint32_t fb = (flags >> (8 * I)) & 0xffu;
-    if (((fb >> 2) & 3u) != FK_SIPG) return;
-    const unsigned j = fb & 3u;
-    FacetCoef fc;
-    facet_coef<I>(K, co, vapex, hinv, fc);
-    double gp_nb;
-    {   // the 16-byte half that holds component j of the neighbour's gphi row: own rows (swizzled image) or the halo's [entry][2]
-        typedef double __attribute__((ext_vector_type(2))) vdouble2;
-        typedef __attribute__((address_space(3))) vdouble2 lds_vdouble2;
-        const unsigned idx = loc < (unsigned)RB ? loc * NV + 2u * (((j >> 1) ^ (loc >> 3)) & 1u) : (unsigned)(RB * NV) + (loc - RB) * 2u;
-        const vdouble2 g2 = *(const lds_vdouble2*)(G + idx);
-        gp_nb = (j & 1u) ? g2.y : g2.x;
-    }
-    const double DV = (double)D * K.vol;
-    const double up_own = fmax(-gp[I], 0.0) * DV;
-    const double up_nb = fmax(-gp_nb, 0.0) * fc.nLI_DV;
-    const double penA = tau * fc.pen_geo;
-    const double hv = 0.5 * K.vol;
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        double xr[NV], xf[D];
-        lds_row(X + (unsigned)k * (UENT * NV), loc, xr);
-        const double xap = pick_apex<D>(xr, (int)j);
-#pragma unroll
-        for (int mm = 0; mm < D; ++mm) xf[mm] = pick_facet<D>(xr, mm, (int)j);
-        const double Dn = sD[(unsigned)k * KNP_MAX_MAT + dsel];
-        const double s_own = gx[k][I];
-        double s_nb = xap * fc.gr;
-#pragma unroll
-        for (int mm = 0; mm < D; ++mm) s_nb = fma(xf[mm], fc.cf[mm], s_nb);
-        const double zp = zpsi[k];
-        const double c_own = Dk[k] * fma(-zp, up_own, penA);
-        const double c_nb = Dn * fma(-zp, up_nb, penA);
-        double sdu = 0.0, w[D], sw = 0.0;
-#pragma unroll
-        for (int mm = 0; mm < D; ++mm) {
-            const double xo = xv[k][mm + (mm >= I)];
-            sdu += xo - xf[mm];
-            w[mm] = fma(c_own, xo, -c_nb * xf[mm]);
-            sw += w[mm];
-        }
-        const double t1m = fma(FacetConst<D>::mass, sw, hv * fma(Dk[k], s_own, Dn * s_nb));
-        const double t2 = hvD[k] * sdu;
-#pragma unroll
-        for (int a = 0; a < NV; ++a) y[k][a] = fma(K.G[a][I], t2, y[k][a]);
-#pragma unroll
-        for (int mm = 0; mm < D; ++mm) y[k][mm + (mm >= I)] += fma(FacetConst<D>::mass, w[mm], t1m);
-    }
-}
-
 template <int NS>
 __global__ __launch_bounds__(RB + 64 * ULOADERS) void k_knp_apply_ring_u(MeshDev m, RingUTables T, const double* __restrict__ x,
                                                                        const double* __restrict__ gphi, double* __restrict__ yout, KnpArgs ka,
@@ -412,18 +245,7 @@ __global__ __launch_bounds__(RB + 64 * ULOADERS) void k_knp_apply_ring_u(MeshDev
                 }
             }
         };
-        list_dma(0); list_dma(1);
-        wait_vm<0>();
-        ring_barrier();                                                // A
-        data_dma(0);
-        wait_vm<0>();
-        ring_barrier();                                                // B
-        for (int64_t n = 0; w.blk(n) >= 0; ++n) {
-            list_dma(n + 2);
-            if (w.blk(n + 1) >= 0) data_dma(n + 1);
-            wait_vm<0>();
-            ring_barrier();
-        }
+        load_one_ahead_drained(w, list_dma, data_dma);
         return;
     }
     const unsigned t = threadIdx.x & (RB - 1);
@@ -431,7 +253,7 @@ __global__ __launch_bounds__(RB + 64 * ULOADERS) void k_knp_apply_ring_u(MeshDev
 #pragma unroll
     for (int k = 0; k < NS; ++k) zpsi[k] = ka.z[k] * ka.psi;
     ring_barrier();                                                    // A: material table staged
-    ring_barrier();                                                    // B
+    ring_barrier();                                                    // B, then one per block (load_one_ahead_drained)
     for (int64_t n = 0;; ++n) {
         const int64_t b = w.blk(n);
         if (b < 0) break;
@@ -448,14 +270,7 @@ __global__ __launch_bounds__(RB + 64 * ULOADERS) void k_knp_apply_ring_u(MeshDev
             const uint32_t nm = ((const lds_u32*)(slot + R::NM))[t];
             const unsigned mymat = ((const lds_u8*)(slot + R::MA))[t];
             CellGeom<3> K;
-            {
-                double Xc[4][3];
-                lds_vertex(co, vl0 & 0xffu, Xc[0]);
-                lds_vertex(co, (vl0 >> 8) & 0xffu, Xc[1]);
-                lds_vertex(co, (vl0 >> 16) & 0xffu, Xc[2]);
-                lds_vertex(co, vl0 >> 24, Xc[3]);
-                cell_geometry_from<3>(Xc, K);
-            }
+            cell_geometry_staged(co, vl0, K);
             double xv[NS][NV], y[NS][NV], gp[NV], hi[NV], Dk[NS], gx[NS][NV], hvD[NS];
             lds_row(G, t, gp);
             lds_row((const lds_double*)(slot + R::HI), t, hi);
@@ -463,29 +278,12 @@ __global__ __launch_bounds__(RB + 64 * ULOADERS) void k_knp_apply_ring_u(MeshDev
             for (int k = 0; k < NS; ++k) {
                 lds_row(X + k * (UENT * NV), t, xv[k]);
                 Dk[k] = sD[k * KNP_MAX_MAT + mymat];
-                hvD[k] = 0.5 * K.vol * Dk[k];
             }
-            const double mw = ka.inv_dt * K.vol / 20.0;
-#pragma unroll
-            for (int k = 0; k < NS; ++k) {
-                double sx = 0.0;
-#pragma unroll
-                for (int a = 0; a < NV; ++a) sx += xv[k][a];
-                const double drift = zpsi[k] * Dk[k] * K.vol * sx / (double)NV;
-                const double dv = Dk[k] * K.vol;
-#pragma unroll
-                for (int a = 0; a < NV; ++a) {
-                    double sacc = 0.0;
-#pragma unroll
-                    for (int bb = 0; bb < NV; ++bb) sacc = fma(xv[k][bb], K.G[bb][a], sacc);
-                    gx[k][a] = sacc;
-                    y[k][a] = fma(mw, sx + xv[k][a], fma(dv, sacc, drift * gp[a]));
-                }
-            }
-            knp_facet_u<NS, 0>(K, flags, lw0 & 0xffffu, vl1 & 0xffu, hi[0], nm & 0xffu, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, co, y);
-            knp_facet_u<NS, 1>(K, flags, lw0 >> 16, (vl1 >> 8) & 0xffu, hi[1], (nm >> 8) & 0xffu, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, co, y);
-            knp_facet_u<NS, 2>(K, flags, lw1 & 0xffffu, (vl1 >> 16) & 0xffu, hi[2], (nm >> 16) & 0xffu, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, co, y);
-            knp_facet_u<NS, 3>(K, flags, lw1 >> 16, vl1 >> 24, hi[3], nm >> 24, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, co, y);
+            knp_cell_term<NS>(K, xv, gp, Dk, zpsi, ka.inv_dt, gx, hvD, y);
+            knp_facet_ring<NS, 0, UENT * NV>(K, flags, lw0 & 0xffffu, CoordCoef{co, vl1 & 0xffu, hi[0]}, nm & 0xffu, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, y);
+            knp_facet_ring<NS, 1, UENT * NV>(K, flags, lw0 >> 16, CoordCoef{co, (vl1 >> 8) & 0xffu, hi[1]}, (nm >> 8) & 0xffu, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, y);
+            knp_facet_ring<NS, 2, UENT * NV>(K, flags, lw1 & 0xffffu, CoordCoef{co, (vl1 >> 16) & 0xffu, hi[2]}, (nm >> 16) & 0xffu, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, y);
+            knp_facet_ring<NS, 3, UENT * NV>(K, flags, lw1 >> 16, CoordCoef{co, vl1 >> 24, hi[3]}, nm >> 24, xv, gx, gp, Dk, hvD, zpsi, ka.tau, X, G, sD, y);
 #pragma unroll
             for (int k = 0; k < NS; ++k) store_nodal<3>(yout + (int64_t)k * m.nc * NV, c, y[k]);
         }

@@ -157,7 +157,21 @@ template <int D> __device__ __forceinline__ void load_cell_geometry(const MeshDe
 typedef __attribute__((address_space(3))) double lds_double;   // explicit LDS pointers: ds_read, never flat_load
 typedef __attribute__((address_space(3))) char lds_char;
 typedef __attribute__((address_space(3))) int lds_int;
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+typedef __attribute__((address_space(3))) uint16_t lds_u16;
+typedef __attribute__((address_space(3))) uint8_t lds_u8;
 #define TO_LDS(p) ((const lds_double*)(p))
+
+// vol + Gram matrix out of a geometry-class record ([0] vol, then the upper triangle of G row by row: MeshDev::cls_table); Rec is a
+// pointer to doubles in LDS or in global memory
+template <int D, typename Rec> __device__ __forceinline__ void class_gram(Rec rec, CellGeom<D>& K) {
+    K.vol = rec[0];
+    int q = 1;
+#pragma unroll
+    for (int a = 0; a <= D; ++a)
+#pragma unroll
+        for (int b = a; b <= D; ++b) { K.G[a][b] = rec[q]; K.G[b][a] = rec[q]; ++q; }
+}
 
 template <int D> struct StageView {
     const lds_double* x;    // [nvalid][NV]      (per species: + k * xstride)

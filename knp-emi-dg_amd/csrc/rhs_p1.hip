@@ -47,16 +47,6 @@ template <int DEG> struct FacetRule<2, DEG> {       // degree 4 and 5 both need 
     }
 };
 
-// volume + Gram matrix of a geometry-class record ([0] vol, [1..10] upper triangle of G; 3D only)
-template <int D> __device__ __forceinline__ void class_gram(const double* __restrict__ rec, CellGeom<D>& K) {
-    K.vol = rec[0];
-    int q = 1;
-#pragma unroll
-    for (int a = 0; a <= D; ++a)
-#pragma unroll
-        for (int b = a; b <= D; ++b) { K.G[a][b] = rec[q]; K.G[b][a] = rec[q]; ++q; }
-}
-
 struct IonArgs {
     int n;                    // total species (last eliminated)
     double z[KNP_MAX_IONS];

@@ -53,6 +53,59 @@ struct RingWalk {
     }
 };
 
+// ---- loader schedules ------------------------------------------------------------------------------------------------------------
+// What the four loader waves of a workgroup run from start to end.  list_dma(n) issues the list piece(s) of the workgroup's n-th
+// block (a no-op past its last block and on every loader but the one that owns the lists), data_dma(n) issues this loader's share
+// of block n's records; every ring_barrier() below is met by one of the consumers, so the CONSUMERS' BARRIER COUNT is part of the
+// schedule -- a mismatch is a hang:
+//     A (lists 0 and 1 visible to every loader; the kernel's tables staged),  B (block 0 landed),  then one per interval.
+// Interval n is the one in which the consumers work on block n: nblk intervals for a workgroup with nblk blocks, nblk + 1 with a
+// closing interval.
+
+// One block ahead, every interval ends in a full drain (unstructured family: two slots, two list buffers).
+// Consumers: A, B, one barrier after each block = 2 + nblk.
+template <typename ListDma, typename DataDma>
+__device__ __forceinline__ void load_one_ahead_drained(const RingWalk& w, ListDma list_dma, DataDma data_dma) {
+    list_dma(0); list_dma(1);
+    wait_vm<0>();
+    ring_barrier();                                                    // A
+    data_dma(0);
+    wait_vm<0>();
+    ring_barrier();                                                    // B
+    for (int64_t n = 0; w.blk(n) >= 0; ++n) {
+        list_dma(n + 2);                                               // into the buffer block n's gathers read in the last interval
+        if (w.blk(n + 1) >= 0) data_dma(n + 1);
+        wait_vm<0>();
+        ring_barrier();
+    }
+}
+
+// Two blocks ahead (structured family: three or four slots, four list buffers).  N0..N3 = the DMA instructions of loaders 0..3 in
+// one data_dma: the counted wait of loader lw retires everything but its share of the youngest block (the list piece issued before
+// that share included) -- exactly the block the consumers need next -- and leaves the youngest in flight across the barrier.
+// Consumers: A, B, one barrier after each block = 2 + nblk; with CLOSING (the staggered EMI consumers, whose last interval holds
+// the second halves of the last block) one more = 3 + nblk.
+template <bool CLOSING, int N0, int N1, int N2, int N3, typename ListDma, typename DataDma>
+__device__ __forceinline__ void load_two_ahead_counted(const RingWalk& w, int lw, ListDma list_dma, DataDma data_dma) {
+    auto wait_older = [&]() {
+        if (lw == 0) wait_vm<N0>(); else if (lw == 1) wait_vm<N1>(); else if (lw == 2) wait_vm<N2>(); else wait_vm<N3>();
+    };
+    list_dma(0); list_dma(1);
+    wait_vm<0>();
+    ring_barrier();                                                    // A
+    data_dma(0);
+    list_dma(2);
+    if (w.blk(1) >= 0) { data_dma(1); wait_older(); } else wait_vm<0>();
+    ring_barrier();                                                    // B: block 0 and list 2 have landed
+    for (int64_t n = 0; w.blk(n) >= 0; ++n) {
+        list_dma(n + 3);
+        if (w.blk(n + 2) >= 0) { data_dma(n + 2); wait_older(); }      // block n + 2 stays in flight; list n + 3, block n + 1 have landed
+        else wait_vm<0>();
+        ring_barrier();
+    }
+    if (CLOSING) { wait_vm<0>(); ring_barrier(); }
+}
+
 // LDS image of a nodal vector: 32-byte rows, read by the consumers with 16-byte ds_read_b128 -- lanes that read consecutive rows
 // hit 16-byte bank groups (2 R + half) mod 16, i.e. rows 8 apart collide.  The two halves of every second group of 8 rows are
 // therefore stored SWAPPED (the DMA writes lane-linear, so the swap is made on the per-lane source address): conflict-free.

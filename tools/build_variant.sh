@@ -10,5 +10,5 @@ python knp-emi-dg_amd/build.py > /dev/null
 obj=/tmp/variant_${name}_${src%.hip}.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value $flags -c $csrc/$src -o $obj
 objs=$(ls $csrc/*.o | grep -v "/${src%.hip}.o")
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o knp-emi-dg_amd/knpemidg/libknpemi_hip_${name}.so $objs $obj -L/opt/rocm/lib -lrccl -lpthread -Wl,-rpath,/opt/rocm/lib
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o knp-emi-dg_amd/knpemidg/libknpemi_hip_${name}.so $objs $obj -L/opt/rocm/lib -lrccl -lhiprtc -lpthread -Wl,-rpath,/opt/rocm/lib
 echo knp-emi-dg_amd/knpemidg/libknpemi_hip_${name}.so
