@@ -1,705 +1,16 @@
 // C ABI of libknpemi_hip.so (see include/knpemi_hip.h for the contract and the reference
-// interfaces each entry point replaces).
+// interfaces each entry point replaces): the entry points that only pass on to a launcher, and the timing / bench helpers.
+// The context's life and setters are in context.hip, the two solves and their state in solve.hip.
 #include "../../include/knpemi_hip.h"
 #include "knpemi_internal.hpp"
-#include <chrono>
-#include <thread>
-#include <cstdio>
-#include <cstdlib>
 #include "krylov.hpp"
-#include <cstring>
-#include <unordered_map>
-#include <algorithm>
-#include <cmath>
-
-namespace {
-
-struct Fields {
-    double* f[KNP_F_COUNT] = {nullptr};
-    int64_t n[KNP_F_COUNT] = {0};
-    // solver workspace
-    bjreal *binv_emi = nullptr, *binv_knp = nullptr;
-    double *r = nullptr, *z = nullptr, *p = nullptr, *w = nullptr, *rhat = nullptr, *v = nullptr, *y = nullptr;
-    // previous converged solutions, for the extrapolated initial guess x0 = 2 x_{k-1} - x_{k-2}
-    double *hist_emi = nullptr, *hist_knp = nullptr;
-    int bj_age_emi = 0, bj_age_knp = 0;   // solves since the block-Jacobi inverses were rebuilt (lagged like the AMG hierarchy)
-    double* tmp_knp = nullptr;     // scratch of the Chebyshev block-Jacobi smoother
-    double bj_lmax_knp = 0.0;      // lambda_max(Binv A_knp) estimate (power iteration; redone after every reset of the lagged
-    int bj_lmax_age = 0;           // inverses, every 64 solves, and when the iteration count jumps by > 1.5x)
-    int it_ref_knp = 0, it_ref_emi = 0;   // iteration counts right after the last estimate
-    int bj_used_tab = -1;          // block set of the last KNP solve (1: drift-free class table, 0: per-cell inverses); a flip redoes the estimate
-    double* tmp_emi = nullptr;
-    double bj_lmax_emi = 0.0;
-    int bj_lmax_emi_age = 0;
-    int nh_emi = 0, nh_knp = 0;            // valid history entries of the extrapolated initial guesses
-    // KNP block-Jacobi table (structured meshes): 0 = not built yet, 1 = ready, -1 = unavailable for this context
-    int bj_tab_state = 0;
-    uint16_t* bj_idx = nullptr;            // [nc_owned]
-    bjreal* bj_tab = nullptr;              // [entries][n_sys][nd*nd]
-    int bj_entries = 0;
-    float* ivol = nullptr;                 // [nc] 1 / cell volume: weights of the residual norms of the stopping tests (krylov.hip)
-    double emi_r_abs = 0.0;                // knp_emi_residual_target: > 0 -> PCG stops on ||b - A phi||_w <= this
-};
-
-// initial guess from the last solutions: nh = number of valid history entries (h1 = previous, h2 = the one before)
-//   nh = 0: h1 <- x;   nh = 1 or order 1: x <- 2 x - h1;   nh = 2 and order 2: x <- 3 x - 3 h1 + h2;   then h2 <- h1 (if keep_h2), h1 <- x(old)
-// Order 1 never reads h2, so it is not written either (4 passes over the field instead of 5); KNP_FUSE_EXTRAP=0 writes it as before.
-__global__ void k_extrapolate_guess(int64_t n, int nh, int order, int keep_h2, double* __restrict__ x, double* __restrict__ h1,
-                                    double* __restrict__ h2) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double xv = x[i];
-    const double a = h1[i];
-    if (nh >= 2 && order >= 2) x[i] = 3.0 * (xv - a) + h2[i];
-    else if (nh >= 1) x[i] = 2.0 * xv - a;
-    if (keep_h2) h2[i] = a;
-    h1[i] = xv;
-}
-
-// The reference starts every Krylov solve from the previous time step's solution (KSP initial guess non-zero, solver.py:444, 701).
-// This path starts from an extrapolation of the last solutions instead (same converged solution, better starting point): linear
-// (2 x_{k-1} - x_{k-2}) by default; at r=2 over 20 steps through the stimulus onset KNP needs 7.4 instead of 9.05 BiCGStab iterations
-// per step and EMI 4.25 instead of 4.55 PCG iterations (-11 % per step).  KNP_EXTRAPOLATE=0 restores the reference's guess;
-// KNP_EXTRAPOLATE_ORDER=2 uses three solutions (quadratic).  A state upload invalidates the history.
-static int extrapolate_guess(knp_ctx* c, double* x, double** hist, int* nh, int64_t n, bool emi) {
-    // KNP_EXTRAPOLATE = 1: both solves, 2: EMI only, 3: KNP only
-    static const int mode = env_int("KNP_EXTRAPOLATE", 1);
-    // order 1: x0 = 2 x_{k-1} - x_{k-2}; order 2: x0 = 3 x_{k-1} - 3 x_{k-2} + x_{k-3}.  KNP_EXTRAPOLATE_ORDER sets both solves,
-    // KNP_EXTRAPOLATE_ORDER_KNP / _EMI one of them (r=2: order 2 costs the EMI solve 4.7 -> 7.0 iterations per step -- the potential
-    // jumps with the membrane currents -- and saves the KNP solve 0.45 of 5.05: profiles/r04_min_it.txt)
-    static const int order_all = env_int("KNP_EXTRAPOLATE_ORDER", 0);
-    static const int order_emi = env_int("KNP_EXTRAPOLATE_ORDER_EMI", (order_all ? order_all : 1));
-    static const int order_knp = env_int("KNP_EXTRAPOLATE_ORDER_KNP", (order_all ? order_all : 1));
-    const int order = emi ? order_emi : order_knp;
-    const bool on = mode == 1 || (mode == 2 && emi) || (mode == 3 && !emi);
-    if (!on || c->p.splitting == 2) return 0;
-    if (!*hist) HIPCHK(c, hipMalloc((void**)hist, sizeof(double) * 2 * n));
-    const char* fe = getenv("KNP_FUSE_EXTRAP");
-    const int keep_h2 = (order >= 2 || (fe && atoi(fe) == 0)) ? 1 : 0;
-    hipLaunchKernelGGL(k_extrapolate_guess, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, *nh, order, keep_h2, x, *hist,
-                       *hist + n);
-    HIPCHK(c, hipGetLastError());
-    if (*nh < 2) ++*nh;
-    return 0;
-}
-
-// everything that is lagged behind the coefficients: the block-Jacobi inverses AND the spectral bound of the Chebyshev
-// block-Jacobi smoother built on them (a stale / too small lambda_max makes the polynomial amplify the top modes)
-static void reset_lagged(Fields* f) {
-    f->bj_age_emi = f->bj_age_knp = 0;
-    f->bj_lmax_knp = f->bj_lmax_emi = 0.0;
-}
-
-std::map<knp_ctx*, Fields*> g_fields;
-thread_local std::string g_err;
-
-Fields* F(knp_ctx* c) { return g_fields[c]; }
-
-// KNP_DMA_PAD zero bytes follow every table: the ring-staged applies (apply_ring.hip) read whole 256-cell blocks of the per-cell
-// tables with 16-byte DMA granules, also where the last block runs past the end of the mesh
-#define KNP_DMA_PAD 4096
-template <typename T> int dev_alloc_copy(knp_ctx* c, T** dst, const T* src, size_t n) {
-    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-    HIPCHK(c, hipMalloc((void**)dst, bytes + KNP_DMA_PAD));
-    HIPCHK(c, hipMemset((char*)*dst + bytes, 0, KNP_DMA_PAD));
-    if (src && n) HIPCHK(c, host_memcpy(c, *dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
-template <typename T> int dev_zeros(knp_ctx* c, T** dst, size_t n) {
-    HIPCHK(c, hipMalloc((void**)dst, std::max<size_t>(n, 1) * sizeof(T)));
-    HIPCHK(c, hipMemset(*dst, 0, std::max<size_t>(n, 1) * sizeof(T)));
-    return 0;
-}
-
-}  // namespace
-
-double* knp_field_ptr(knp_ctx* c, int field, int64_t* n) {
-    if (!c || field < 0 || field >= KNP_F_COUNT) return nullptr;
-    if (n) *n = F(c)->n[field];
-    return F(c)->f[field];
-}
-
-void ode_destroy_all(knp_ctx* c);
-
-AmgHierarchy* amg_slot(knp_ctx* c, int which) {
-    if (which < 0 || which >= (int)c->amg.size()) return nullptr;
-    return &c->amg[which];
-}
-
-// contiguous chunks of [0, n) on a few host threads (the O(cells) table loops of knp_ctx_create: 0.6 s in one thread at 8 x 10^6 tets)
-template <typename F> static void host_chunks(int64_t n, F f) {
-    int nt = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    if (const char* ev = getenv("KNP_SETUP_THREADS")) nt = std::max(1, atoi(ev));
-    nt = std::min(nt, 64);                                             // callers keep per-thread results in 64 slots
-    if (n < (int64_t(1) << 16) || nt == 1) { f(0, n, 0); return; }
-    std::vector<std::thread> pool;
-    const int64_t chunk = (n + nt - 1) / nt;
-    for (int t = 0; t < nt; ++t) {
-        const int64_t lo = t * chunk, hi = std::min(n, lo + chunk);
-        if (lo >= hi) break;
-        pool.emplace_back([=]() { f(lo, hi, t); });
-    }
-    for (auto& th : pool) th.join();
-}
 
 extern "C" {
 
-const char* knp_last_error(knp_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
-
-int knp_ctx_create(knp_ctx** out, int device, int dim, int degree, int n_ions, int64_t nv, int64_t nc, int64_t nc_owned,
-                   int64_t nf, const double* coords, const int32_t* cells, const uint32_t* cell_tags,
-                   const int32_t* facet_cells, const int8_t* facet_local, const uint32_t* facet_tags, int n_membrane_tags,
-                   const uint32_t* membrane_tags) {
-    if (!out) return -1;
-    *out = nullptr;
-    if (dim != 2 && dim != 3) { g_err = "dim must be 2 or 3"; return -1; }
-    if (degree != 1 && degree != 2) { g_err = "degree must be 1 or 2"; return -1; }
-    if (n_ions < 2 || n_ions > KNP_MAX_IONS) { g_err = "n_ions out of range"; return -1; }
-    if (nc_owned < 0 || nc_owned > nc) { g_err = "nc_owned out of range"; return -1; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device visible"; return -5; }
-    if (device < 0 || device >= ndev) { g_err = "device index out of range"; return -5; }
-    // KNP_DEBUG_SETUP=1: wall-clock stamps of the stages below on stderr (next to the host-side stamps of knpemidg/_abi.py)
-    const bool stamps = env_int("KNP_DEBUG_SETUP", 0) == 1;
-    auto t_last = std::chrono::steady_clock::now();
-    auto stamp = [&](const char* what) {
-        if (!stamps) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[knp setup            +%6.3f] knp_ctx_create: %s\n", std::chrono::duration<double>(now - t_last).count(), what);
-        t_last = now;
-    };
-    knp_ctx* c = new knp_ctx();
-    c->device = device;
-    c->degree = degree;
-    c->p2_assembled = degree != 1 && env_int("KNP_P2_ASSEMBLED", 0) == 1;
-    const int NV = dim + 1;
-    const int ND = degree == 1 ? NV : NV * (NV + 1) / 2;      // P2: vertices, then edges (a,b), a<b, lexicographic
-    c->nd = ND;
-    c->p.n_ions = n_ions;
-    c->p.n_sys = n_ions - 1;
-    c->amg.resize(1 + (size_t)(n_ions - 1));
-    if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; delete c; return -5; }
-    if (hipStreamCreate(&c->stream) != hipSuccess) { g_err = "hipStreamCreate failed"; delete c; return -5; }
-    hipEventCreate(&c->ev0);
-    hipEventCreate(&c->ev1);
-    stamp("HIP runtime, stream");
-
-    // ---- host-side validation + derived tables ------------------------------------------------
-    {
-        int bad[64] = {0};
-        host_chunks(nc * NV, [&](int64_t lo, int64_t hi, int t) {
-            for (int64_t i = lo; i < hi; ++i)
-                if (cells[i] < 0 || cells[i] >= nv) bad[t & 63] = 1;
-        });
-        for (int b : bad)
-            if (b) { g_err = "cell vertex index out of range"; delete c; return -1; }
-    }
-    // NOTE: the facet matching relies on both cells of a facet listing the shared vertices in the same
-    // relative order (ascending ids in the caller's numbering); the ids themselves may be relabelled for
-    // storage locality, so they are not required to be ascending here.
-    std::vector<int32_t> nbr(nc * NV, -1), cfacet(nc * NV, -1);
-    std::vector<uint32_t> fflag(nc, 0);
-    std::vector<uint8_t> fb(nc * NV, (uint8_t)(FK_EXTERIOR << 2));
-    std::vector<int32_t> mf;
-    auto is_mem = [&](uint32_t t) {
-        for (int i = 0; i < n_membrane_tags; ++i) if (membrane_tags[i] == t) return true;
-        return false;
-    };
-    {
-        // facets in contiguous chunks: a (cell, local facet) entry belongs to exactly one facet, so the chunks write disjoint entries; the
-        // membrane facets of a chunk are collected per chunk and appended in chunk order = facet order
-        std::vector<std::vector<int32_t>> mf_part(64);
-        int bad[64] = {0};
-        host_chunks(nf, [&](int64_t flo, int64_t fhi, int tid) {
-            auto& mine = mf_part[(size_t)(tid & 63)];
-            for (int64_t f = flo; f < fhi; ++f) {
-                const int64_t c0 = facet_cells[2 * f], c1 = facet_cells[2 * f + 1];
-                const int l0 = facet_local[2 * f], l1 = facet_local[2 * f + 1];
-                if (c0 < 0 || c0 >= nc || l0 < 0 || l0 >= NV || c1 >= nc || (c1 >= 0 && (l1 < 0 || l1 >= NV))) { bad[tid & 63] = 1; continue; }
-                cfacet[c0 * NV + l0] = (int32_t)f;
-                if (c1 < 0) continue;
-                cfacet[c1 * NV + l1] = (int32_t)f;
-                const uint32_t t = facet_tags[f];
-                const uint32_t kind = (t == 0) ? FK_SIPG : (is_mem(t) ? FK_MEMBRANE : FK_INACTIVE);
-                // plus (normal-leaving, lower tag) side; on equal tags the reference takes n('-'), i.e. side 1
-                const int e_side = (cell_tags[c0] >= cell_tags[c1]) ? 1 : 0;
-                nbr[c0 * NV + l0] = (int32_t)c1;
-                nbr[c1 * NV + l1] = (int32_t)c0;
-                fb[c0 * NV + l0] = (uint8_t)((l1 & 3) | (kind << 2) | ((e_side == 0 ? 1u : 0u) << 4));
-                fb[c1 * NV + l1] = (uint8_t)((l0 & 3) | (kind << 2) | ((e_side == 1 ? 1u : 0u) << 4));
-                if (kind == FK_MEMBRANE) {
-                    const int64_t ce = e_side == 0 ? c0 : c1, ci = e_side == 0 ? c1 : c0;
-                    const int le = e_side == 0 ? l0 : l1, li = e_side == 0 ? l1 : l0;
-                    const int active = (ce < nc_owned || ci < nc_owned) ? 1 : 0;
-                    mine.insert(mine.end(), {(int32_t)ce, (int32_t)ci, le, li, (int32_t)f, active});
-                }
-            }
-        });
-        for (int b : bad)
-            if (b) { g_err = "facet table entry out of range"; delete c; return -1; }
-        for (auto& part : mf_part) mf.insert(mf.end(), part.begin(), part.end());
-        int missing[64] = {0};
-        host_chunks(nc, [&](int64_t lo, int64_t hi, int tid) {
-            for (int64_t k = lo; k < hi; ++k) {
-                uint32_t w = 0;
-                for (int a = 0; a < NV; ++a) {
-                    w |= (uint32_t)fb[k * NV + a] << (8 * a);
-                    if (k < nc_owned && cfacet[k * NV + a] < 0) missing[tid & 63] = 1;     // owned cells must have every neighbour present (one ghost layer)
-                }
-                fflag[k] = w;
-            }
-        });
-        for (int b : missing)
-            if (b) { g_err = "owned cell with a facet missing from the facet table"; delete c; return -1; }
-    }
-
-    stamp("facet flags, neighbours");
-    c->h_fflag = fflag;
-    c->h_mf_mask.assign((size_t)nf, 0);
-    for (size_t i = 0; i < mf.size(); i += 6) c->h_mf_mask[(size_t)mf[i + 4]] = 1;
-    MeshDev& m = c->m;
-    m.dim = dim; m.nv = nv; m.nc = nc; m.nc_owned = nc_owned; m.nf = nf; m.nmf = (int64_t)mf.size() / 6;
-    m.c_begin = 0; m.c_end = nc_owned; m.n_interior = nc_owned;
-    std::vector<double> cpad;
-    const double* csrc = coords;
-    size_t cstride = dim;
-    if (dim == 3) {
-        cpad.resize(nv * 4, 0.0);
-        for (int64_t v = 0; v < nv; ++v) for (int k = 0; k < 3; ++k) cpad[4 * v + k] = coords[3 * v + k];
-        csrc = cpad.data();
-        cstride = 4;
-    }
-    std::vector<double> hcell(nc, 0.0);
-    std::vector<float> ivol((size_t)nc, 1.0f);                             // 1 / cell volume (weights of the residual norms)
-    host_chunks(nc, [&](int64_t klo, int64_t khi, int) {
-    for (int64_t k = klo; k < khi; ++k) {
-        double h2 = 0.0;
-        for (int a = 0; a < NV; ++a)
-            for (int b = a + 1; b < NV; ++b) {
-                double d2 = 0.0;
-                for (int q = 0; q < dim; ++q) {
-                    const double d = coords[(int64_t)cells[k * NV + a] * dim + q] - coords[(int64_t)cells[k * NV + b] * dim + q];
-                    d2 += d * d;
-                }
-                h2 = std::max(h2, d2);
-            }
-        hcell[k] = std::sqrt(h2);
-        double e[3][3] = {{0.0}};
-        for (int a = 0; a < dim; ++a)
-            for (int q = 0; q < dim; ++q)
-                e[a][q] = coords[(int64_t)cells[k * NV + a + 1] * dim + q] - coords[(int64_t)cells[k * NV] * dim + q];
-        const double det = dim == 2 ? e[0][0] * e[1][1] - e[0][1] * e[1][0]
-                                    : e[0][0] * (e[1][1] * e[2][2] - e[1][2] * e[2][1]) - e[0][1] * (e[1][0] * e[2][2] - e[1][2] * e[2][0]) +
-                                      e[0][2] * (e[1][0] * e[2][1] - e[1][1] * e[2][0]);
-        const double vol = std::fabs(det) / (dim == 2 ? 2.0 : 6.0);
-        ivol[(size_t)k] = vol > 0.0 ? (float)(1.0 / vol) : 0.0f;
-    }
-    });
-    stamp("diameters, volumes");
-    int rc = 0;
-    rc |= dev_alloc_copy(c, &m.h, hcell.data(), hcell.size());
-    rc |= dev_alloc_copy(c, &m.coords, csrc, (size_t)nv * cstride);
-    rc |= dev_alloc_copy(c, &m.cells, cells, (size_t)nc * NV);
-    rc |= dev_alloc_copy(c, &m.nbr, nbr.data(), nbr.size());
-    rc |= dev_alloc_copy(c, &m.fflag, fflag.data(), fflag.size());
-    rc |= dev_alloc_copy(c, &m.cfacet, cfacet.data(), cfacet.size());
-    rc |= dev_alloc_copy(c, &m.mf, mf.data(), mf.size());
-    stamp("mesh tables on the device");
-    if (dim == 3 && degree == 1 && nc_owned > 0 && nc < (int64_t(1) << 29)) {
-        // halo- / ring-staged applies: per block of 256 consecutive cells, the coupled (SIPG or membrane: a_emi couples both) neighbours outside the block
-        const int64_t B = KNP_HALO_BLK, nblk = (nc_owned + B - 1) / B;
-        std::vector<int32_t> hcnt(nblk, 0);
-        std::vector<std::vector<int32_t>> lists((size_t)nblk);
-        std::vector<uint16_t> hloc((size_t)nc_owned * 4, 0);
-        int hmax = 0;
-        for (int64_t b = 0; b < nblk; ++b) {
-            auto& L = lists[(size_t)b];
-            for (int64_t k = b * B; k < std::min(nc_owned, (b + 1) * B); ++k)
-                for (int a = 0; a < 4; ++a) {
-                    const uint32_t kind = (fb[k * 4 + a] >> 2) & 3u;
-                    const int64_t nbk = nbr[k * 4 + a];
-                    if ((kind != FK_SIPG && kind != FK_MEMBRANE) || nbk < 0) continue;
-                    if (nbk / B == b) { hloc[k * 4 + a] = (uint16_t)(nbk - b * B); continue; }
-                    hloc[k * 4 + a] = (uint16_t)(B + L.size());
-                    L.push_back((int32_t)(nbk * 4 + (fb[k * 4 + a] & 3u)));
-                }
-            hmax = std::max(hmax, (int)L.size());
-        }
-        // a partition's cells on the cut come last and sit in a plane: nearly all their neighbours are outside their block.  Blocks
-        // whose list does not fit one entry per thread are left to the LDS-staged kernel: the halo-staged one covers [0, hb_long0 * 256)
-        int64_t long0 = nblk;
-        for (int64_t b = 0; b < nblk; ++b)
-            if ((int64_t)lists[(size_t)b].size() > B) { long0 = b; break; }
-        hmax = 0;
-        for (int64_t b = 0; b < long0; ++b) hmax = std::max(hmax, (int)lists[(size_t)b].size());
-        const int hs = ((hmax + 7) / 8) * 8;
-        if (hs > 0 && long0 > 0) {
-            std::vector<int32_t> hsrc((size_t)nblk * hs, -1);
-            for (int64_t b = 0; b < long0; ++b) std::copy(lists[(size_t)b].begin(), lists[(size_t)b].end(), hsrc.begin() + b * hs);
-            rc |= dev_alloc_copy(c, &m.hb_src, hsrc.data(), hsrc.size());
-            rc |= dev_alloc_copy(c, &m.hb_loc, hloc.data(), hloc.size());
-            rc |= dev_zeros(c, &c->halo_ctr, KNP_HALO_CTR_INTS);
-            m.hb_stride = hs;
-            m.hb_long0 = long0;
-        }
-    }
-    if (rc) { g_err = c->err; delete c; return -2; }
-    stamp("halo lists");
-
-    Fields* fl = new Fields();
-    const int64_t ndof = nc * ND, ns = c->p.n_sys;
-    const int64_t sizes[KNP_F_COUNT] = {ndof, ns * ndof, ns * ndof, ndof, nf, n_ions * nf, n_ions * nf, ndof, ndof,
-                                        ndof, ns * ndof, ns * ndof, ns * ndof, (int64_t)KNP_FACET_TMP_SLOTS * nf};
-    for (int i = 0; i < KNP_F_COUNT; ++i) {
-        fl->n[i] = sizes[i];
-        rc |= dev_zeros(c, &fl->f[i], sizes[i]);
-    }
-    rc |= dev_zeros(c, &fl->binv_emi, ndof * ND);
-    rc |= dev_zeros(c, &fl->binv_knp, ns * ndof * ND);
-    double** wk[] = {&fl->r, &fl->z, &fl->p, &fl->w, &fl->rhat, &fl->v, &fl->y};
-    for (auto pp : wk) rc |= dev_zeros(c, pp, ns * ndof);
-    rc |= dev_zeros(c, &c->D, (size_t)n_ions * nc);
-    rc |= dev_zeros(c, &c->rho, nc);
-    c->partial_blocks = grid_for(nc_owned) + 8;
-    rc |= dev_zeros(c, &c->partial, (size_t)c->partial_blocks * KNP_MAX_SYS * KNP_MAX_RED);
-    // the status block: status words | Krylov scalars, reduction results, GMRES state.  One allocation, so that a look is one copy
-    char* blk = nullptr;
-    rc |= dev_zeros(c, &blk, KNP_STATUS_BYTES + sizeof(double) * KNP_SCAL_DOUBLES);
-    c->status = (int*)blk;
-    c->scal = blk ? (double*)(blk + KNP_STATUS_BYTES) : nullptr;
-    if (!rc && hipHostMalloc(&c->pinned, KNP_PINNED_BYTES) != hipSuccess) rc = -2;
-    if (!rc) memset(c->pinned, 0, KNP_PINNED_BYTES);
-    if (rc) { g_err = "device allocation failed: " + c->err; delete fl; delete c; return -2; }
-    if (dev_alloc_copy(c, &fl->ivol, ivol.data(), ivol.size())) { g_err = "device allocation failed: " + c->err; delete fl; delete c; return -2; }
-    g_fields[c] = fl;
-    *out = c;
-    stamp("fields allocated");
-    return 0;
-}
-
-void knp_ctx_destroy(knp_ctx* c) {
-    if (!c) return;
-    hipSetDevice(c->device);
-    hipDeviceSynchronize();
-    for (auto& H : c->amg) amg_free(H);
-    for (auto st : c->aux_streams) hipStreamDestroy(st);
-    for (auto ev : c->aux_events) hipEventDestroy(ev);
-    if (c->fork_event) hipEventDestroy(c->fork_event);
-    ode_destroy_all(c);
-    rec_destroy(c);
-    state_destroy(c);
-    tab_free(c);
-    Fields* fl = g_fields[c];
-    if (fl) {
-        for (int i = 0; i < KNP_F_COUNT; ++i) hipFree(fl->f[i]);
-        hipFree(fl->binv_emi); hipFree(fl->binv_knp); hipFree(fl->bj_idx); hipFree(fl->bj_tab); hipFree(fl->ivol);
-        double* wk[] = {fl->r, fl->z, fl->p, fl->w, fl->rhat, fl->v, fl->y, fl->hist_emi, fl->hist_knp, fl->tmp_knp, fl->tmp_emi};
-        for (auto p : wk) hipFree(p);
-        delete fl;
-        g_fields.erase(c);
-    }
-    ring_u_free(c);
-    hipFree(c->m.hb_src); hipFree(c->m.hb_loc);
-    hipFree(c->m.cls); hipFree(c->m.cls_table); hipFree(c->m.cls_ext); hipFree(c->m.coords); hipFree(c->m.h); hipFree(c->m.cells); hipFree(c->m.nbr); hipFree(c->m.fflag); hipFree(c->m.cfacet); hipFree(c->m.mf);
-    hipFree(c->mat); hipFree(c->nmat4); hipFree(c->dtab); hipFree(c->halo_ctr);
-    hipFree(c->D); hipFree(c->rho); hipFree(c->fsrc); hipFree(c->mms_C); hipFree(c->extra_emi); hipFree(c->extra_knp); hipFree(c->partial); hipFree(c->status); /* c->scal: same allocation */ hipFree(c->gm_V);
-    hipFree(c->halo_send_idx); hipFree(c->halo_sendbuf);
-    if (c->pinned) hipHostFree(c->pinned);
-    if (c->ev0) hipEventDestroy(c->ev0);
-    if (c->ev1) hipEventDestroy(c->ev1);
-
-    for (int w = 0; w < 2; ++w)
-        for (auto& pr : c->tev[w]) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
-    comm_destroy(c);
-    if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
-}
-
-int knp_set_params(knp_ctx* c, double C_M, double dt, double Fc, double R, double T, double C_phi, double tau_emi,
-                   double tau_knp, const double* z, const double* D, const double* rho, const double* fsrc, int splitting) {
-    if (!c || !z || !D) return -1;
-    Params& p = c->p;
-    p.C_M = C_M; p.dt = dt; p.F = Fc; p.R = R; p.T = T; p.C_phi = C_phi; p.psi = Fc / (R * T);
-    p.tau_emi = tau_emi; p.tau_knp = tau_knp; p.splitting = splitting;
-    if (splitting == 2 && !c->mms_C) { c->err = "MMS mode needs knp_set_mms first"; return -1; }
-    if (g_fields.count(c)) reset_lagged(F(c));                               // new coefficients: rebuild the block-Jacobi inverses
-    for (int i = 0; i < p.n_ions; ++i) {
-        p.z[i] = z[i];
-        if (z[i] == 0.0) { c->err = "ion valence z must be non-zero"; return -1; }
-    }
-    if (!(dt > 0.0)) { c->err = "dt must be positive"; return -1; }
-    HIPCHK(c, host_memcpy(c, c->D, D, sizeof(double) * p.n_ions * c->m.nc, hipMemcpyHostToDevice));
-    if (g_fields.count(c)) F(c)->bj_tab_state = 0;                          // D / dt may have changed: rebuild the block-Jacobi table
-    {   // distinct D tuples over the cells (any dimension / degree): one of the keys of the KNP block-Jacobi table
-        const int64_t nc = c->m.nc;
-        const int ni = p.n_ions;
-        c->h_mat.assign((size_t)nc, 0);
-        std::vector<double> seen;                                           // [id][ni]
-        bool ok = true;
-        for (int64_t k = 0; k < nc && ok; ++k) {
-            const int nm = (int)(seen.size() / ni);
-            int id = -1;
-            for (int q = nm - 1; q >= 0 && id < 0; --q) {
-                bool same = true;
-                for (int i = 0; i < ni && same; ++i) same = seen[(size_t)q * ni + i] == D[(int64_t)i * nc + k];
-                if (same) id = q;
-            }
-            if (id < 0) {
-                if (nm >= 256) { ok = false; break; }
-                for (int i = 0; i < ni; ++i) seen.push_back(D[(int64_t)i * nc + k]);
-                id = nm;
-            }
-            c->h_mat[(size_t)k] = (uint16_t)id;
-        }
-        if (!ok) c->h_mat.clear();
-    }
-    c->nmat = 0;
-    if (c->m.dim == 3 && c->degree == 1 && c->m.hb_stride) {
-        // material ids: distinct coefficient tuples (D_0 .. D_{n_ions-1}) over the cells, in order of first appearance
-        const int64_t nc = c->m.nc;
-        const int ni = p.n_ions;
-        std::vector<uint8_t> mat((size_t)nc);
-        std::vector<double> tab((size_t)ni * KNP_MAX_MAT, 0.0);
-        int nm = 0;
-        bool ok = true;
-        for (int64_t k = 0; k < nc && ok; ++k) {
-            int id = -1;
-            for (int q = nm - 1; q >= 0 && id < 0; --q) {           // neighbours in the cell order mostly share the material: newest first
-                bool same = true;
-                for (int i = 0; i < ni && same; ++i) same = tab[(size_t)i * KNP_MAX_MAT + q] == D[(int64_t)i * nc + k];
-                if (same) id = q;
-            }
-            if (id < 0) {
-                if (nm == KNP_MAX_MAT) { ok = false; break; }
-                for (int i = 0; i < ni; ++i) tab[(size_t)i * KNP_MAX_MAT + nm] = D[(int64_t)i * nc + k];
-                id = nm++;
-            }
-            mat[k] = (uint8_t)id;
-        }
-        if (ok) {
-            if (!c->mat) { HIPCHK(c, hipMalloc((void**)&c->mat, (size_t)nc + KNP_DMA_PAD)); HIPCHK(c, hipMemset(c->mat, 0, (size_t)nc + KNP_DMA_PAD)); }
-            if (!c->nmat4) { HIPCHK(c, hipMalloc((void**)&c->nmat4, (size_t)nc * 4 + KNP_DMA_PAD)); HIPCHK(c, hipMemset(c->nmat4, 0, (size_t)nc * 4 + KNP_DMA_PAD)); }
-            if (!c->dtab) HIPCHK(c, hipMalloc((void**)&c->dtab, sizeof(double) * KNP_MAX_IONS * KNP_MAX_MAT));
-            HIPCHK(c, host_memcpy(c, c->mat, mat.data(), (size_t)nc, hipMemcpyHostToDevice));
-            HIPCHK(c, host_memcpy(c, c->dtab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
-            c->nmat = nm;
-            int rcm = launch_neighbour_materials(c);
-            if (rcm) return rcm;
-        }
-    }
-    if (rho) HIPCHK(c, host_memcpy(c, c->rho, rho, sizeof(double) * c->m.nc, hipMemcpyHostToDevice));
-    else HIPCHK(c, hipMemset(c->rho, 0, sizeof(double) * c->m.nc));
-    if (fsrc) {
-        if (!c->fsrc) HIPCHK(c, hipMalloc((void**)&c->fsrc, sizeof(double) * p.n_sys * c->m.nc));
-        HIPCHK(c, host_memcpy(c, c->fsrc, fsrc, sizeof(double) * p.n_sys * c->m.nc, hipMemcpyHostToDevice));
-    } else if (c->fsrc) {
-        hipFree(c->fsrc);
-        c->fsrc = nullptr;
-    }
-    return 0;
-}
-
-static int chk_field(knp_ctx* c, int field) {
-    if (!c) return -1;
-    if (field < 0 || field >= KNP_F_COUNT) { c->err = "unknown field id"; return -1; }
-    return 0;
-}
-
-int knp_set_geometry_classes(knp_ctx* c, int ncls, const uint16_t* cls, const double* table) {
-    if (!c) return -1;
-    hipFree(c->m.cls); hipFree(c->m.cls_table); hipFree(c->m.cls_ext);
-    c->m.cls = nullptr; c->m.cls_table = nullptr; c->m.cls_ext = nullptr; c->m.ncls = 0;
-    c->h_cls.clear();
-    if (g_fields.count(c)) F(c)->bj_tab_state = 0;
-    if (ncls <= 0) return 0;
-    if (ncls > 65535 || !cls || !table) { c->err = "geometry classes: bad arguments"; return -1; }
-    for (int64_t k = 0; k < c->m.nc; ++k)
-        if (cls[k] >= ncls) { c->err = "geometry class id out of range"; return -1; }
-    HIPCHK(c, hipMalloc((void**)&c->m.cls, sizeof(uint16_t) * c->m.nc + KNP_DMA_PAD));
-    HIPCHK(c, hipMemset(c->m.cls, 0, sizeof(uint16_t) * c->m.nc + KNP_DMA_PAD));
-    HIPCHK(c, host_memcpy(c, c->m.cls, cls, sizeof(uint16_t) * c->m.nc, hipMemcpyHostToDevice));
-    c->h_cls.assign(cls, cls + c->m.nc);
-    if (g_fields.count(c)) F(c)->bj_tab_state = 0;
-    HIPCHK(c, hipMalloc((void**)&c->m.cls_table, sizeof(double) * (size_t)ncls * KNP_CLS_STRIDE));
-    HIPCHK(c, host_memcpy(c, c->m.cls_table, table, sizeof(double) * (size_t)ncls * KNP_CLS_STRIDE, hipMemcpyHostToDevice));
-    // derived per-facet coefficients of the classed P1 applies, so that no lane recomputes what only depends on the class:
-    //   [8 i + 0] gr = G_ii / L_i          [8 i + 1..3] G_{a_m i} - L_{a_m} gr  (neighbour's gradient through the own basis, cell_geom.hpp)
-    //   [8 i + 4] (2 / (h + h')) sqrt(G_ii) D vol   [8 i + 5] -L_i D vol (the neighbour's D vol')   [8 i + 6] sqrt(G_ii) D vol   [8 i + 7] 0
-    std::vector<double> ext((size_t)ncls * KNP_CLS_EXT, 0.0);
-    for (int q = 0; q < ncls; ++q) {
-        const double* rec = table + (size_t)q * KNP_CLS_STRIDE;
-        double G[4][4];
-        int k = 1;
-        for (int a = 0; a < 4; ++a)
-            for (int b = a; b < 4; ++b) { G[a][b] = rec[k]; G[b][a] = rec[k]; ++k; }
-        const double DV = 3.0 * rec[0];
-        for (int i = 0; i < 4; ++i) {
-            const double* L = rec + 11 + 6 * i;
-            const double sqG = L[4], hinv = L[5];
-            double* e = ext.data() + (size_t)q * KNP_CLS_EXT + 8 * i;
-            if (L[i] != 0.0) {
-                const double gr = G[i][i] / L[i];
-                e[0] = gr;
-                for (int mm = 0; mm < 3; ++mm) { const int a = mm + (mm >= i); e[1 + mm] = G[a][i] - L[a] * gr; }
-            }
-            e[4] = hinv * sqG * DV;
-            e[5] = -L[i] * DV;
-            e[6] = sqG * DV;
-        }
-    }
-    hipFree(c->m.cls_ext); c->m.cls_ext = nullptr;
-    HIPCHK(c, hipMalloc((void**)&c->m.cls_ext, sizeof(double) * ext.size()));
-    HIPCHK(c, host_memcpy(c, c->m.cls_ext, ext.data(), sizeof(double) * ext.size(), hipMemcpyHostToDevice));
-    c->m.ncls = ncls;
-    return 0;
-}
-
-// Host-integrated load vector of the ion sources, int f_k v dx(0) (solver.py:599), for sources that are not constants: added to
-// L_knp by the right-hand-side kernels.  src[n_sys][nc*nd] in device cell order, or null to clear.  (The manufactured-solution
-// mode owns the same buffer: knp_set_mms.)
-int knp_set_source(knp_ctx* c, const double* src) {
-    if (!c) return -1;
-    if (c->p.splitting == 2) { c->err = "knp_set_source: the manufactured-solution mode sets its own data terms"; return -1; }
-    const int64_t n = (int64_t)c->p.n_sys * c->m.nc * c->nd;
-    if (!src) {
-        hipFree(c->extra_knp);
-        c->extra_knp = nullptr;
-        return 0;
-    }
-    if (!c->extra_knp) HIPCHK(c, hipMalloc((void**)&c->extra_knp, sizeof(double) * n));
-    HIPCHK(c, host_memcpy(c, c->extra_knp, src, sizeof(double) * n, hipMemcpyHostToDevice));
-    return 0;
-}
-
-int knp_set_mms(knp_ctx* c, const double* C, const double* extra_emi, const double* extra_knp) {
-    if (!c) return -1;
-    const int64_t ndof = c->m.nc * c->nd, ns = c->p.n_sys;
-    hipFree(c->mms_C); hipFree(c->extra_emi); hipFree(c->extra_knp);
-    c->mms_C = c->extra_emi = c->extra_knp = nullptr;
-    if (C) {
-        HIPCHK(c, hipMalloc((void**)&c->mms_C, sizeof(double) * ns * c->m.nc));
-        HIPCHK(c, host_memcpy(c, c->mms_C, C, sizeof(double) * ns * c->m.nc, hipMemcpyHostToDevice));
-    }
-    if (extra_emi) {
-        HIPCHK(c, hipMalloc((void**)&c->extra_emi, sizeof(double) * ndof));
-        HIPCHK(c, host_memcpy(c, c->extra_emi, extra_emi, sizeof(double) * ndof, hipMemcpyHostToDevice));
-    }
-    if (extra_knp) {
-        HIPCHK(c, hipMalloc((void**)&c->extra_knp, sizeof(double) * ns * ndof));
-        HIPCHK(c, host_memcpy(c, c->extra_knp, extra_knp, sizeof(double) * ns * ndof, hipMemcpyHostToDevice));
-    }
-    return 0;
-}
-
-int64_t knp_field_size(knp_ctx* c, int field) { return chk_field(c, field) ? -1 : F(c)->n[field]; }
-
-static int64_t debug_table_ptr(knp_ctx* c, int which, const void** p) {
-    const MeshDev& m = c->m;
-    const int64_t NV = m.dim + 1;
-    const int64_t nblk = (m.nc_owned + KNP_HALO_BLK - 1) / KNP_HALO_BLK;
-    switch (which) {
-        case KNP_DT_CELLS: *p = m.cells; return m.nc * NV * 4;
-        case KNP_DT_NBR: *p = m.nbr; return m.nc * NV * 4;
-        case KNP_DT_FLAG: *p = m.fflag; return m.nc * 4;
-        case KNP_DT_CFACET: *p = m.cfacet; return m.nc * NV * 4;
-        case KNP_DT_MF: *p = m.mf; return m.nmf * 6 * 4;
-        case KNP_DT_HB_SRC: *p = m.hb_src; return m.hb_src ? nblk * m.hb_stride * 4 : 0;
-        case KNP_DT_HB_LOC: *p = m.hb_loc; return m.hb_loc ? m.nc_owned * 4 * 2 : 0;
-        case KNP_DT_META: *p = nullptr; return 8 * 8;
-        default: return -1;
-    }
-}
-int64_t knp_debug_table_size(knp_ctx* c, int which) {
-    const void* p = nullptr;
-    return c ? debug_table_ptr(c, which, &p) : -1;
-}
-int knp_debug_table(knp_ctx* c, int which, void* out, int64_t nbytes) {
-    if (!c) return -1;
-    const void* p = nullptr;
-    const int64_t n = debug_table_ptr(c, which, &p);
-    if (n < 0 || nbytes != n || (n && !out)) { c->err = "debug_table: unknown table or size mismatch"; return -1; }
-    if (which == KNP_DT_META) {
-        const int64_t meta[8] = {c->m.nc, c->m.nc_owned, c->m.nf, c->m.nmf, c->m.hb_stride, c->m.hb_long0, c->m.n_interior, c->m.dim};
-        memcpy(out, meta, sizeof(meta));
-        return 0;
-    }
-    if (n) HIPCHK(c, host_memcpy(c, out, p, (size_t)n, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int knp_upload(knp_ctx* c, int field, const double* src, int64_t offset, int64_t count) {
-    if (chk_field(c, field)) return -1;
-    if (offset < 0 || count < 0 || offset + count > F(c)->n[field]) { c->err = "upload range out of bounds"; return -1; }
-    HIPCHK(c, hipMemcpyAsync(F(c)->f[field] + offset, src, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, host_stream_sync(c, c->stream));
-    // a caller-supplied state may be far from the one the lagged block-Jacobi inverses were built for
-    if (field == KNP_F_C || field == KNP_F_C_ELIM || field == KNP_F_PHI || field == KNP_F_KAPPA) reset_lagged(F(c));
-    if (field == KNP_F_PHI) { F(c)->nh_emi = 0; c->last_peclet = -1.0f; }   // a caller-supplied state is not a point of the solution history
-    if (field == KNP_F_C) F(c)->nh_knp = 0;
-    return 0;
-}
-
-int knp_download(knp_ctx* c, int field, double* dst, int64_t offset, int64_t count) {
-    if (chk_field(c, field)) return -1;
-    if (offset < 0 || count < 0 || offset + count > F(c)->n[field]) { c->err = "download range out of bounds"; return -1; }
-    HIPCHK(c, hipMemcpyAsync(dst, F(c)->f[field] + offset, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, host_stream_sync(c, c->stream));
-    return 0;
-}
-
-int knp_copy_field(knp_ctx* c, int dst, int src) {
-    if (chk_field(c, dst) || chk_field(c, src)) return -1;
-    if (F(c)->n[dst] != F(c)->n[src]) { c->err = "copy_field: size mismatch"; return -1; }
-    HIPCHK(c, hipMemcpyAsync(F(c)->f[dst], F(c)->f[src], sizeof(double) * F(c)->n[src], hipMemcpyDeviceToDevice, c->stream));
-    return 0;
-}
-
 int knp_update_kappa(knp_ctx* c) {
     if (!c) return -1;
-    Fields* f = F(c);
+    Fields* f = &c->fields;
     return launch_kappa(c, f->f[KNP_F_C], f->f[KNP_F_C_ELIM], f->f[KNP_F_KAPPA]);
-}
-
-// cell Peclet number of the drift term, max over the owned cells of  psi max|z| (max - min nodal phi): decides whether the
-// drift-free block-Jacobi table is a good preconditioner (build_bj_table).  Written as float bits into a status word that travels
-// with the solvers' status polls -- no synchronisation of its own.
-__global__ void k_cell_peclet(int64_t nc_owned, int nd, const double* __restrict__ phi, double scale, int* __restrict__ out) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    float pe = 0.0f;
-    if (c < nc_owned) {
-        double lo = phi[c * nd], hi = lo;
-        for (int a = 1; a < nd; ++a) { const double v = phi[c * nd + a]; lo = fmin(lo, v); hi = fmax(hi, v); }
-        pe = (float)(scale * (hi - lo));
-        if (!(pe >= 0.0f)) pe = 3.0e38f;                                     // NaN / inf potentials: never trust the table
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) pe = fmaxf(pe, __shfl_down(pe, off, 64));
-    __shared__ float s_pe[4];
-    if ((threadIdx.x & 63) == 0) s_pe[threadIdx.x >> 6] = pe;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        pe = fmaxf(fmaxf(s_pe[0], s_pe[1]), fmaxf(s_pe[2], s_pe[3]));
-        // one atomic per workgroup, and only when it would raise the value: atomics on one line retire at ~13 ns chip-wide (one per wave
-        // cost 180 us at r=2); non-negative floats order like their bit patterns
-        const int bits = __float_as_int(pe);
-        if (bits > __atomic_load_n(out, __ATOMIC_RELAXED)) atomicMax(out, bits);
-    }
-}
-
-int knp_update_dnphi(knp_ctx* c) {
-    if (!c) return -1;
-    Fields* f = F(c);
-    double zmax = 0.0;
-    for (int i = 0; i < c->p.n_sys; ++i) zmax = std::max(zmax, std::fabs(c->p.z[i]));
-    HIPCHK(c, hipMemsetAsync(c->status + KNP_PECLET_SLOT, 0, sizeof(int), c->stream));
-    if (c->m.nc_owned)
-        hipLaunchKernelGGL(k_cell_peclet, dim3((unsigned)((c->m.nc_owned + 255) / 256)), dim3(256), 0, c->stream, c->m.nc_owned, c->nd,
-                           (const double*)f->f[KNP_F_PHI], c->p.psi * zmax, c->status + KNP_PECLET_SLOT);
-    HIPCHK(c, hipGetLastError());
-    // partitioned runs: the max over ALL ranks, so that every rank of a solve applies the same preconditioner blocks (knp_knp_solve)
-    if (c->dist) { int rc = allreduce_max_word(c, c->status + KNP_PECLET_SLOT); if (rc) return rc; }
-    return launch_dnphi(c, f->f[KNP_F_PHI], f->f[KNP_F_DNPHI]);
 }
 
 int knp_allreduce_sum(knp_ctx* c, double* values, int n) {
@@ -710,301 +21,61 @@ int knp_allreduce_sum(knp_ctx* c, double* values, int n) {
 static int chk_vec(knp_ctx* c, int fx, int fy, int64_t need) {
     if (chk_field(c, fx) || chk_field(c, fy)) return -1;
     if (fx == fy) { c->err = "apply: input and output fields must differ"; return -1; }
-    if (F(c)->n[fx] < need || F(c)->n[fy] < need) { c->err = "apply: field too small for this operator"; return -1; }
+    if (c->fields.n[fx] < need || c->fields.n[fy] < need) { c->err = "apply: field too small for this operator"; return -1; }
     return 0;
 }
 
 int knp_emi_apply(knp_ctx* c, int fx, int fy) {
     if (!c) return -1;
     if (chk_vec(c, fx, fy, c->m.nc * c->nd)) return -1;
-    Fields* f = F(c);
+    Fields* f = &c->fields;
     return dist_apply(c, 0, f->f[fx], f->f[KNP_F_KAPPA], f->f[fy]);
 }
 
 int knp_knp_apply(knp_ctx* c, int fx, int fy) {
     if (!c) return -1;
     if (chk_vec(c, fx, fy, (int64_t)c->p.n_sys * c->m.nc * c->nd)) return -1;
-    Fields* f = F(c);
+    Fields* f = &c->fields;
     return dist_apply(c, 1, f->f[fx], f->f[KNP_F_DNPHI], f->f[fy]);
 }
 
 int knp_emi_rhs(knp_ctx* c) {
     if (!c) return -1;
-    Fields* f = F(c);
+    Fields* f = &c->fields;
     return launch_emi_rhs(c, f->f[KNP_F_C], f->f[KNP_F_C_ELIM], f->f[KNP_F_PHI_M], f->f[KNP_F_I_CH], f->f[KNP_F_B_EMI]);
 }
 
 int knp_knp_rhs(knp_ctx* c) {
     if (!c) return -1;
-    Fields* f = F(c);
+    Fields* f = &c->fields;
     return launch_knp_rhs(c, f->f[KNP_F_C], f->f[KNP_F_C_PREV], f->f[KNP_F_C_ELIM], f->f[KNP_F_PHI], f->f[KNP_F_PHI_M],
                           f->f[KNP_F_I_CH], f->f[KNP_F_B_KNP]);
 }
 
-// Error-controlled stop of the EMI solve (round 3; replaces the per-mesh factors on rtol_emi).  PCG stops when the residual b - A phi,
-// in the cell-volume-weighted norm ||r||_w^2 = sum_K |r_K|^2 / vol_K, falls below r_abs.  The caller derives r_abs from the accuracy it
-// wants for the CONCENTRATIONS: the potential enters the KNP step through the drift form int z_k psi D_k c_k grad(phi).grad(v), which
-// is alpha_k / (F z_k) times a_emi(phi, v) (kappa = F psi sum_j z_j^2 D_j c_j, alpha_k = z_k^2 D_k c_k / sum_j ... <= 1): an EMI residual
-// r perturbs the KNP load vector by alpha_k r / (F z_k), i.e. the concentrations by about |r| / (F |z_k| |b_knp,k|) relative
-// (b_knp,k ~ M c_k / dt, the KNP right-hand side).  r_abs = theta eps_c F min_k |z_k| ||b_knp,k||_w (knpemidg/solver.py).
-// 0 restores PETSc's test on the preconditioned norm (rtol, atol of knp_emi_solve).
-int knp_emi_residual_target(knp_ctx* c, double r_abs) {
-    if (!c || !(r_abs >= 0.0)) return -1;
-    F(c)->emi_r_abs = r_abs;
-    return 0;
-}
-
-int knp_knp_early_stop(knp_ctx* c, double factor) {
-    if (!c || !(factor >= 0.0) || factor >= 1.0) { if (c) c->err = "knp_knp_early_stop: factor must be in [0, 1)"; return -1; }
-    c->knp_early = factor;
-    return 0;
-}
-
-int knp_knp_load_measure(knp_ctx* c, double* out) {
-    if (!c || !out) return -1;
-    Fields* f = F(c);
-    const bool d8 = env_int("KNP_KNP_NORM2", 0) != 1;
-    return load_measure(c, f->f[KNP_F_B_KNP], f->ivol, d8, out);
-}
-
-int knp_emi_solve(knp_ctx* c, double rtol, double atol, int maxit, int check_every, int* niter, double* res) {
-    if (!c || !niter || !res) return -1;
-    Fields* f = F(c);
-    // the cell-block inverses only precondition: rebuilt every KNP_BJ_LAG-th solve (default 8; the coefficients move by < 1 %
-    // per step), like the lagged AMG hierarchy; 1 = every solve
-    static const int bj_lag = env_int("KNP_BJ_LAG", 8);
-    int rc = 0;
-    if (f->bj_age_emi % (bj_lag > 0 ? bj_lag : 1) == 0) rc = launch_emi_blockjacobi(c, f->f[KNP_F_KAPPA], f->binv_emi);
-    ++f->bj_age_emi;
-    if (rc) return rc;
-    if ((rc = extrapolate_guess(c, f->f[KNP_F_PHI], &f->hist_emi, &f->nh_emi, f->n[KNP_F_PHI], true))) return rc;
-    KrylovVecs kv{};
-    kv.x = f->f[KNP_F_PHI]; kv.b = f->f[KNP_F_B_EMI]; kv.coef = f->f[KNP_F_KAPPA]; kv.binv = f->binv_emi;
-    kv.ivol = f->ivol; kv.r_abs = f->emi_r_abs;
-    kv.d8 = env_int("KNP_KNP_NORM2", 0) != 1;   // the residual target is a density norm of order 8, like the KNP test
-    kv.r = f->r; kv.z = f->z; kv.p = f->p; kv.w = f->w; kv.rhat = f->rhat; kv.v = f->v; kv.y = f->y;
-    // the same two-step Chebyshev block-Jacobi smoother for EMI (KNP_EMI_CHEB=0 disables): at the effective tolerance the
-    // parity bounds need (rtol 2e-8, knpemidg/solver.py) it cuts the PCG iterations from 5.2 to 4.2 per step and the
-    // error of phi by 2x at equal tolerance (r=1, 40 steps through an action potential) for one more apply per iteration
-    static const int cheb_env_emi = env_int("KNP_EMI_CHEB", -1);
-    // Round 3: with the finest conforming level smoothed, the step no longer pays on large uniform meshes (r=2: 4.25 -> 4.7 iterations
-    // for 27 % less work per iteration, 7.35 -> 7.14 ms/step; r=3 48.9 -> 46.0) while small or badly shaped meshes still need it (EMIx:
-    // 9.2 -> 13.5 iterations): the host decides per mesh (knp_set_emi_dg_smoother; knpemidg/solver.py), the environment overrides
-    const int cheb_emi = cheb_env_emi >= 0 ? cheb_env_emi : (c->emi_dg_cheb >= 0 ? c->emi_dg_cheb : (c->degree == 1 ? 1 : 0));
-    if (cheb_emi && c->amg.size() && c->amg[0].ready) {
-        if (!f->tmp_emi) HIPCHK(c, hipMalloc((void**)&f->tmp_emi, sizeof(double) * f->n[KNP_F_PHI]));
-        kv.tmp = f->tmp_emi;
-        if (f->bj_lmax_emi <= 0.0 || ++f->bj_lmax_emi_age >= 64 || (f->it_ref_emi > 0 && 2 * c->last_it_emi > 3 * f->it_ref_emi + 2)) {
-            double lam = 0.0;
-            if ((rc = knp_bj_lambda_max(c, kv, 20, &lam, true))) return rc;
-            f->bj_lmax_emi = 1.1 * lam;
-            f->bj_lmax_emi_age = 0;
-            f->it_ref_emi = -1;
-            if (getenv("KNP_DEBUG")) fprintf(stderr, "[knp] lambda_max(Binv A_emi) ~ %.4f\n", lam);
-        }
-        kv.bj_lmax = f->bj_lmax_emi;
-    }
-    rc = pcg_solve(c, kv, rtol, atol, maxit, check_every, niter, res);
-    if (rc) return rc;
-    if (f->it_ref_emi < 0) f->it_ref_emi = c->last_it_emi;
-    if (c->dist) return halo_exchange(c, kv.x, 1);     // ghostUpdate (solver.py:529)
-    return 0;
-}
-
-// KNP block-Jacobi TABLE.  On a (block-)structured mesh the cell-diagonal block of A_knp without its drift part -- M / dt + the SIPG
-// volume, consistency and penalty terms of the cell's own D -- is decided by the cell's geometry class (own shape, neighbour
-// apexes and diameters), its material (D tuple) and the kinds of its facets: a few hundred distinct blocks for 10^6 cells.  The
-// Krylov vector kernels then read a 2-byte index per cell and the block through the caches instead of 4 nd^2 bytes per cell and
-// species from HBM (64 B against 32 B per cell vector for P1, 400 B against 80 B for P2: 18 % / 50 % of the bytes the fused BiCGStab
-// kernels move).  Dropping the drift from the PRECONDITIONER's blocks changes no iteration count (tools/precond_experiment.py:
-// the drift is 1e-3 of the operator at +-70 mV random nodal potentials), and the blocks no longer depend on the state: built once
-// per coefficient set instead of every 8th solve.  KNP_BJ_TABLE=0 keeps the per-cell inverses.
-__global__ void k_bj_gather(int nent, const int32_t* __restrict__ rep, int nsys, int64_t nc, int nn, const bjreal* __restrict__ binv,
-                            bjreal* __restrict__ tab) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)nent * nsys * nn) return;
-    const int e = (int)(i % nn), s = (int)((i / nn) % nsys), k = (int)(i / ((int64_t)nn * nsys));
-    tab[i] = binv[((int64_t)s * nc + rep[k]) * nn + e];
-}
-
-static int build_bj_table(knp_ctx* c, Fields* f) {
-    f->bj_tab_state = -1;
-    static const bool enabled = env_flag("KNP_BJ_TABLE", true);
-    const int64_t nc = c->m.nc, n_own = c->m.nc_owned;
-    if (!enabled || c->h_cls.size() != (size_t)nc || c->h_mat.size() != (size_t)nc || c->h_fflag.size() != (size_t)nc || c->p.splitting == 2 ||
-        c->p.n_sys > 4 || n_own == 0 || (c->degree != 1 && p2_assembled(c)))
-        return 0;
-    // key: class (16 bits) | material (8) | kind of each facet (4 x 2 bits)
-    std::unordered_map<uint64_t, int> ids;
-    std::vector<int32_t> rep;
-    std::vector<uint16_t> idx((size_t)n_own);
-    const int NVf = c->m.dim + 1;
-    for (int64_t k = 0; k < n_own; ++k) {
-        uint64_t kinds = 0;
-        for (int a = 0; a < NVf; ++a) kinds |= (uint64_t)((c->h_fflag[k] >> (8 * a + 2)) & 3u) << (2 * a);
-        const uint64_t key = (uint64_t)c->h_cls[k] | ((uint64_t)c->h_mat[k] << 16) | (kinds << 32);
-        auto it = ids.find(key);
-        if (it == ids.end()) {
-            if (rep.size() >= 8192) return 0;                                 // not structured enough: keep the per-cell inverses
-            it = ids.emplace(key, (int)rep.size()).first;
-            rep.push_back((int32_t)k);
-        }
-        idx[(size_t)k] = (uint16_t)it->second;
-    }
-    const int nn = c->nd * c->nd, ns = c->p.n_sys, nent = (int)rep.size();
-    // drift-free inverses of all cells (one launch of the kernel that builds the per-cell array), then the representatives' blocks
-    HIPCHK(c, hipMemsetAsync(f->w, 0, sizeof(double) * nc * c->nd, c->stream));
-    int rc = launch_knp_blockjacobi(c, f->w, f->binv_knp);
-    if (rc) return rc;
-    hipFree(f->bj_idx); hipFree(f->bj_tab);
-    f->bj_idx = nullptr; f->bj_tab = nullptr;
-    int32_t* drep = nullptr;
-    HIPCHK(c, hipMalloc((void**)&drep, sizeof(int32_t) * nent));
-    HIPCHK(c, hipMemcpyAsync(drep, rep.data(), sizeof(int32_t) * nent, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMalloc((void**)&f->bj_tab, sizeof(bjreal) * (size_t)nent * ns * nn));
-    HIPCHK(c, hipMalloc((void**)&f->bj_idx, sizeof(uint16_t) * (size_t)n_own));
-    HIPCHK(c, hipMemcpyAsync(f->bj_idx, idx.data(), sizeof(uint16_t) * (size_t)n_own, hipMemcpyHostToDevice, c->stream));
-    const int64_t tot = (int64_t)nent * ns * nn;
-    hipLaunchKernelGGL(k_bj_gather, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, nent, (const int32_t*)drep, ns, nc, nn,
-                       (const bjreal*)f->binv_knp, f->bj_tab);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, host_stream_sync(c, c->stream));
-    hipFree(drep);
-    f->bj_entries = nent;
-    f->bj_tab_state = 1;
-    if (getenv("KNP_DEBUG")) fprintf(stderr, "[knp] KNP block-Jacobi table: %d entries for %lld cells\n", nent, (long long)n_own);
-    return 0;
-}
-
-int knp_knp_solve(knp_ctx* c, double rtol, double atol, int maxit, int min_it, int check_every, int* niter, double* res) {
-    if (!c || !niter || !res) return -1;
-    Fields* f = F(c);
-    static const int bj_lag = env_int("KNP_BJ_LAG", 8);
-    int rc = 0;
-    if (f->bj_tab_state == 0 && (rc = build_bj_table(c, f))) return rc;
-    // the table ignores the drift: good while the potential varies little over a cell (psi |z| dphi << 1: 0.01-0.05 through an action
-    // potential on the reference's meshes), poor when the drift dominates (seeded random potentials of the tests: 5).  The cell
-    // Peclet number arrives with the status polls (knp_update_dnphi), i.e. one solve late; the first solve reads it itself.
-    static const double pe_limit = getenv("KNP_BJ_TABLE_PECLET") ? atof(getenv("KNP_BJ_TABLE_PECLET")) : 0.5;
-    bool use_tab = f->bj_tab_state == 1;
-    if (use_tab && c->last_peclet < 0.0f) {
-        int bits = 0;
-        HIPCHK(c, hipMemcpyAsync(&bits, c->status + KNP_PECLET_SLOT, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, host_stream_sync(c, c->stream));
-        memcpy(&c->last_peclet, &bits, sizeof(float));
-    }
-    if (use_tab && !(c->last_peclet <= pe_limit)) use_tab = false;
-    if ((int)use_tab != f->bj_used_tab) {         // another block set: its lambda_max and reference iteration count are not this one's
-        f->bj_lmax_knp = 0.0;
-        f->it_ref_knp = 0;
-        f->bj_used_tab = (int)use_tab;
-    }
-    if (use_tab) {
-        f->bj_age_knp = 0;                        // a later fall-back to the per-cell array starts with a rebuild (its content is the drift-free one)
-    } else {
-        if (f->bj_age_knp % (bj_lag > 0 ? bj_lag : 1) == 0) rc = launch_knp_blockjacobi(c, f->f[KNP_F_DNPHI], f->binv_knp);
-        ++f->bj_age_knp;
-    }
-    if (rc) return rc;
-    if ((rc = extrapolate_guess(c, f->f[KNP_F_C], &f->hist_knp, &f->nh_knp, f->n[KNP_F_C], false))) return rc;
-    KrylovVecs kv{};
-    kv.x = f->f[KNP_F_C]; kv.b = f->f[KNP_F_B_KNP]; kv.coef = f->f[KNP_F_DNPHI]; kv.binv = f->binv_knp;
-    if (use_tab) { kv.bj_idx = f->bj_idx; kv.bj_tab = f->bj_tab; }
-    kv.ivol = f->ivol;
-    // Stopping test on the order-8 norms of the residual / load densities (krylov.hip): the max-norm error of the concentrations was
-    // measured at 0.03-0.055 of that ratio on both mesh families, so  ratio <= KNP_D8_FACTOR * rtol  asks for an estimated max-norm
-    // error of about rtol (profiles/r03_knp_norms_*.txt).  KNP_KNP_NORM2=1: plain rtol on the cell-volume-weighted 2-norm instead.
-    // read per call, like knp_knp_load_measure and the EMI target: the load measure and this test must agree after an environment change
-    const bool d8 = env_int("KNP_KNP_NORM2", 0) != 1;
-    static const double d8_factor = getenv("KNP_D8_FACTOR") ? atof(getenv("KNP_D8_FACTOR")) : 20.0;
-    kv.d8 = d8;
-    if (d8) rtol *= d8_factor;
-    kv.r = f->r; kv.z = f->z; kv.p = f->p; kv.w = f->w; kv.rhat = f->rhat; kv.v = f->v; kv.y = f->y;
-    // DG-level smoother of the KNP preconditioner: two-step Chebyshev iteration on Binv A instead of one block-Jacobi
-    // application (one more operator apply per preconditioner application; BiCGStab iterations 14-20 -> 9-13 through an
-    // action potential at r=2, -10 % per step).  lambda_max(Binv A) comes from a power iteration at the first solve.
-    // Degree 1 only by default: the assembled P2 apply is 3x as expensive and the trade does not pay (21 -> 25 ms/step).
-    static const int cheb_env = env_int("KNP_KNP_CHEB", -1);
-    // (round 3, matrix-free P2 applies: with the step DG-P2 takes 8.1 -> 6.1 KNP iterations and steps 5 % faster at r=2, but 40 steps of
-    // the P2 configuration then end with 1.08e-6 in the concentrations against the 1e-6 bound: not enabled)
-    // (round 4: the step is on for DG-P2 too.  Round 3 had to keep it off because the EMI stop let more error through with better
-    // preconditioners; with the stops of round 4 the P2 configuration stays within c <= 1e-6 with it -- 6.8e-7 over 25 steps,
-    // profiles/r04_stop_sweep.txt -- and steps 6 % faster, KNP 7.4 -> 5.2 iterations)
-    const int cheb = cheb_env >= 0 ? cheb_env : 1;
-    if (cheb && c->p.n_sys <= 4) {
-        if (!f->tmp_knp) HIPCHK(c, hipMalloc((void**)&f->tmp_knp, sizeof(double) * f->n[KNP_F_C]));
-        kv.tmp = f->tmp_knp;
-        if (f->bj_lmax_knp <= 0.0 || ++f->bj_lmax_age >= 64 || (f->it_ref_knp > 0 && 2 * c->last_it_knp > 3 * f->it_ref_knp + 2)) {
-            double lam = 0.0;
-            if ((rc = knp_bj_lambda_max(c, kv, 20, &lam))) return rc;
-            f->bj_lmax_knp = 1.1 * lam;                 // the power iteration approaches lambda_max from below
-            f->bj_lmax_age = 0;
-            f->it_ref_knp = -1;
-            if (getenv("KNP_DEBUG")) fprintf(stderr, "[knp] lambda_max(Binv A_knp) ~ %.4f\n", lam);
-        }
-        kv.bj_lmax = f->bj_lmax_knp;
-    }
-    if (c->knp_krylov == 1) {
-        const int m = std::min(std::max(c->gm_restart, 2), KNP_GM_MAX);
-        if (c->gm_alloc < 2 * m + 1) {                    // basis V_0..V_m and its preconditioned image Z_0..Z_{m-1}
-            hipFree(c->gm_V); c->gm_V = nullptr; c->gm_alloc = 0;
-            HIPCHK(c, hipMalloc((void**)&c->gm_V, sizeof(double) * (size_t)(2 * m + 1) * f->n[KNP_F_C]));
-            c->gm_alloc = 2 * m + 1;
-        }
-        kv.gm_V = c->gm_V; kv.gm_m = m;
-        rc = gmres_solve(c, kv, rtol, atol, maxit, min_it, check_every, niter, res);
-    } else {
-        rc = bicgstab_solve(c, kv, rtol, atol, maxit, min_it, check_every, niter, res);
-    }
-    if (rc) return rc;
-    if (f->it_ref_knp < 0) f->it_ref_knp = c->last_it_knp;
-    if (c->dist) return halo_exchange(c, kv.x, c->p.n_sys);   // ghostUpdate (solver.py:789)
-    return 0;
-}
-
-int knp_set_knp_krylov(knp_ctx* c, int method, int restart) {
-    if (!c) return -1;
-    if (method != 0 && method != 1) { c->err = "knp_set_knp_krylov: method 0 (BiCGStab) or 1 (GMRES)"; return -1; }
-    if (method == 1 && (restart < 2 || restart > KNP_GM_MAX)) { c->err = "knp_set_knp_krylov: restart length 2.." + std::to_string(KNP_GM_MAX); return -1; }
-    c->knp_krylov = method;
-    if (method == 1) c->gm_restart = restart;
-    return 0;
-}
-
-int knp_set_emi_dg_smoother(knp_ctx* c, int chebyshev) {
-    if (!c) return -1;
-    if (chebyshev < -1 || chebyshev > 1) { c->err = "knp_set_emi_dg_smoother: -1 (default), 0 or 1"; return -1; }
-    if (chebyshev != c->emi_dg_cheb) F(c)->bj_lmax_emi = 0.0;       // (the bound is estimated at the next solve that needs it)
-    c->emi_dg_cheb = chebyshev;
-    return 0;
-}
-
 int knp_step_updates(knp_ctx* c) {
     if (!c) return -1;
-    Fields* f = F(c);
+    Fields* f = &c->fields;
     HIPCHK(c, hipMemcpyAsync(f->f[KNP_F_C_PREV], f->f[KNP_F_C], sizeof(double) * f->n[KNP_F_C], hipMemcpyDeviceToDevice, c->stream));
     return launch_step_updates(c, f->f[KNP_F_C], f->f[KNP_F_C_ELIM], f->f[KNP_F_PHI], f->f[KNP_F_PHI_M], f->f[KNP_F_E]);
 }
 
-
-
 // Picard level update (solver.py:882-910): C_ELIM and E from the current C; phi_M and C_PREV are left alone
 int knp_picard_updates(knp_ctx* c) {
     if (!c) return -1;
-    Fields* f = F(c);
+    Fields* f = &c->fields;
     return launch_step_updates(c, f->f[KNP_F_C], f->f[KNP_F_C_ELIM], nullptr, nullptr, f->f[KNP_F_E]);
 }
 
 int knp_max_abs_diff(knp_ctx* c, int fa, int fb, double* out) {
     if (chk_field(c, fa) || chk_field(c, fb) || !out) return -1;
     const int64_t ndof = c->m.nc * c->nd;
-    if (F(c)->n[fa] != F(c)->n[fb] || F(c)->n[fa] % ndof) { c->err = "max_abs_diff: nodal fields of equal size expected"; return -1; }
-    return max_abs_diff(c, F(c)->f[fa], F(c)->f[fb], (int)(F(c)->n[fa] / ndof), out);
+    if (c->fields.n[fa] != c->fields.n[fb] || c->fields.n[fa] % ndof) { c->err = "max_abs_diff: nodal fields of equal size expected"; return -1; }
+    return max_abs_diff(c, c->fields.f[fa], c->fields.f[fb], (int)(c->fields.n[fa] / ndof), out);
 }
 
 int knp_nernst(knp_ctx* c) {
     if (!c) return -1;
-    Fields* f = F(c);
+    Fields* f = &c->fields;
     return launch_nernst_only(c, f->f[KNP_F_C], f->f[KNP_F_C_ELIM], f->f[KNP_F_E]);
 }
 
@@ -1013,8 +84,8 @@ int knp_facet_trace(knp_ctx* c, int field, int species, int side, int slot) {
     if (side != 0 && side != 1) { c->err = "side must be 0 (plus) or 1 (minus)"; return -1; }
     if (slot < 0 || slot >= KNP_FACET_TMP_SLOTS) { c->err = "facet_trace: scratch slot out of range"; return -1; }
     const int64_t ndof = c->m.nc * c->nd;
-    if (species < 0 || (int64_t)(species + 1) * ndof > F(c)->n[field]) { c->err = "facet_trace: species out of range"; return -1; }
-    return launch_facet_trace(c, F(c)->f[field] + (int64_t)species * ndof, side, F(c)->f[KNP_F_FACET_TMP] + (int64_t)slot * c->m.nf);
+    if (species < 0 || (int64_t)(species + 1) * ndof > c->fields.n[field]) { c->err = "facet_trace: species out of range"; return -1; }
+    return launch_facet_trace(c, c->fields.f[field] + (int64_t)species * ndof, side, c->fields.f[KNP_F_FACET_TMP] + (int64_t)slot * c->m.nf);
 }
 
 int knp_sync(knp_ctx* c) {
@@ -1040,7 +111,7 @@ int knp_timer_end(knp_ctx* c, float* ms) {
 
 int knp_bench_apply(knp_ctx* c, int which, int reps, float* avg_ms) {
     if (!c || !avg_ms || reps < 1) return -1;
-    Fields* f = F(c);
+    Fields* f = &c->fields;
     int rc = 0;
     // three input / output pairs in rotation (X -> Y, r -> z, p -> w: 3 x the vectors of one apply), so that back-to-back
     // launches cannot be served from the 256 MiB Infinity Cache once the working set of ONE apply approaches it
@@ -1096,100 +167,12 @@ int knp_apply_timing_read(knp_ctx* c, int which, float* avg_ms, int* count) {
     return 0;
 }
 
-/* Owned cells [0, n_interior) of the device order have no ghost neighbour: with a communicator their part of an operator apply is
- * launched while the halo exchange of the input vector is in flight, the remaining owned cells after it (comm.hip: dist_apply). */
-int knp_set_interior(knp_ctx* c, int64_t n_interior) {
-    if (!c) return -1;
-    if (n_interior < 0 || n_interior > c->m.nc_owned) { c->err = "set_interior: out of range"; return -1; }
-    // every owned cell below n_interior must really be interior (checked once on the host copy of the neighbour table)
-    std::vector<int32_t> nbr((size_t)c->m.nc_owned * (c->m.dim + 1));
-    HIPCHK(c, host_memcpy(c, nbr.data(), c->m.nbr, sizeof(int32_t) * nbr.size(), hipMemcpyDeviceToHost));
-    for (int64_t k = 0; k < n_interior * (c->m.dim + 1); ++k)
-        if (nbr[k] >= c->m.nc_owned) { c->err = "set_interior: a cell below n_interior has a ghost neighbour"; return -1; }
-    c->m.n_interior = n_interior;
-    return 0;
-}
-
 int knp_halo_exchange(knp_ctx* c, int field) {
     if (chk_field(c, field)) return -1;
     const int64_t ndof = c->m.nc * c->nd;
-    if (F(c)->n[field] % ndof) { c->err = "halo_exchange: not a nodal field"; return -1; }
+    if (c->fields.n[field] % ndof) { c->err = "halo_exchange: not a nodal field"; return -1; }
     if (!c->dist) return 0;
-    return halo_exchange(c, F(c)->f[field], (int)(F(c)->n[field] / ndof));
+    return halo_exchange(c, c->fields.f[field], (int)(c->fields.n[field] / ndof));
 }
 
 }  // extern "C"
-
-// ---- checkpoint: the step-to-step state this file owns (state.hip packs it) ----------------------------------
-// Saved: the fields one step hands to the next, both solution histories with their counters, the LAGGED block-Jacobi inverses with
-// their ages and spectral bounds (rebuilt from the current coefficients they would differ from the ones the uninterrupted run still
-// applies), the reference iteration counts that trigger a new bound, last_peclet and the residual target.
-enum { SB_PHI = 1, SB_C, SB_C_PREV, SB_C_ELIM, SB_PHI_M, SB_I_CH, SB_E, SB_HIST_EMI, SB_HIST_KNP, SB_BINV_EMI, SB_BINV_KNP, SB_COUNTERS, SB_REALS };
-#define SB_N_COUNTERS 11
-#define SB_N_REALS 4
-
-static void fields_apply_host(knp_ctx* c, int id, const char* data) {
-    Fields* f = F(c);
-    if (id == SB_COUNTERS) {
-        int64_t v[SB_N_COUNTERS];
-        memcpy(v, data, sizeof(v));
-        f->nh_emi = (int)v[0]; f->nh_knp = (int)v[1]; f->bj_age_emi = (int)v[2]; f->bj_age_knp = (int)v[3];
-        f->bj_lmax_age = (int)v[4]; f->bj_lmax_emi_age = (int)v[5]; f->it_ref_knp = (int)v[6]; f->it_ref_emi = (int)v[7];
-        f->bj_used_tab = (int)v[8]; c->last_it_emi = (int)v[9]; c->last_it_knp = (int)v[10];
-    } else if (id == SB_REALS) {
-        double v[SB_N_REALS];
-        memcpy(v, data, sizeof(v));
-        f->bj_lmax_knp = v[0]; f->bj_lmax_emi = v[1]; f->emi_r_abs = v[2]; c->last_peclet = (float)v[3];
-    }
-}
-
-int fields_state_blocks(knp_ctx* c, std::vector<StateBlk>& out) {
-    Fields* f = F(c);
-    const int64_t nc = c->m.nc, nf = c->m.nf;
-    const int nd = c->nd, ns = c->p.n_sys, ni = c->p.n_ions;
-    // the histories are allocated by the first solve that extrapolates: a snapshot holds them always (zeros and a counter of 0 before)
-    if (!f->hist_emi) { HIPCHK(c, hipMalloc((void**)&f->hist_emi, sizeof(double) * 2 * f->n[KNP_F_PHI])); HIPCHK(c, hipMemset(f->hist_emi, 0, sizeof(double) * 2 * f->n[KNP_F_PHI])); }
-    if (!f->hist_knp) { HIPCHK(c, hipMalloc((void**)&f->hist_knp, sizeof(double) * 2 * f->n[KNP_F_C])); HIPCHK(c, hipMemset(f->hist_knp, 0, sizeof(double) * 2 * f->n[KNP_F_C])); }
-    auto cell = [&](int id, int type, int ncomp, int width, void* dev) {
-        StateBlk b; b.id = id; b.kind = KNP_SK_CELL_DOF; b.type = type; b.ncomp = ncomp; b.count = nc; b.width = width; b.dev = dev;
-        out.push_back(b);
-    };
-    auto facet = [&](int id, int ncomp, void* dev) {
-        StateBlk b; b.id = id; b.kind = KNP_SK_FACET; b.type = KNP_ST_F64; b.ncomp = ncomp; b.count = nf; b.width = 1; b.dev = dev;
-        out.push_back(b);
-    };
-    cell(SB_PHI, KNP_ST_F64, 1, nd, f->f[KNP_F_PHI]);
-    cell(SB_C, KNP_ST_F64, ns, nd, f->f[KNP_F_C]);
-    cell(SB_C_PREV, KNP_ST_F64, ns, nd, f->f[KNP_F_C_PREV]);
-    cell(SB_C_ELIM, KNP_ST_F64, 1, nd, f->f[KNP_F_C_ELIM]);
-    facet(SB_PHI_M, 1, f->f[KNP_F_PHI_M]);
-    facet(SB_I_CH, ni, f->f[KNP_F_I_CH]);
-    facet(SB_E, ni, f->f[KNP_F_E]);
-    cell(SB_HIST_EMI, KNP_ST_F64, 2, nd, f->hist_emi);
-    cell(SB_HIST_KNP, KNP_ST_F64, 2 * ns, nd, f->hist_knp);
-    cell(SB_BINV_EMI, KNP_ST_F32, 1, nd * nd, f->binv_emi);
-    cell(SB_BINV_KNP, KNP_ST_F32, ns, nd * nd, f->binv_knp);
-    {
-        const int64_t v[SB_N_COUNTERS] = {f->nh_emi, f->nh_knp, f->bj_age_emi, f->bj_age_knp, f->bj_lmax_age, f->bj_lmax_emi_age, f->it_ref_knp,
-                                          f->it_ref_emi, f->bj_used_tab, c->last_it_emi, c->last_it_knp};
-        StateBlk b; b.id = SB_COUNTERS; b.kind = KNP_SK_OPAQUE; b.type = KNP_ST_I64; b.apply = fields_apply_host;
-        state_push_host(b, v, SB_N_COUNTERS);
-        out.push_back(b);
-    }
-    {
-        const double v[SB_N_REALS] = {f->bj_lmax_knp, f->bj_lmax_emi, f->emi_r_abs, (double)c->last_peclet};
-        StateBlk b; b.id = SB_REALS; b.kind = KNP_SK_OPAQUE; b.type = KNP_ST_F64; b.apply = fields_apply_host;
-        state_push_host(b, v, SB_N_REALS);
-        out.push_back(b);
-    }
-    return 0;
-}
-
-// A fresh context builds the drift-free KNP block table inside its first solve and uses the per-cell inverse array as scratch for it:
-// done here instead, BEFORE the saved inverses are scattered over that array, so that the first solve after a load finds the table
-// ready and the lagged inverses as the interrupted run left them.
-int fields_state_prepare_load(knp_ctx* c) {
-    Fields* f = F(c);
-    if (f->bj_tab_state == 0) return build_bj_table(c, f);
-    return 0;
-}

@@ -697,7 +697,10 @@ void amg_free(AmgHierarchy& H) {
     H.ready = false;
 }
 
-AmgHierarchy* amg_slot(knp_ctx* c, int which);   // abi.hip
+static AmgHierarchy* amg_slot(knp_ctx* c, int which) {
+    if (which < 0 || which >= (int)c->amg.size()) return nullptr;
+    return &c->amg[which];
+}
 
 extern "C" {
 

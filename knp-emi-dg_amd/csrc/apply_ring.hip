@@ -62,7 +62,7 @@ template <int NS> struct KnpRing {
 };
 
 // per-cell topology bytes of a block, DMA'd by the loaders next to the nodal rows: flag bytes (4 B / cell), hb_loc (8 B), neighbour
-// materials (4 B), class (2 B), material (1 B).  The device arrays are padded by 4 KB (abi.hip), so whole blocks can be read past nc.
+// materials (4 B), class (2 B), material (1 B).  The device arrays are padded by 4 KB (context.hip), so whole blocks can be read past nc.
 struct CellMeta { uint32_t flags, nm; uint2 lw; unsigned cls, mymat; };
 __device__ __forceinline__ CellMeta read_meta(const char* meta, unsigned t, bool knp) {
     CellMeta q;

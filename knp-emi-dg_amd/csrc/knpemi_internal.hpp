@@ -8,6 +8,7 @@
 #include <type_traits>
 #include <vector>
 #include <map>
+#include "../../include/knpemi_hip.h"
 #include "amg.hpp"
 
 // block-Jacobi inverses are preconditioner data: stored in fp32 (half the bytes of the largest stream of the fused Krylov
@@ -22,7 +23,7 @@ typedef float bjreal;
 #define KNP_ODE_FAIL_SLOT (2 * KNP_MAX_SYS)   // word of knp_ctx::status raised by k_ode_step (read back with the solver status)
 #define KNP_PECLET_SLOT (2 * KNP_MAX_SYS + 1)     // bits of a float: max over the owned cells of psi max|z| (max - min nodal phi), set by knp_update_dnphi
 #define KNP_STATUS_WORDS (2 * KNP_MAX_SYS + 2)
-#define KNP_STATUS_BYTES (sizeof(int) * KNP_STATUS_WORDS)   // knp_ctx::scal starts this far into the status block (abi.hip)
+#define KNP_STATUS_BYTES (sizeof(int) * KNP_STATUS_WORDS)   // knp_ctx::scal starts this far into the status block (context.hip)
 #define KNP_PINNED_BYTES 4096
 
 // facet kinds stored in bits 2..3 of the per-(cell, local facet) flag byte
@@ -44,7 +45,7 @@ struct MeshDev {
     int32_t* mf = nullptr;         // [nmf][6]: cell_e, cell_i, lf_e, lf_i, facet, owner flag
     uint16_t* cls = nullptr;       // [nc] geometry class of every cell (structured meshes), or null
     double* cls_table = nullptr;   // [ncls][KNP_CLS_STRIDE]
-    double* cls_ext = nullptr;     // [ncls][KNP_CLS_EXT]: per facet 8 derived coefficients (abi.hip: knp_set_geometry_classes), read by the halo-staged KNP apply
+    double* cls_ext = nullptr;     // [ncls][KNP_CLS_EXT]: per facet 8 derived coefficients (context.hip: knp_set_geometry_classes), read by the halo-staged KNP apply
     int ncls = 0;
     // per-256-cell-block neighbour tables of the halo-staged applies (3D P1; blocks are aligned at multiples of 256 from cell 0)
     int32_t* hb_src = nullptr;     // [nblk][hb_stride]: 4 * neighbour cell + its local facet, one entry per coupled facet whose neighbour lies
@@ -84,6 +85,41 @@ struct KernelArgsIons {            // small by-value structs for kernels
     double z[KNP_MAX_IONS];
 };
 
+// What one linear system (EMI or KNP) keeps from solve to solve (solve.hip).  The inverses and the spectral bound lag behind the
+// coefficients; the history feeds the extrapolated initial guess.
+struct PrecState {
+    bjreal* binv = nullptr;        // per-cell block-Jacobi inverses, rebuilt every KNP_BJ_LAG-th solve (like the AMG hierarchy)
+    double* hist = nullptr;        // [2][n] previous converged solutions: x0 = 2 x_{k-1} - x_{k-2}; allocated by the first solve
+    int nh = 0;                    // valid history entries
+    int age = 0;                   // solves since the inverses were rebuilt
+    double* tmp = nullptr;         // scratch of the Chebyshev block-Jacobi smoother
+    double lmax = 0.0;             // lambda_max(Binv A) estimate (power iteration; redone after every reset of the lagged inverses,
+    int lmax_age = 0;              // every 64 solves, and when the iteration count jumps by > 1.5x)
+    int it_ref = 0;                // iteration count right after the last estimate
+};
+
+// the fields of the public ABI (knp_field) and the solver state of a context
+struct Fields {
+    double* f[KNP_F_COUNT] = {nullptr};
+    int64_t n[KNP_F_COUNT] = {0};
+    double *r = nullptr, *z = nullptr, *p = nullptr, *w = nullptr, *rhat = nullptr, *v = nullptr, *y = nullptr;   // Krylov work vectors
+    PrecState emi, knp;
+    int bj_used_tab = -1;          // block set of the last KNP solve (1: drift-free class table, 0: per-cell inverses); a flip redoes the estimate
+    // KNP block-Jacobi table (structured meshes): 0 = not built yet, 1 = ready, -1 = unavailable for this context
+    int bj_tab_state = 0;
+    uint16_t* bj_idx = nullptr;    // [nc_owned]
+    bjreal* bj_tab = nullptr;      // [entries][n_sys][nd*nd]
+    int bj_entries = 0;
+    float* ivol = nullptr;         // [nc] 1 / cell volume: weights of the residual norms of the stopping tests (krylov.hip)
+    double emi_r_abs = 0.0;        // knp_emi_residual_target: > 0 -> PCG stops on ||b - A phi||_w <= this
+    // everything that is lagged behind the coefficients: the block-Jacobi inverses AND the spectral bound of the Chebyshev
+    // block-Jacobi smoother built on them (a stale / too small lambda_max makes the polynomial amplify the top modes)
+    void reset_lagged() {
+        emi.age = knp.age = 0;
+        emi.lmax = knp.lmax = 0.0;
+    }
+};
+
 struct knp_ctx {
     int device = 0;
     int degree = 1;
@@ -100,7 +136,7 @@ struct knp_ctx {
     uint8_t* nmat4 = nullptr;      // [nc][4] material id of the neighbour behind every facet (3D)
     double* dtab = nullptr;        // [n_ions][KNP_MAX_MAT]
     int nmat = 0;
-    // host copies of what decides a cell's KNP block-Jacobi block on a structured mesh (abi.hip: build_bj_table): geometry class,
+    // host copies of what decides a cell's KNP block-Jacobi block on a structured mesh (solve.hip: build_bj_table): geometry class,
     // material (distinct D tuple, any count up to 65535; empty = too many), flag bytes (facet kinds)
     std::vector<uint16_t> h_cls, h_mat;
     std::vector<uint32_t> h_fflag;
@@ -172,6 +208,7 @@ struct knp_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> tev[2];   // [0] EMI, [1] KNP
     size_t tev_used[2] = {0, 0};
     std::string err;
+    Fields fields;
 };
 
 #define HIPCHK(ctx, call)                                                        \
@@ -208,6 +245,18 @@ inline hipError_t host_event_sync(knp_ctx* c, hipEvent_t e) { ++c->host_round_tr
 inline hipError_t host_memcpy(knp_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
     ++c->host_round_trips;
     return hipMemcpy(dst, src, bytes, kind);
+}
+
+inline int chk_field(knp_ctx* c, int field) {
+    if (!c) return -1;
+    if (field < 0 || field >= KNP_F_COUNT) { c->err = "unknown field id"; return -1; }
+    return 0;
+}
+// device array and length of a field of the public ABI, or null for an unknown id
+inline double* knp_field_ptr(knp_ctx* c, int field, int64_t* n) {
+    if (!c || field < 0 || field >= KNP_F_COUNT) return nullptr;
+    if (n) *n = c->fields.n[field];
+    return c->fields.f[field];
 }
 
 inline int64_t grid_for(int64_t n) { return (n + KNP_BLOCK - 1) / KNP_BLOCK; }
@@ -299,8 +348,8 @@ struct StateBlk {
     std::vector<char> host;                        // host values as they are now (what a save writes)
     void (*apply)(knp_ctx*, int id, const char* data) = nullptr;   // host values: takes a loaded block
 };
-int fields_state_blocks(knp_ctx* c, std::vector<StateBlk>& out);   // abi.hip: fields, solution histories, lagged inverses, counters
-int fields_state_prepare_load(knp_ctx* c);                         // abi.hip: builds what a first solve would build over restored arrays
+int fields_state_blocks(knp_ctx* c, std::vector<StateBlk>& out);   // solve.hip: fields, solution histories, lagged inverses, counters
+int fields_state_prepare_load(knp_ctx* c);                         // solve.hip: builds what a first solve would build over restored arrays
 int ode_state_blocks(knp_ctx* c, std::vector<StateBlk>& out);      // ode.hip: state / parameter tables and step sizes of every model
 int rec_state_blocks(knp_ctx* c, std::vector<StateBlk>& out);      // record.hip: ring, row counter, map accumulators
 void state_destroy(knp_ctx* c);                                    // state.hip: staging buffers of the context
@@ -309,6 +358,7 @@ template <typename T> inline void state_push_host(StateBlk& b, const T* v, int64
     b.host.assign((const char*)v, (const char*)v + sizeof(T) * (size_t)n);
 }
 
+void ode_destroy_all(knp_ctx* c);   // ode.hip: frees the context's membrane models and runtime-compiled kernels
 void rec_destroy(knp_ctx* c);       // record.hip: frees the context's time-series recorder, if any
 int ode_check_failed(knp_ctx* c);   // ode.hip: reads and clears the ODE failure flag (stream idle); sets c->err
 int status_look(knp_ctx* c);        // krylov.hip: head of the status block -> c->pinned, one copy and one stream wait

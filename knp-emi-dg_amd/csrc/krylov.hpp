@@ -34,7 +34,7 @@ template <typename T> struct GmState : GmLayout {        // T = double, or const
 // knp_ctx::scal: KS_N scalars per system | reduction results, KNP_MAX_RED per system (also the all-reduce scratch of comm.hip) | GMRES state
 #define KNP_RED_OFFSET (KNP_MAX_SYS * KS_N)
 #define KNP_GM_OFFSET (KNP_RED_OFFSET + KNP_MAX_SYS * KNP_MAX_RED)      // doubles in front of the GMRES state in knp_ctx::scal
-#define KNP_SCAL_DOUBLES (KNP_GM_OFFSET + KNP_MAX_SYS * KNP_GM_STRIDE)  // the allocation (abi.hip)
+#define KNP_SCAL_DOUBLES (KNP_GM_OFFSET + KNP_MAX_SYS * KNP_GM_STRIDE)  // the allocation (context.hip)
 static_assert(KNP_GM_STRIDE == 1056 && KNP_GM_OFFSET == KNP_MAX_SYS * (KS_N + KNP_MAX_RED) &&
               KNP_SCAL_DOUBLES == KNP_MAX_SYS * (KS_N + KNP_MAX_RED + GmLayout::SIZE), "regions of knp_ctx::scal");
 template <typename T> __host__ __device__ inline T* scal_row(T* scal, int s) { return scal + s * KS_N; }

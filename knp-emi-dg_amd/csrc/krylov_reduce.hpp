@@ -77,7 +77,7 @@ template <int NV> __device__ __forceinline__ void block_matvec(const bjreal* __r
 struct VecDims {
     int64_t nc_owned, nc;   // vectors are [nsys][nc*NV]; only owned cells are updated / reduced
     int nsys;
-    // block-Jacobi table (KNP on structured meshes, abi.hip: build_bj_table): the cell's inverse block is entry bj_idx[c] of a small
+    // block-Jacobi table (KNP on structured meshes, solve.hip: build_bj_table): the cell's inverse block is entry bj_idx[c] of a small
     // table instead of 4 NV^2 bytes per cell and species read from HBM in every vector kernel; null -> per-cell inverses
     const uint16_t* bj_idx;
     const bjreal* bj_tab;   // [n_entries][nsys][NV*NV]

@@ -233,8 +233,6 @@ __global__ void k_ode_exchange_multi(int64_t n, const int32_t* __restrict__ face
     }
 }
 
-double* knp_field_ptr(knp_ctx* c, int field, int64_t* n);   // abi.hip
-
 // `assert success` of membrane.py:113, deferred: knp_ode_step does not synchronise; the flag travels with the next status poll of
 // a solve (krylov.hip: poll_status), a table download or knp_sync.  Call with the stream idle.
 int ode_check_failed(knp_ctx* c) {

@@ -32,7 +32,6 @@
 #include <cmath>
 #include <cstring>
 
-double* knp_field_ptr(knp_ctx* c, int field, int64_t* n);   // abi.hip
 bool ode_state_table(knp_ctx* c, int handle, const double** states, int64_t* n, int* ns);   // ode.hip
 
 #define KNP_REC_MAX_REGIONS 16

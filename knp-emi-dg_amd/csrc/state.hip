@@ -1,6 +1,6 @@
 // Checkpoint of the step-to-step state: knp_state_describe / knp_state_save / knp_state_load (include/knpemi_hip.h).
 //
-// abi.hip, ode.hip and record.hip each list the state they own as blocks [ncomp][count][width] (knpemi_internal.hpp: StateBlk).  A
+// solve.hip, ode.hip and record.hip each list the state they own as blocks [ncomp][count][width] (knpemi_internal.hpp: StateBlk).  A
 // save packs every device block into one staging buffer -- per-cell blocks through the cell permutation, so that the snapshot is in
 // the caller's numbering whatever order the device keeps --, copies the staging buffer to pinned host memory in one transfer and
 // puts the prologue, the block table and the few host-side counters around it.  A load checks the table against the context's own

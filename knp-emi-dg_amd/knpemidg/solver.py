@@ -405,7 +405,7 @@ class Solver:
         sp = getattr(self, "solver_params", None)
         explicit = getattr(sp, "emi_dg_chebyshev", None)
         if explicit is None and os.environ.get("KNP_EMI_CHEB") is not None:
-            explicit = int(os.environ["KNP_EMI_CHEB"]) != 0                # the device reads the same variable as an override (csrc/abi.hip)
+            explicit = int(os.environ["KNP_EMI_CHEB"]) != 0                # the device reads the same variable as an override (csrc/solve.hip)
         self._emi_trial = None if explicit is not None else True
         recorded = (getattr(self, "_resume_header", None) or {}).get("emi_dg_chebyshev")
         if explicit is None and recorded is not None:
@@ -711,7 +711,7 @@ class Solver:
         # tools/tolerance_sweep.py / tools/tolerance_emix.py measure them.
         # ROUND 3: the per-mesh factors above are replaced by an error-controlled stop.  The EMI solve stops when its residual, in the
         # cell-volume-weighted norm, is small enough for the concentration accuracy wanted (knp_emi_residual_target,
-        # csrc/abi.hip): r_abs = theta * c_tol * F * min_k |z_k| ||b_knp,k||_w with c_tol = 0.1 * rtol_emi (the reference pairs
+        # csrc/solve.hip): r_abs = theta * c_tol * F * min_k |z_k| ||b_knp,k||_w with c_tol = 0.1 * rtol_emi (the reference pairs
         # rtol_emi 1e-5 with concentrations good to 1e-6) and ONE safety factor theta for every mesh family and degree
         # (EMI_TARGET_SAFETY below; measured: profiles/r03_error_controlled_stop.txt).  `emi_rtol_scale` in solver_params (or
         # KNP_EMI_RTOL_SCALE, tools only) selects the old preconditioned-norm test with that factor instead.
@@ -740,7 +740,7 @@ class Solver:
         kscale = float(ks) if ks is not None else 1.0
         rk = float(self.rtol_knp) if not self.direct_knp else 0.0
         # direct_knp (MUMPS in the reference) is emulated by a tightly converged solve: rtol_direct is meant for the residual itself, so the
-        # factor 20 the device puts on the order-8 density test (csrc/abi.hip: KNP_D8_FACTOR) is divided out here
+        # factor 20 the device puts on the order-8 density test (csrc/solve.hip: KNP_D8_FACTOR) is divided out here
         self._rtol_knp = float(getattr(sp, "rtol_direct", 1e-10)) / 20.0 if self.direct_knp else max(rk * kscale, min(rk, 1.0e-13))
         if self.verbose:
             print(" effective tolerances: EMI %s, KNP rtol %.2e (weighted residual norm)" % (

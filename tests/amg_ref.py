@@ -166,7 +166,7 @@ def _blocks(binv, r):
 
 
 def bj_lambda_max(As, binvs, bs, iters=20):
-    """krylov.hip: bj_lambda_max_impl (the systems are normalised together: max over the species), times the 1.1 of abi.hip"""
+    """krylov.hip: bj_lambda_max_impl (the systems are normalised together: max over the species), times the 1.1 of solve.hip"""
     v = [np.asarray(b, dtype=np.float64).copy() for b in bs]
     nv = max(np.abs(x).max() for x in v)
     lam = 0.0
@@ -459,7 +459,7 @@ class Host:
         return self._knp
 
     def peclet(self):
-        """abi.hip: k_cell_peclet -- above 0.5 the KNP solve uses the per-cell block inverses (drift included), as `knp` does"""
+        """solve.hip: k_cell_peclet -- above 0.5 the KNP solve uses the per-cell block inverses (drift included), as `knp` does"""
         zmax = max(abs(ion["z"]) for ion in self.pb.ions[:-1])
         return float(self.pb.psi * zmax * (self.pb.phi.max(axis=1) - self.pb.phi.min(axis=1)).max())
 

@@ -7,7 +7,7 @@ import numpy as np
 
 import knpemi_oracle as ko
 
-KNP_D8_FACTOR = 20.0            # abi.hip: knp_knp_solve scales rtol of the order-8 density test by this
+KNP_D8_FACTOR = 20.0            # solve.hip: knp_knp_solve scales rtol of the order-8 density test by this
 
 
 def _fsum(a):
@@ -20,7 +20,7 @@ class Ref:
     def __init__(self, pb):
         self.pb, self.nd = pb, pb.nd
         self.nc = pb.mesh.num_cells()
-        # 1 / vol stored in fp32 (abi.hip: knp_ctx_create, `ivol`)
+        # 1 / vol stored in fp32 (context.hip: knp_ctx_create, `ivol`)
         self.w = (1.0 / pb.geom.vol).astype(np.float32).astype(np.float64)
         self.A_emi, self.b_emi, _ = ko.assemble_emi(pb, want_B=False)
         self.A_emi = self.A_emi.tocsr()

@@ -88,7 +88,7 @@ def test_knp_early_stop_below_the_iteration_floor(case):
     dev.knp_early_stop(0.01)
     niter, res = dev.knp_solve(1e-6, maxit=100, min_it=5)
     assert all(n == 1 for n in niter), (niter, res)
-    assert np.all(res[:, 1] <= 0.01 * 20.0 * 1e-6 * res[:, 2])         # 20: the device's factor on the order-8 density test (csrc/abi.hip)
+    assert np.all(res[:, 1] <= 0.01 * 20.0 * 1e-6 * res[:, 2])         # 20: the device's factor on the order-8 density test (csrc/solve.hip)
     assert relerr(dev.download(A.F_C), c_ref) < 1e-9
     # not yet 100x under the tolerance after the first iteration: the solve goes on as before
     dev.upload(A.F_C, c_ref * (1.0 + 1e-3 * np.random.default_rng(8).uniform(-1.0, 1.0, size=c_ref.shape)))

@@ -1,7 +1,7 @@
 """Bit-exact parity of the connectivity / orientation tables (`north_star`: "bit-exact for DoF/connectivity indexing").
 
 The library derives its neighbour, flag (neighbour-local facet, integration class, plus-side bit), facet-id, membrane-facet and
-halo-block tables inside `knp_ctx_create` (csrc/abi.hip) from raw cells / tags -- the device counterpart of DOLFIN's facet
+halo-block tables inside `knp_ctx_create` (csrc/context.hip) from raw cells / tags -- the device counterpart of DOLFIN's facet
 topology, of the `dS(tag)` classification (reference: src/knpemidg/solver.py:113-121) and of `interface_normal` / `plus` /
 `minus` (reference: src/knpemidg/utils.py:61-98).  They are read back through `knp_debug_table` and compared ENTRY FOR ENTRY with
 the tables `oracle/connectivity.py` derives independently (dictionary matching of sorted vertex tuples in the caller's numbering,

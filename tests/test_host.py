@@ -147,6 +147,26 @@ def test_apply_plan_selects_the_asserted_kernel_families(tmp_path):
     assert run.returncode == 0 and "apply plan ok" in run.stdout, run.stdout
 
 
+def test_context_table_steps_on_the_host(tmp_path):
+    """csrc/context_tables.hpp holds the host steps of knp_ctx_create and knp_set_params (facet / neighbour tables, cell metrics,
+    halo block lists, material scan).  tools/check_context_tables.cpp, plain host C++ without a GPU call, runs them on the one-axon
+    box dumped by tools/dump_context_mesh.py and on 17 / 256 / 257 distinct coefficient tuples.  (The same program is what a host
+    sanitizer build runs: its header comment has the command line.)"""
+    import shutil
+    import subprocess
+    import sys
+    cxx = shutil.which(os.environ.get("CXX", "g++"))
+    rocm_inc = os.path.join(os.path.dirname(os.path.dirname(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))), "include")
+    if cxx is None or not os.path.exists(os.path.join(rocm_inc, "hip", "hip_runtime.h")):
+        pytest.skip("no host C++ compiler or no HIP headers")
+    mesh, exe = str(tmp_path / "small_3d.bin"), str(tmp_path / "check_context_tables")
+    subprocess.run([sys.executable, os.path.join(ROOT, "tools", "dump_context_mesh.py"), mesh], check=True)
+    subprocess.run([cxx, "-std=c++17", "-O1", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I", rocm_inc, "-I", os.path.join(ROOT, "knp-emi-dg_amd", "csrc"),
+                    os.path.join(ROOT, "tools", "check_context_tables.cpp"), "-o", exe], check=True)
+    run = subprocess.run([exe, mesh], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert run.returncode == 0 and "context tables ok" in run.stdout, run.stdout
+
+
 def test_product_never_imports_oracle():
     """The oracle is test infrastructure: nothing under knp-emi-dg_amd/ may import or execute it."""
     pkg = os.path.join(ROOT, "knp-emi-dg_amd")
