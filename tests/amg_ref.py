@@ -27,6 +27,17 @@ KERNELS = ("k_csr<0>", "k_csr<1>", "k_csr<2>", "k_csr_first", "k_cheb_first_res"
 MUTATIONS = ("no_round_A", "drop_tail", "swap_columns", "short_post_smooth", "no_prolongation", "dense_last_row")
 
 
+# ions of the KNP cases by number of solved species (None: the K / Cl / Na problem), and the cases the device runs on the drift-free
+# class table of solve.hip (tests/test_gpu_amg.py) -- (mesh, solved species, hierarchy or one per species, four materials) at the
+# potential TABLE_PHI_SCALE times the synthetic one; tests/test_amg_ref_host.py asserts that the replica supports every one of them
+IONS = {2: None, 3: ("K", "Cl", "X", "Na"), 4: ("K", "Cl", "X", "Y", "Na")}
+TABLE_PHI_SCALE = 0.05
+TABLE_CASES = (("box_P1", 2, "bands", False), ("box_P1", 2, "bands_t0", False), ("box_P1", 2, "coarse_257", False),
+               ("box_P1", 2, "bands", True), ("box_P1", 3, "bands", False), ("box_P1", 4, "bands", False),
+               ("box_P1", 2, ("bands", "mid"), True),
+               ("box_P2", 2, "bands", False), ("box_P2", 2, "coarse_257", False), ("box_P2", 2, "bands_t0", True))
+
+
 class _Level:
     pass
 
@@ -401,17 +412,32 @@ EXTRA_IONS = dict(X=(1.0, 1.6e-9), Y=(-1.0, 1.8e-9))                    # (z, D)
                                                                         # test_knp_solve_with_other_species_counts)
 
 
+def four_materials(pb):
+    """[D per ion] with four D tuples over the cells: D of every ion times 0.5 in the intracellular cells (tag 1) and times 1.5 in the
+    extracellular cells whose centroid lies in the upper half of x; the second ion times 0.8 more in that upper half, inside and outside: four D tuples, and interior SIPG facets
+    (tag 0) between different ones (the x mid-plane cuts both subdomains).  (Which ion and which factor is the reference's choice:
+    with the first ion times 1.25 instead, BiCGStab on the P2 box comes close to a breakdown in its second iteration -- the float64
+    and extended-precision replicas of x_2 differ by 6e-9 of x_2, the bound would be 1.9e-7 -- so that case compares nothing.)"""
+    m = pb.mesh
+    x = m.coords[m.cells].mean(axis=1)[:, 0]
+    upper = x > 0.5 * (m.coords[:, 0].min() + m.coords[:, 0].max())
+    f = np.where(pb.cell_tags == 1, 0.5, np.where(upper, 1.5, 1.0))
+    return [ion["D"] * f * (np.where(upper, 0.8, 1.0) if i == 1 else 1.0) for i, ion in enumerate(pb.ions)]
+
+
 class Host:
     """One of the test meshes ("box_P1": small_3d((8, 4, 4)), "box_P2": small_3d((6, 3, 3)) with DG-P2, "2D_P1": make_mesh_2D(0)) with
     the oracle's problem in the seeded synthetic state, its matrices (krylov_ref.Ref) and the conforming map of the preconditioner.
-    names: ions of the problem, the last one eliminated (default: the K / Cl / Na problem of the examples)."""
+    names: ions of the problem, the last one eliminated (default: the K / Cl / Na problem of the examples).
+    phi_scale: factor on the synthetic potential (1: cell Peclet number 5.4, the per-cell blocks; 0.05: 0.270 and 0.01: 0.054, the
+    drift-free class table of solve.hip).  materials: four D tuples instead of one (`four_materials`)."""
 
-    def __init__(self, mesh, names=None):
+    def __init__(self, mesh, names=None, phi_scale=1.0, materials=False):
         import knpemi_oracle as ko
         import krylov_ref as kr
         from common import synthetic_state, small_3d
         from knpemidg import amg
-        self.mesh_name, p = mesh, (2 if mesh.endswith("P2") else 1)
+        self.mesh_name, self.materials, p = mesh, bool(materials), (2 if mesh.endswith("P2") else 1)
         if mesh == "2D_P1":
             from knpemidg.mesh import make_mesh_2D
             self.mt = make_mesh_2D(0)
@@ -431,12 +457,35 @@ class Host:
             pb.c_prev_n = pb.c * (1 + 1e-3 * rng.uniform(-1, 1, size=pb.c.shape))
             pb.c_elim = rng.uniform(80.0, 120.0, size=pb.c_elim.shape)
         synthetic_state(pb)
-        self.pb, self.ref, self.nd = pb, kr.Ref(pb), pb.nd
+        pb.phi = phi_scale * pb.phi
+        if materials:
+            for ion, D in zip(pb.ions, four_materials(pb)):
+                ion["D"] = D
+        self.pb, self.ref, self.nd = pb, kr.Ref(pb), pb.nd                # (after the changes above: its matrices see them)
         self.cs = amg.ConformingSpace(m, f.array(), (1,))
         self.cs2 = amg.ConformingSpaceP2(self.cs) if p != 1 else None
         self.dg2cg = np.asarray((self.cs2 or self.cs).dof)
         self.ncg = int(self.dg2cg.max()) + 1
-        self._knp = None
+        self._knp = self._tab = None
+
+    def variant(self, phi=None, dt=None, D=None):
+        """this host with another potential [nc, nd], time step or diffusion coefficients [ions, nc]: the KNP matrices and both block
+        sets follow (assembled at first use), the mesh, the state and the EMI side (`ref`) are shared.  For potentials and
+        coefficients that change on a live device."""
+        import copy
+        h = copy.copy(self)
+        h.pb = copy.copy(self.pb)
+        h._knp = None
+        if phi is not None:
+            h.pb.phi = np.array(phi, dtype=np.float64).reshape(self.pb.phi.shape)
+        if dt is not None:
+            h.pb.dt, h._tab = float(dt), None
+        if D is not None:
+            h.pb.ions = [dict(ion, D=np.array(d, dtype=np.float64)) for ion, d in zip(self.pb.ions, D)]
+            h._tab = None
+        h.ref = copy.copy(self.ref)
+        h.ref.pb = h.pb
+        return h
 
     def emi_levels(self):
         """the production hierarchy (Case.upload_amg of test_gpu_krylov.py)"""
@@ -458,10 +507,51 @@ class Host:
             self._knp = ([A for A, _ in mats], [kr.block_inverses(A, self.nd) for A, _ in mats], [b.ravel() for _, b in mats])
         return self._knp
 
-    def peclet(self):
-        """solve.hip: k_cell_peclet -- above 0.5 the KNP solve uses the per-cell block inverses (drift included), as `knp` does"""
+    def knp_table_blocks(self):
+        """[fp32 cell-block inverses of A_k assembled at phi = 0]: what build_bj_table (solve.hip) gathers its table from -- one launch of
+        the per-cell kernel with a zero drift coefficient, then the representatives' blocks (k_bj_gather).  Listed per cell here; that
+        the cells of one table key hold the same bits is asserted by tests/test_amg_ref_host.py (`table_keys`)."""
+        if self._tab is None:
+            import krylov_ref as kr
+            import knpemi_oracle as ko
+            keep = self.pb.phi
+            self.pb.phi = np.zeros_like(keep)
+            try:
+                self._tab = [kr.block_inverses(ko.assemble_knp(self.pb, k).tocsr(), self.nd) for k in range(self.pb.N_ions)]
+            finally:
+                self.pb.phi = keep
+        return self._tab
+
+    def blocks(self, which):
+        """"cell": the per-cell inverses with the drift of the host's potential; "table": the drift-free ones; a list: itself"""
+        if isinstance(which, str):
+            return {"cell": lambda: self.knp()[1], "table": self.knp_table_blocks}[which]()
+        return list(which)
+
+    def table_keys(self):
+        """per cell, the key of build_bj_table: (geometry class, material id of the D tuple over all ions, kind of each of the four
+        facets: 0 interior SIPG, 1 membrane, 2 exterior, 3 interior and inactive -- FK_* of knpemi_internal.hpp)"""
+        from knpemidg import _abi
+        m, pb = self.mt[0], self.pb
+        nc = m.num_cells()
+        cls = _abi.geometry_classes(m, np.arange(nc))
+        assert cls is not None, "not a structured 3D mesh"
+        D = np.stack([ion["D"] for ion in pb.ions], axis=1)
+        mat = np.unique(D, axis=0, return_inverse=True)[1].ravel()
+        cf = np.asarray(m.cell_facets)
+        interior = np.asarray(m.facet_cells)[cf, 1] >= 0
+        tags = pb.facet_tags[cf]
+        kind = np.where(~interior, 2, np.where(tags == 0, 0, np.where(np.isin(tags, pb.membrane_tags), 1, 3)))
+        return [(int(cls[0][c]), int(mat[c])) + tuple(int(v) for v in kind[c]) for c in range(nc)]
+
+    def cell_peclet(self):
         zmax = max(abs(ion["z"]) for ion in self.pb.ions[:-1])
-        return float(self.pb.psi * zmax * (self.pb.phi.max(axis=1) - self.pb.phi.min(axis=1)).max())
+        return self.pb.psi * zmax * (self.pb.phi.max(axis=1) - self.pb.phi.min(axis=1))
+
+    def peclet(self):
+        """solve.hip: k_cell_peclet -- above 0.5 the KNP solve uses the per-cell block inverses (drift included), as `knp` does; up to
+        0.5 the drift-free class table (`knp_table_blocks`)"""
+        return float(self.cell_peclet().max())
 
 
 def emi_xk(host, levels, cheb, k, dtype=np.float64, b=None, mut=None):
@@ -475,16 +565,79 @@ def emi_xk(host, levels, cheb, k, dtype=np.float64, b=None, mut=None):
     return kr.pcg(types.SimpleNamespace(A_emi=ref.A_emi, b_emi=b, binv_emi=ref.binv_emi), 0.0, 0.0, precond=M, iters=k, dtype=dtype)[0]
 
 
-def knp_xk(host, levels, k, dtype=np.float64, bs=None, lmax_bs=None, mut=None):
+def knp_lmax(host, blocks, bs):
+    """the spectral bound a KNP solve on `host`'s matrices estimates from the right-hand sides bs with the block set `blocks`"""
+    return bj_lambda_max(host.knp()[0], host.blocks(blocks), [np.asarray(b, dtype=np.float64).ravel() for b in bs])
+
+
+def knp_xk(host, levels, k, dtype=np.float64, bs=None, lmax_bs=None, mut=None, blocks="cell", lmax=None):
     """x_k [nsys, ndof] of the device's KNP BiCGStab from x_0 = 0.  levels: one hierarchy shared by the species (its columns), or a
-    list with one hierarchy per species.  lmax_bs: the right-hand sides the spectral bound was estimated from (default: bs)."""
-    As, binvs, b0 = host.knp()
+    list with one hierarchy per species.  lmax_bs: the right-hand sides the spectral bound was estimated from (default: bs).
+    blocks: the cell blocks of the preconditioner and of the spectral bound -- "cell" (per-cell inverses with the drift), "table" (the
+    drift-free class table of solve.hip) or an explicit list (lagged inverses of another potential: `Host.variant(...).blocks`).
+    lmax: the spectral bound itself, where the device keeps one estimated on other matrices (`knp_lmax`)."""
+    As, _, b0 = host.knp()
+    binvs = host.blocks(blocks)
     bs = b0 if bs is None else [np.asarray(b, dtype=np.float64).ravel() for b in bs]
     ns = len(As)
-    lmax = bj_lambda_max(As, binvs, bs if lmax_bs is None else lmax_bs)
+    if lmax is None:
+        lmax = bj_lambda_max(As, binvs, bs if lmax_bs is None else lmax_bs)
     shared = hasattr(levels[0], "A")
     Hs = store(levels, dtype, mut, ncol=ns) if shared else [store(lv, dtype, mut) for lv in levels]
     return bicgstab(As, bs, KnpPrecond(As, binvs, host.dg2cg, Hs, lmax, dtype, mut), k, dtype)
+
+
+def at_peclet(host, pe):
+    """`host` with its potential scaled to the cell Peclet number pe"""
+    h = host.variant(phi=host.pb.phi * (pe / host.peclet()))
+    assert abs(h.peclet() - pe) <= 1e-12
+    return h
+
+
+def one_cell_peclet(host, cell, pe=0.8, background=0.054):
+    """`host` at the Peclet number `background`, but for `cell`, whose nodal potentials are stretched to `pe`"""
+    low = at_peclet(host, background)
+    phi = low.pb.phi.copy()
+    phi[cell] *= pe / low.cell_peclet()[cell]
+    h = host.variant(phi=phi)
+    cp = h.cell_peclet()
+    assert int(np.argmax(cp)) == cell and abs(cp[cell] - pe) <= 1e-12 and np.sort(cp)[-2] <= background + 1e-12
+    return h
+
+
+def switch_sequence(lo, bs):
+    """The solves of a context whose potential changes ON THE DEVICE (no state upload, as in a time step) between `lo` (Peclet number
+    0.27) and two higher ones (0.8, 0.7), x_0 = 0 likewise, by the rules of knp_knp_solve (solve.hip):
+
+      * the Peclet number of a potential arrives with the status polls of the first solve at that potential: that solve still uses
+        the block set of the previous potential, the next one the new set;
+      * the table solves keep the age of the per-cell array at 0, so the first solve that falls back rebuilds it from the drift of the
+        potential it runs at -- the array then holds the drift-free content the table build left there, or older inverses; later
+        per-cell solves keep the array (KNP_BJ_LAG = 8): the one solve that still runs on it after the potential has returned applies
+        the inverses of the OTHER potential;
+      * the spectral bound (chebyshev_bound) is estimated from the right-hand side by the first solve, after a state upload and after
+        a flip of the block set -- on the matrices and blocks of that solve; otherwise it is kept: no solve of the tests converges,
+        so no reference iteration count exists (it_ref stays -1), and the age limit of 64 solves is not reached.
+
+    Returns the steps: dict(tag, phi: the host whose potential goes to the device before the solve (or None), host: the matrices,
+    blocks, lmax: the kept bound (None: estimated by this solve), wrong: {what a broken rule would give: (blocks, lmax)}).  The first
+    step follows a state upload."""
+    hi, hi2 = at_peclet(lo, 0.8), at_peclet(lo, 0.7)
+    lm_lo = knp_lmax(lo, "table", bs)
+    lm_hi = knp_lmax(hi, "cell", bs)
+    T, C = "table", "cell"
+    step = lambda tag, phi, host, blocks, lmax, **wrong: dict(tag=tag, phi=phi, host=host, blocks=blocks, lmax=lmax, wrong=wrong)
+    return [
+        step("1 low", lo, lo, T, None, per_cell=(C, None)),
+        step("2 high, Peclet not seen yet", hi, hi, T, lm_lo, switched_at_once=(C, None), new_bound=(T, None)),
+        step("3 high", None, hi, C, None, still_table=(T, lm_lo), bound_kept=(C, lm_lo), drift_free_array=(T, None)),
+        step("4 low, Peclet not seen yet", lo, lo, hi.blocks(C), lm_hi, switched_at_once=(T, None), rebuilt=(C, lm_hi),
+             new_bound=(hi.blocks(C), None)),
+        step("5 low", None, lo, T, None, still_per_cell=(hi.blocks(C), lm_hi), bound_kept=(T, lm_hi)),
+        step("6 low again", None, lo, T, lm_lo),
+        step("7 high again, Peclet not seen yet", hi2, hi2, T, lm_lo, switched_at_once=(C, None), new_bound=(T, None)),
+        step("8 high again", None, hi2, C, None, stale_array=(hi.blocks(C), None), bound_kept=(C, lm_lo)),
+    ]
 
 
 def hp_dtype():

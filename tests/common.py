@@ -28,11 +28,16 @@ def synthetic_state(pb, seed=0, volt=1.0):
 def device_for(pb, **kw):
     from knpemidg import _abi
     dev = _abi.Device(pb.mesh, pb.cell_tags, pb.facet_tags, pb.membrane_tags, len(pb.ions), degree=pb.p, **kw)
+    set_params_of(dev, pb)
+    return dev
+
+
+def set_params_of(dev, pb):
+    """the problem's coefficients (dt, D, ...) to the device: at its creation, and again when a test changes them"""
     z = [ion["z"] for ion in pb.ions]
     D = np.stack([ion["D"] for ion in pb.ions])
     dev.set_params(pb.C_M, pb.dt, pb.F, pb.R, pb.T, pb.C_phi, pb.tau, pb.tau, z, D, rho=pb.rho,
                    splitting=pb.splitting)
-    return dev
 
 
 def push_state(dev, pb):

@@ -2,6 +2,8 @@
 k-iteration iterates is meant to use: the replica V-cycle is a symmetric positive operator that preconditions, it equals
 P Ac^-1 P^T where that is what it must be, the hand-built hierarchies reach every instantiation of the density-dispatched kernels of csrc/amg.hip, and each of six
 deliberate errors in the replica moves the k-iteration result by at least 100 times the comparison bound (amg_ref.bound).
+For the KNP solve on the drift-free class table of solve.hip (build_bj_table): the replica's table blocks are one block per table key,
+to the bit; the two block sets give iterates at least 1e6 bounds apart; and the bound exists for every case the device runs.
 No GPU is needed, but knpemidg.amg builds its hierarchies with the host routines of the built library (as tests/test_host.py does)."""
 import os
 
@@ -227,3 +229,126 @@ def test_emi_preconditioner_replica(mesh):
         # its dense pseudo-inverse carries the 1e8 condition of the isolated subdomain-constant mode)
         for cheb in (False, True):
             ar.bound(ar.emi_xk(h, levels, cheb, 3), ar.emi_xk(h, levels, cheb, 3, ar.hp_dtype()))
+
+
+# ---- the drift-free class table of the KNP solve (solve.hip: build_bj_table) ------------------------------------------------------------
+_TABLE_HOSTS = {}
+
+
+def _table_host(mesh, ns=2, materials=False):
+    key = (mesh, ns, materials)
+    if key not in _TABLE_HOSTS:
+        _TABLE_HOSTS[key] = ar.Host(mesh, ar.IONS[ns], phi_scale=ar.TABLE_PHI_SCALE, materials=materials)
+    return _TABLE_HOSTS[key]
+
+
+@pytest.mark.parametrize("materials", [False, True])
+@pytest.mark.parametrize("mesh", ["box_P1", "box_P2"])
+def test_table_blocks_are_one_block_per_key(mesh, materials):
+    """What lets a table stand for the cells: within every key (geometry class, material, facet kinds) the oracle's drift-free diagonal
+    blocks, inverted and rounded to fp32, hold the same bits -- also with four materials and interior SIPG facets between different
+    ones (the block takes the cell's own D only); with the drift they do not.  The keys fit build_bj_table's 8192 entries, and the
+    potential of these cases is on the table's side of the switch (Peclet number <= 0.5) by a margin."""
+    h = _table_host(mesh, materials=materials)
+    keys = h.table_keys()
+    ids = {}
+    for c, key in enumerate(keys):
+        ids.setdefault(key, []).append(c)
+    assert 24 <= len(ids) <= 8192, len(ids)
+    assert len({k[0] for k in ids}) == 24 and len({k[1] for k in ids}) == (4 if materials else 1)
+    if materials:
+        fc, D = h.mt[0].facet_cells[h.pb.int0], np.stack([ion["D"] for ion in h.pb.ions], axis=1)
+        assert (D[fc[:, 0]] != D[fc[:, 1]]).any(axis=1).sum() >= 10
+    tab, cell = h.knp_table_blocks(), h.knp()[1]
+    assert len(tab) == h.pb.N_ions and tab[0].shape == (len(keys), h.nd, h.nd)
+    spread = lambda B: max(np.abs(B[cs] - B[cs[0]]).max() / np.abs(B[cs[0]]).max() for cs in ids.values())
+    for s in range(h.pb.N_ions):
+        assert all(np.array_equal(tab[s][cs], np.broadcast_to(tab[s][cs[0]], tab[s][cs].shape)) for cs in ids.values()), (mesh, s)
+        assert spread(tab[s]) == 0.0 and spread(cell[s]) > 1e-3, (spread(tab[s]), spread(cell[s]))
+    assert 0.1 <= h.peclet() <= 0.4, h.peclet()
+
+
+@pytest.mark.parametrize("materials", [False, True])
+@pytest.mark.parametrize("mesh", ["box_P1", "box_P2"])
+def test_table_and_cell_replicas_are_far_apart(mesh, materials):
+    """the discriminating power of the device comparison on the table path: x_1 and x_2 with the drift-free blocks and with the per-cell
+    blocks differ by >= 1e6 bounds for every species (measured: >= 1e9) -- a device on the other block set cannot pass"""
+    h = _table_host(mesh, materials=materials)
+    levels = ar.synthetic_set(h.ncg, h.scale(knp=True))["bands"]
+    for k in (1, 2):
+        xt = ar.knp_xk(h, levels, k, blocks="table")
+        xc = ar.knp_xk(h, levels, k, blocks="cell")
+        xhp = ar.knp_xk(h, levels, k, ar.hp_dtype(), blocks="table")
+        for s in range(h.pb.N_ions):
+            ratio = np.abs(xt[s] - xc[s]).max() / ar.bound(xt[s], xhp[s])
+            print("TABLE/CELL %s materials=%d k=%d species %d: %.3g bounds" % (mesh, materials, k, s, ratio))
+            assert ratio >= 1e6, (mesh, materials, k, s, ratio)
+
+
+@pytest.mark.parametrize("mesh", ["box_P1", "box_P2"])
+def test_one_wrong_table_index_is_far_above_the_bound(mesh):
+    """a single cell that reads another entry of the table (the next cell's whose block differs: a wrong bj_idx, a wrong key) moves
+    x_1 of every species by >= 1e6 bounds -- every 16th cell (measured over all cells: >= 4.7e9 on the P1 box, >= 9.1e9 on the P2 box)"""
+    h = _table_host(mesh)
+    levels = ar.synthetic_set(h.ncg, h.scale(knp=True))["bands"]
+    tab = h.knp_table_blocks()
+    nc = len(tab[0])
+    x = ar.knp_xk(h, levels, 1, blocks="table")
+    xhp = ar.knp_xk(h, levels, 1, ar.hp_dtype(), blocks="table")
+    bd = [ar.bound(x[s], xhp[s]) for s in range(2)]
+    for c in range(3, nc, 16):
+        o = next(d % nc for d in range(c + 1, c + nc) if not np.array_equal(tab[0][d % nc], tab[0][c]))
+        wrong = [t.copy() for t in tab]
+        for t in wrong:
+            t[c] = t[o]
+        y = ar.knp_xk(h, levels, 1, blocks=wrong)
+        moved = [np.abs(x[s] - y[s]).max() / bd[s] for s in range(2)]
+        assert min(moved) >= 1e6, (mesh, c, o, moved)
+
+
+@pytest.mark.parametrize("case", ar.TABLE_CASES, ids=lambda c: "-".join(str(v) for v in c))
+def test_table_cases_of_the_device_are_well_conditioned(case):
+    """amg_ref.bound raises for an ill-conditioned case (bound above 1e-9 of the result): none of the cases the device runs is one"""
+    mesh, ns, names, materials = case
+    h = _table_host(mesh, ns, materials)
+    S = ar.synthetic_set(h.ncg, h.scale(knp=True))
+    levels = S[names] if isinstance(names, str) else [S[n] for n in names]
+    for k in (1, 2):
+        x64 = ar.knp_xk(h, levels, k, blocks="table")
+        xhp = ar.knp_xk(h, levels, k, ar.hp_dtype(), blocks="table")
+        for s in range(ns):
+            bd = ar.bound(x64[s], xhp[s])
+            print("TABLE BOUND %s k=%d species %d: %.3g" % (case, k, s, bd / np.abs(xhp[s]).max()))
+
+
+def _apart(h, levels, k, bs, right, wrong, tag):
+    """x_k of the replica by the rule (blocks, lmax) `right` and by `wrong`, in bounds of the right one; every species >= 1e6"""
+    x = ar.knp_xk(h, levels, k, bs=bs, blocks=right[0], lmax=right[1])
+    xhp = ar.knp_xk(h, levels, k, ar.hp_dtype(), bs=bs, blocks=right[0], lmax=right[1])
+    y = ar.knp_xk(h, levels, k, bs=bs, blocks=wrong[0], lmax=wrong[1])
+    ratio = [np.abs(x[s] - y[s]).max() / ar.bound(x[s], xhp[s]) for s in range(len(x))]
+    print("SWITCH %s: %s bounds" % (tag, ", ".join("%.3g" % r for r in ratio)))
+    assert min(ratio) >= 1e6, (tag, ratio)
+
+
+def test_switch_cases_of_the_device_tell_the_rule_from_a_broken_one():
+    """the device tests of the switch between the two block sets (tests/test_gpu_amg.py) compare with the replica by the rules of
+    knp_knp_solve; here, what a broken rule would give instead -- the other block set, the array the table build left behind, a stale
+    array or table, a spectral bound kept or re-estimated at the wrong solve -- is >= 1e6 bounds away in every step and species"""
+    lo = _table_host("box_P1")
+    levels = ar.synthetic_set(lo.ncg, lo.scale(knp=True))["bands"]
+    bs = lo.knp()[2]
+    other = {"table": "cell", "cell": "table"}
+    for pe, blocks in ((0.45, "table"), (0.55, "cell")):
+        for k in (1, 2):
+            _apart(ar.at_peclet(lo, pe), levels, k, bs, (blocks, None), (other[blocks], None), "Peclet %.2f k=%d" % (pe, k))
+    nc = lo.mt[0].num_cells()
+    for mesh, cell in (("box_P1", 0), ("box_P1", nc - 1), ("box_P2", 323)):
+        h0 = _table_host(mesh)
+        lv = ar.synthetic_set(h0.ncg, h0.scale(knp=True))["bands"]
+        _apart(ar.one_cell_peclet(h0, cell), lv, 1, h0.knp()[2], ("cell", None), ("table", None), "%s one cell %d" % (mesh, cell))
+    for st in ar.switch_sequence(lo, bs):
+        for what, wrong in st["wrong"].items():
+            _apart(st["host"], levels, 1, bs, (st["blocks"], st["lmax"]), wrong, "step %s / %s" % (st["tag"], what))
+    for what, h in (("dt", lo.variant(dt=lo.pb.dt / 2)), ("materials", lo.variant(D=ar.four_materials(lo.pb)))):
+        _apart(h, levels, 1, bs, ("table", None), (lo.blocks("table"), None), "new %s / table of the old ones" % what)

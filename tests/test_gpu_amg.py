@@ -9,6 +9,18 @@ k_prolong_add(_pair)).  Hierarchies are uploaded through Device.amg_upload: the 
 instantiations of the density-dispatched kernels (tests/test_amg_ref_host.py asserts that) and coarsest levels of 1 ... 2051 rows; the
 production ones come from amg.build_emi_levels.  The host runs the same iterations on the oracle's matrices with the fp32 cell blocks.
 
+The KNP solve has two sets of cell blocks (solve.hip: knp_knp_solve): the per-cell inverses with the drift, and, on structured 3D meshes
+while the cell Peclet number of the potential is at most 0.5 -- every production step -- the drift-free table of build_bj_table, one
+block per (geometry class, material, facet kinds) that all Krylov vector kernels read through bj_block().  The synthetic potential has
+Peclet number 5.4 (per-cell blocks); the "table" groups below run at 0.05 times that potential (0.27), with one and with four
+materials, against the replica on the oracle's blocks assembled at phi = 0; the "switch" groups check which set a solve uses: on either
+side of the limit, with the largest cell Peclet number at the edges of k_cell_peclet's waves and workgroups, through a fall-back and
+return on a potential that changes on the device (one solve late, with the rebuilt per-cell array and the re-estimated spectral bound),
+and after set_params.  Against the replica on the OTHER block set the table cases miss by 7.4e8 ... 6.5e11 bounds (tried once on the
+MI355X; tests/test_amg_ref_host.py asserts >= 1e6 between the two replicas).  GMRES on the table path is covered by the stopping tests
+of tests/test_gpu_krylov.py alone (converged solves frozen at the EMI solution: Peclet number 0.012 on box_P1, 0.018 on axon_P1), not
+vector by vector: there is no GMRES replica.
+
 Bound ("V-cycle parity"): max(32 ||x64 - x_hp||_inf, 1e-13 ||x_hp||_inf) with x64 / x_hp the replica in float64 / extended
 precision -- never taken from the device's numbers.  Measured on the MI355X, as multiples of ||x_k||_inf, worst case of each group:
 
@@ -25,6 +37,16 @@ precision -- never taken from the device's numbers.  Measured on the MI355X, as 
   KNP  3D P1 box, one hierarchy per species (2 and 3 species)    1.2e-11         5.9e-13                0.35
   KNP  3D P2 box, 2 / 3 species shared                           1.8e-10         7.0e-12                0.20
   KNP  3D P2 box, one hierarchy per species                      1.4e-10         7.1e-12                0.22
+  KNP  table, 3D P1 box, 2 species, 3 hierarchies + unfused      3.3e-11         1.8e-12                0.25
+  KNP  table, 3D P1 box, 2 species shared, four materials        2.2e-12         1.0e-13                0.07
+  KNP  table, 3D P1 box, 3 and 4 species shared                  3.3e-13         1.9e-14                0.14
+  KNP  table, 3D P1 box, one per species, four materials         2.2e-12         6.4e-13                0.29
+  KNP  table, 3D P2 box, bands / coarse_257                      1.8e-10         6.3e-12                0.20
+  KNP  table, 3D P2 box, bands_t0, four materials                6.8e-11         1.5e-12                0.12
+  KNP  switch, threshold (Peclet 0.45 table, 0.55 per cell)      8.0e-12         2.4e-13                0.21
+  KNP  switch, largest Peclet number in 6 + 1 cell positions     1.1e-12         5.8e-14                0.27
+  KNP  switch, fall-back and return on the device, 8 solves      3.7e-13         2.2e-14                0.12
+  KNP  switch, table after set_params (dt / 2, four materials)   3.7e-13         2.2e-14                0.11
   (both DG smoothers, the random right-hand side and the unfused paths are inside their groups)
 
 Two production cases are ill-conditioned by the rule above and are not run: the single-level hierarchy of the 2D mesh (bounds 0.85e-9 ...
@@ -32,11 +54,13 @@ Two production cases are ill-conditioned by the rule above and are not run: the 
 
 Each case also solves twice (same bits: graph replay, swapped x / d1 buffers) and, with several columns, changes one species'
 right-hand side (the others' iterates keep their bits)."""
+import contextlib
+
 import numpy as np
 import pytest
 
 import amg_ref as ar
-from common import device_for, push_state
+from common import device_for, push_state, set_params_of
 
 pytestmark = pytest.mark.gpu
 
@@ -46,10 +70,10 @@ ALL = ar.SYNTHETIC                 # the list whose coverage of the 48 kernel in
 
 
 class Ctx:
-    def __init__(self, mesh, names):
+    def __init__(self, mesh, names, phi_scale=1.0, materials=False):
         from knpemidg import _abi as A
         self.A = A
-        self.host = ar.Host(mesh, names)
+        self.host = ar.Host(mesh, names, phi_scale, materials)
         pb = self.host.pb
         self.dev = device_for(pb)
         push_state(self.dev, pb)
@@ -104,10 +128,11 @@ def _close_devices():
     _CTX.clear()
 
 
-def _ctx(mesh, names=None):
-    if (mesh, names) not in _CTX:
-        _CTX[(mesh, names)] = Ctx(mesh, names)
-    return _CTX[(mesh, names)]
+def _ctx(mesh, names=None, phi_scale=1.0, materials=False):
+    key = (mesh, names, phi_scale, materials)
+    if key not in _CTX:
+        _CTX[key] = Ctx(*key)
+    return _CTX[key]
 
 
 def _report(tag, k, bd, err, scale):
@@ -171,12 +196,15 @@ def test_emi_iterates_unfused_paths(hip_lib, monkeypatch, name, switch, cheb):
 
 
 # ---- KNP ---------------------------------------------------------------------------------------------------------------------------
-IONS = {2: None, 3: ("K", "Cl", "X", "Na"), 4: ("K", "Cl", "X", "Y", "Na")}
+IONS = ar.IONS
 
 
-def _check_knp(c, names, independent=True):
+def _check_knp(c, names, independent=True, blocks="cell"):
     """names: one hierarchy shared by the species (slot 1, one column each) or a tuple with one per species (slots 1 ...)"""
-    assert c.host.peclet() > 0.5                                        # per-cell block inverses with the drift, as the replica's
+    if blocks == "cell":
+        assert c.host.peclet() > 0.5                                    # per-cell block inverses with the drift, as the replica's
+    else:
+        assert c.host.peclet() <= 0.4                                   # the drift-free class table (solve.hip: at most 0.5)
     shared = isinstance(names, str)
     levels = c.levels(names, True) if shared else [c.levels(n, True) for n in names]
     dev, ns = c.dev, c.ns
@@ -202,11 +230,13 @@ def _check_knp(c, names, independent=True):
         if other is not None:
             keep = [s for s in range(ns) if s != 1]
             assert np.array_equal(other[keep], x[keep]) and not np.array_equal(other[1], x[1]), (names, k, "species are not independent")
-        x64 = ar.knp_xk(c.host, levels, k, bs=c.b_knp)
-        xhp = ar.knp_xk(c.host, levels, k, ar.hp_dtype(), bs=c.b_knp)
+        x64 = ar.knp_xk(c.host, levels, k, bs=c.b_knp, blocks=blocks)
+        xhp = ar.knp_xk(c.host, levels, k, ar.hp_dtype(), bs=c.b_knp, blocks=blocks)
         for s in range(ns):
             bd, err = ar.bound(x64[s], xhp[s]), np.abs(x[s] - x64[s]).max()
-            _report("knp %s ns=%d %s species %d" % (c.host.mesh_name, ns, names, s), k, bd, err, np.abs(xhp[s]).max())
+            _report("knp %s%s%s ns=%d %s species %d" % ("" if blocks == "cell" else "table ", c.host.mesh_name,
+                                                        " 4 materials" if c.host.materials else "", ns, names, s), k, bd, err,
+                    np.abs(xhp[s]).max())
             if not err <= bd:
                 bad.append((k, s, err / bd))
     assert not bad, (names, bad)
@@ -239,3 +269,128 @@ def test_knp_iterates_one_hierarchy_per_species(hip_lib, mesh, ns, names):
 def test_knp_iterates_unfused_restriction(hip_lib, monkeypatch):
     monkeypatch.setenv("KNP_FUSE_RESTRICT", "0")
     _check_knp(_ctx("box_P1"), "bands", independent=False)
+
+
+# ---- KNP on the drift-free class table (solve.hip: build_bj_table) -----------------------------------------------------------------
+def _check_knp_table(c, names, independent=True):
+    """_check_knp at a potential whose cell Peclet number is below the switch: the device preconditions with its table, the replica
+    with the oracle's drift-free blocks (amg_ref.Host.knp_table_blocks)"""
+    _check_knp(c, names, independent, blocks="table")
+
+
+def _table_ctx(mesh="box_P1", ns=2, materials=False):
+    return _ctx(mesh, IONS[ns], ar.TABLE_PHI_SCALE, materials)
+
+
+@pytest.mark.parametrize("case", ar.TABLE_CASES, ids=lambda c: "-".join(str(v) for v in c))
+def test_knp_table_iterates(hip_lib, case):
+    """every key's block (24 geometry classes, 42 keys; 100 / 72 with four materials), bj_idx in device cell order, all the Krylov vector
+    kernels that read through bj_block() and the power iteration of the spectral bound"""
+    mesh, ns, names, materials = case
+    _check_knp_table(_table_ctx(mesh, ns, materials), names)
+
+
+def test_knp_table_iterates_unfused_restriction(hip_lib, monkeypatch):
+    monkeypatch.setenv("KNP_FUSE_RESTRICT", "0")
+    _check_knp_table(_table_ctx(), "bands", independent=False)
+
+
+# ---- the switch between the two block sets and its state ---------------------------------------------------------------------------
+def _set_phi(c, phi, upload=True):
+    """upload: a state upload (it resets the lagged state and last_peclet: the next solve reads the Peclet number itself).  Otherwise
+    the potential changes on the device, as a time step changes it: through a same-sized field whose upload has no side effects."""
+    A, dev = c.A, c.dev
+    if upload:
+        dev.upload(A.F_PHI, phi)
+    else:
+        dev.upload(A.F_B_EMI, phi)
+        dev.copy_field(A.F_PHI, A.F_B_EMI)
+    dev.update_dnphi()
+
+
+@contextlib.contextmanager
+def _bands(c):
+    """the hierarchy `bands` shared by the species, for solves at other potentials / coefficients; the context's state afterwards"""
+    dev, ns, A = c.dev, c.ns, c.A
+    levels = c.levels("bands", True)
+    for s in range(ns):
+        dev.amg_clear(1 + s)
+    dev.amg_upload(1, c.host.dg2cg, levels, ncol=ns)
+    try:
+        yield levels
+    finally:
+        for s in range(ns):
+            dev.amg_clear(1 + s)
+        set_params_of(dev, c.host.pb)
+        dev.upload(A.F_B_KNP, c.b_knp)
+        dev.upload(A.F_B_EMI, c.b_emi)
+        dev.upload(A.F_C, c.host.pb.c)
+        _set_phi(c, c.host.pb.phi)
+
+
+def _match(c, host, levels, k, x, tag, blocks, lmax=None):
+    """the device's x_k against the replica on `host`'s matrices with `blocks` (and the spectral bound `lmax`, default: estimated on
+    these matrices and blocks from the right-hand side)"""
+    x64 = ar.knp_xk(host, levels, k, bs=c.b_knp, blocks=blocks, lmax=lmax)
+    xhp = ar.knp_xk(host, levels, k, ar.hp_dtype(), bs=c.b_knp, blocks=blocks, lmax=lmax)
+    bad = []
+    for s in range(c.ns):
+        bd, err = ar.bound(x64[s], xhp[s]), np.abs(x[s] - x64[s]).max()
+        _report("knp switch %s %s species %d" % (c.host.mesh_name, tag, s), k, bd, err, np.abs(xhp[s]).max())
+        if not err <= bd:
+            bad.append((k, s, err / bd))
+    assert not bad, (tag, bad)
+
+
+@pytest.mark.parametrize("pe,blocks", [(0.45, "table"), (0.55, "cell")])
+def test_knp_switch_threshold(hip_lib, pe, blocks):
+    """on either side of KNP_BJ_TABLE_PECLET = 0.5 (the float the device compares is 0.45 / 0.55 to 1e-7)"""
+    c = _table_ctx()
+    h = ar.at_peclet(c.host, pe)
+    with _bands(c) as levels:
+        _set_phi(c, h.pb.phi)
+        for k in (1, 2):
+            _match(c, h, levels, k, c.knp(k, c.b_knp), "Pe %.2f" % pe, blocks)
+
+
+@pytest.mark.parametrize("mesh,pos", [("box_P1", p) for p in (0, 63, 64, 255, 256, -1)] + [("box_P2", -1)])
+def test_knp_switch_finds_the_largest_cell_peclet_number(hip_lib, mesh, pos):
+    """k_cell_peclet: one cell with Peclet number 0.8 in a background of 0.054, first and last lane of a wave, of a workgroup (256
+    cells), of the grid (768 cells: three full workgroups; 324 on the P2 box: the second one partly filled) -- the solve must fall
+    back to the per-cell blocks wherever the cell sits"""
+    c = _table_ctx(mesh)
+    h = ar.one_cell_peclet(c.host, int(c.dev.cell_order[pos if pos >= 0 else c.dev.nc_owned - 1]))
+    with _bands(c) as levels:
+        _set_phi(c, h.pb.phi)
+        _match(c, h, levels, 1, c.knp(1, c.b_knp), "cell %d of the device" % pos, "cell")
+
+
+def test_knp_switch_falls_back_and_returns_without_an_upload(hip_lib):
+    """amg_ref.switch_sequence (the rules of solve.hip are written there): the potential changes on the device, through a field whose
+    upload has no side effects, and x_0 = 0 likewise (Ctx.knp(keep_bound=True)); every solve is one BiCGStab iteration.  That each
+    step tells its rule from a broken one by >= 1e6 bounds is asserted on the CPU (tests/test_amg_ref_host.py)."""
+    c = _table_ctx()
+    assert abs(c.host.peclet() - 0.27) < 0.005
+    with _bands(c) as levels:
+        last = None
+        for i, st in enumerate(ar.switch_sequence(c.host, c.b_knp)):
+            if st["phi"] is not None:
+                _set_phi(c, st["phi"].pb.phi, upload=i == 0)
+            x = c.knp(1, c.b_knp, keep_bound=i > 0)                     # (the first one: upload of c, x_0 = 0 and an empty history)
+            _match(c, st["host"], levels, 1, x, st["tag"], st["blocks"], st["lmax"])
+            if st["tag"] == "6 low again":
+                assert np.array_equal(x, last), "a table solve with the kept bound gave other bits"
+            last = x
+
+
+@pytest.mark.parametrize("what", ["dt", "materials"])
+def test_knp_table_is_rebuilt_after_new_coefficients(hip_lib, what):
+    """set_params with half the time step, or with the four-material diffusion coefficients, on a context whose table exists: the
+    next solve runs on the table of the new coefficients (same mesh, same state)"""
+    c = _table_ctx()
+    h = c.host.variant(dt=c.host.pb.dt / 2) if what == "dt" else c.host.variant(D=ar.four_materials(c.host.pb))
+    with _bands(c) as levels:
+        _match(c, c.host, levels, 1, c.knp(1, c.b_knp), "before new %s" % what, "table")
+        set_params_of(c.dev, h.pb)
+        c.dev.update_dnphi()
+        _match(c, h, levels, 1, c.knp(1, c.b_knp), "new %s" % what, "table")
