@@ -246,7 +246,7 @@ static int shm_halo_exchange(knp_ctx* c, double* v, int nfields, hipStream_t st)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Interface exchange of the row-distributed conforming level (amg.hip: dist0).  Message p carries this rank's partial sums at the dofs
+// Interface exchange of the row-distributed conforming level (amg_vcycle.hip: dist0).  Message p carries this rank's partial sums at the dofs
 // it shares with peer p ([position][column]); both sides list those dofs in ascending global order, so what arrives from p has the
 // layout of what was sent to p.  k_if_add then forms, per shared dof, the sum over ALL its owners in ascending rank order -- every
 // owner gets the same bits.  Messages: r=2 mesh, 8 slabs: ~3 k dofs x 8 B x columns per peer, i.e. latency only.

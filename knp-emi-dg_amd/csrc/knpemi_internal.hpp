@@ -193,7 +193,7 @@ struct knp_ctx {
     int32_t* halo_send_idx = nullptr;   // device: owned cell ids to pack, grouped by peer
     double* halo_sendbuf = nullptr;
     int64_t halo_send_total = 0;
-    // row-distributed finest conforming level (amg.hip: dist0; knp_amg_interface): the conforming dofs this rank shares with peers.
+    // row-distributed finest conforming level (amg_vcycle.hip: dist0; knp_amg_interface): the conforming dofs this rank shares with peers.
     // The list of one peer is the same on both sides (ascending global dof), so message p is sent and received with one layout
     std::vector<int> if_peer;
     std::vector<int64_t> if_off, if_cnt;

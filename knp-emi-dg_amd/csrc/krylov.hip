@@ -14,7 +14,7 @@
 // (P1: membrane-broken vertex dofs; P2: vertex + edge dofs of the conforming P2 space) -- pure injection
 template <int NV> __device__ __forceinline__ void prolong_cell(const int32_t* __restrict__ dg2cg, const double* __restrict__ e,
                                                                 int64_t c, double* add, int nil = 1) {
-    // nil: interleaved right-hand-side columns of the level vector (amg.hip); e points at this column's first entry
+    // nil: interleaved right-hand-side columns of the level vector (amg_vcycle.hip); e points at this column's first entry
 #pragma unroll
     for (int a = 0; a < NV; ++a) add[a] = e[(int64_t)dg2cg[c * NV + a] * nil];
 }
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_cg_update(VecDims d, const double
     write_partials<3>(partial, 1, acc);
 }
 
-// The same update fused with stage 1 of the tile-wise restriction of the auxiliary-space correction (amg.hip: k_restrict_tiles), for
+// The same update fused with stage 1 of the tile-wise restriction of the auxiliary-space correction (amg_restrict.hip: k_restrict_tiles), for
 // preconditioners WITHOUT the DG-level Chebyshev step (large uniform meshes, knp_set_emi_dg_smoother): the restricted vector is the new
 // residual, which this kernel has in registers -- one pass over r less per PCG iteration (r=3: 104 us).  No partial sums: with a
 // hierarchy k_prolong_dot forms them from the corrected z.  grid = tiles of tile_cells consecutive owned cells.
@@ -113,14 +113,12 @@ template <int NV>
 __global__ __launch_bounds__(256) void k_cg_update_restrict(VecDims d, const double* __restrict__ scal, const int* __restrict__ status,
                                                             const double* __restrict__ p, const double* __restrict__ w,
                                                             const bjreal* __restrict__ binv, double* __restrict__ x, double* __restrict__ r,
-                                                            double* __restrict__ z, int tile_cells, const int32_t* __restrict__ tile_off,
-                                                            const int32_t* __restrict__ slot_ptr, const uint16_t* __restrict__ slot_idx,
-                                                            double* __restrict__ part) {
+                                                            double* __restrict__ z, TileTables T, double* __restrict__ part) {
     extern __shared__ double s_r[];
     if (status[0]) return;                                     // converged: the V-cycle's output is not used either
     const double alpha = scal[KS_ALPHA];
-    const int64_t c0 = (int64_t)blockIdx.x * tile_cells;
-    const int ncell = (int)((d.nc_owned - c0 < tile_cells) ? (d.nc_owned - c0) : tile_cells);
+    const int64_t c0 = (int64_t)blockIdx.x * T.tile_cells;
+    const int ncell = (int)((d.nc_owned - c0 < T.tile_cells) ? (d.nc_owned - c0) : T.tile_cells);
     for (int i = threadIdx.x; i < ncell; i += 256) {
         const int64_t c = c0 + i;
         double pv[NV], wv[NV], xv[NV], rv[NV], zv[NV];
@@ -136,7 +134,7 @@ __global__ __launch_bounds__(256) void k_cg_update_restrict(VecDims d, const dou
         stv<NV>(z, c, zv);
     }
     __syncthreads();
-    tile_slot_sums(s_r, tile_off, slot_ptr, slot_idx, part);
+    tile_slot_sums(s_r, T.tile_off, T.slot_ptr, T.slot_idx, part);
 }
 
 // z += P e (conforming correction, gathered through dg2cg) ; partials r.z, z.z, ||r||_w^2 (NR = 3)  |  on init (NR = 4): r.z, z.z,
@@ -219,7 +217,7 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_prolong_add(VecDims d, const int*
                                                            int64_t ncg, double* __restrict__ y) {
     int nil = 1;
     if (sys < 0) {                                   // batched: grid.y = species, y is [nsys][nc*NV]; e is the shared hierarchy's level
-        sys = blockIdx.y;                            // vector: columns interleaved in pairs when nsys is even (amg.hip)
+        sys = blockIdx.y;                            // vector: columns interleaved in pairs when nsys is even (amg_vcycle.hip)
         nil = (d.nsys % 2 == 0) ? 2 : 1;
         e += (int64_t)(sys / nil) * nil * ncg + (sys % nil);
         y += (int64_t)sys * d.nc * NV;
@@ -357,20 +355,18 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_bj_cheb2(VecDims d, const int* __
     stv<NV>(SYS_PTR(y, s), c, yv);
 }
 
-// The same step fused with stage 1 of the tile-wise restriction of the coarse correction (amg.hip: k_restrict_tiles): both read r and
+// The same step fused with stage 1 of the tile-wise restriction of the coarse correction (amg_restrict.hip: k_restrict_tiles): both read r and
 // t = A Binv r, and the restricted vector r - ct t (hybrid form; ct = 0: r itself) is formed from the values already in registers.
 // One pass over r and t instead of two (128 MB per preconditioner application at r=2).  grid = (tiles, systems).
 template <int NV>
 __global__ __launch_bounds__(256) void k_bj_cheb2_restrict(VecDims d, const int* __restrict__ status, const bjreal* __restrict__ binv,
                                                            const double* __restrict__ r, const double* __restrict__ t, double* __restrict__ y,
-                                                           double cr, double ctt, int tile_cells, const int32_t* __restrict__ tile_off,
-                                                           const int32_t* __restrict__ slot_ptr, const uint16_t* __restrict__ slot_idx,
-                                                           double* __restrict__ part, int64_t nslots, double ct) {
+                                                           double cr, double ctt, TileTables T, double* __restrict__ part, double ct) {
     extern __shared__ double s_r[];
     const int s = blockIdx.y;
     if (status && status[2 * s]) return;                       // converged system: its V-cycle output is not used either
-    const int64_t c0 = (int64_t)blockIdx.x * tile_cells;
-    const int ncell = (int)((d.nc_owned - c0 < tile_cells) ? (d.nc_owned - c0) : tile_cells);
+    const int64_t c0 = (int64_t)blockIdx.x * T.tile_cells;
+    const int ncell = (int)((d.nc_owned - c0 < T.tile_cells) ? (d.nc_owned - c0) : T.tile_cells);
     for (int i = threadIdx.x; i < ncell; i += 256) {
         const int64_t c = c0 + i;
         double rv[NV], tv[NV], yv[NV];
@@ -385,7 +381,7 @@ __global__ __launch_bounds__(256) void k_bj_cheb2_restrict(VecDims d, const int*
         stv<NV>(SYS_PTR(y, s), c, yv);
     }
     __syncthreads();
-    tile_slot_sums(s_r, tile_off, slot_ptr, slot_idx, part + (int64_t)s * nslots);
+    tile_slot_sums(s_r, T.tile_off, T.slot_ptr, T.slot_idx, part + (int64_t)s * T.nslots);
 }
 
 // out = alpha[s] * in  (per system)
@@ -603,9 +599,9 @@ static int bj_cheb2(knp_ctx* c, const VecDims& d, const KrylovVecs& kv, const do
     if (Hfuse) {
         AmgHierarchy& H = *Hfuse;
         if ((rc = amg_restrict_tiles_prepare(c, H))) return rc;
-        hipLaunchKernelGGL(k_bj_cheb2_restrict<NV>, dim3((unsigned)H.ntiles, (unsigned)d.nsys), dim3(256), sizeof(double) * H.tile_cells * NV,
-                           c->stream, d, st, kv.binv, r, (const double*)kv.tmp, y, cr, ctt, H.tile_cells, (const int32_t*)H.tile_off,
-                           (const int32_t*)H.slot_ptr, (const uint16_t*)H.slot_idx, H.part, H.nslots, ct_restrict);
+        hipLaunchKernelGGL(k_bj_cheb2_restrict<NV>, dim3((unsigned)H.tiles.ntiles, (unsigned)d.nsys), dim3(256),
+                           sizeof(double) * H.tiles.tile_cells * NV, c->stream, d, st, kv.binv, r, (const double*)kv.tmp, y, cr, ctt, H.tiles,
+                           H.part, ct_restrict);
         return amg_restrict_finish(c, H);
     }
     const dim3 g((unsigned)grid_for(c->m.nc_owned), (unsigned)d.nsys), b(KNP_BLOCK);
@@ -613,14 +609,14 @@ static int bj_cheb2(knp_ctx* c, const VecDims& d, const KrylovVecs& kv, const do
     return 0;
 }
 // whether the second Chebyshev step and the restriction into H can share one pass (KNP_FUSE_RESTRICT=0: two passes, A/B runs)
-static bool fuse_restrict(const knp_ctx* c, const KrylovVecs& kv, const AmgHierarchy& H, int nsys) {
+static bool fuse_restrict(const KrylovVecs& kv, const AmgHierarchy& H, int nsys) {
     const bool on = env_flag("KNP_FUSE_RESTRICT", true);    // read per call: tests switch it inside one process
-    return on && kv.bj_lmax > 0.0 && H.ready && H.ntiles > 0 && H.ncol == nsys && H.tile_cells * c->nd * sizeof(double) <= 65536;
+    return on && kv.bj_lmax > 0.0 && H.ready && H.tiles.usable() && H.ncol == nsys;
 }
 
-static bool fuse_update_restrict(const knp_ctx* c, const AmgHierarchy& H) {
+static bool fuse_update_restrict(const AmgHierarchy& H) {
     // KNP_FUSE_CG_RESTRICT is read per call: tests switch it inside one process
-    return env_flag("KNP_FUSE_CG_RESTRICT", true) && H.ready && H.ntiles > 0 && H.ncol == 1 && H.tile_cells * c->nd * sizeof(double) <= 65536;
+    return env_flag("KNP_FUSE_CG_RESTRICT", true) && H.ready && H.tiles.usable() && H.ncol == 1;
 }
 
 // power iteration for lambda_max(Binv A) of the batched KNP operator (inf-norm normalisation; max over the species)
@@ -673,16 +669,15 @@ static int emi_precondition_residual(knp_ctx* c, const VecDims& d, const KrylovV
     const dim3 g((unsigned)grid_for(c->m.nc_owned)), b(KNP_BLOCK);
     const bool cheb = kv.bj_lmax > 0.0;
     int rc;
-    if (H && !cheb && fuse_update_restrict(c, *H)) {
+    if (H && !cheb && fuse_update_restrict(*H)) {
         if ((rc = amg_restrict_tiles_prepare(c, *H))) return rc;
-        hipLaunchKernelGGL(k_cg_update_restrict<NV>, dim3((unsigned)H->ntiles), dim3(256), sizeof(double) * H->tile_cells * NV, c->stream, d,
-                           c->scal, c->status, kv.p, kv.w, kv.binv, kv.x, kv.r, kv.z, H->tile_cells, (const int32_t*)H->tile_off,
-                           (const int32_t*)H->slot_ptr, (const uint16_t*)H->slot_idx, H->part);
+        hipLaunchKernelGGL(k_cg_update_restrict<NV>, dim3((unsigned)H->tiles.ntiles), dim3(256), sizeof(double) * H->tiles.tile_cells * NV,
+                           c->stream, d, c->scal, c->status, kv.p, kv.w, kv.binv, kv.x, kv.r, kv.z, H->tiles, H->part);
         if ((rc = amg_restrict_finish(c, *H))) return rc;
     } else {
         hipLaunchKernelGGL(k_cg_update<NV>, g, b, 0, c->stream, d, c->scal, c->status, kv.p, kv.w, kv.binv, kv.x, kv.r, kv.z, c->partial);
         if (!H) return 0;
-        if (fuse_restrict(c, kv, *H, 1)) {
+        if (fuse_restrict(kv, *H, 1)) {
             if ((rc = bj_cheb2<NV, true>(c, d, kv, kv.r, kv.z, true, H, 0.0))) return rc;
         } else {
             if (cheb && (rc = bj_cheb2<NV, true>(c, d, kv, kv.r, kv.z))) return rc;
@@ -838,7 +833,7 @@ static int knp_precondition(knp_ctx* c, const VecDims& d, const KrylovVecs& kv, 
     int rc;
     const bool hyb = kv.bj_lmax > 0.0 && knp_hybrid();
     const double ct = hyb ? 1.0 / bj_theta<false>(kv) : 0.0;
-    const bool fuse = (int)c->amg.size() > 1 && fuse_restrict(c, kv, c->amg[1], d.nsys);
+    const bool fuse = (int)c->amg.size() > 1 && fuse_restrict(kv, c->amg[1], d.nsys);
     if (kv.bj_lmax > 0.0 && (rc = bj_cheb2<NV, false>(c, d, kv, in, out, true, fuse ? &c->amg[1] : nullptr, ct))) return rc;
     return knp_coarse_correction<NV>(c, d, in, out, hyb ? kv.tmp : nullptr, ct, fuse);
 }

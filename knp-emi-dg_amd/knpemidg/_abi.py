@@ -800,7 +800,7 @@ class Device:
             self._rtc_ids[kernel] = mid
         return self._rtc_ids[kernel]
 
-    # -- auxiliary-space AMG (knpemidg/amg.py builds, csrc/amg.hip applies) ------------------
+    # -- auxiliary-space AMG (knpemidg/amg.py builds, csrc/amg_upload.hip receives, csrc/amg_vcycle.hip applies) ------------------
     def amg_interface(self, n_local, peers, lists, uvtx, aptr, asrc):
         """Shared-dof tables of the row-distributed conforming level (amg.Dist0Space.interface_tables)."""
         peers = np.ascontiguousarray(peers, dtype=np.int32)

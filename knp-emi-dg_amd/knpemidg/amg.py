@@ -1,4 +1,4 @@
-"""Host-side SETUP of the auxiliary-space preconditioner (the apply runs on the GPU, csrc/amg.hip).
+"""Host-side SETUP of the auxiliary-space preconditioner (the apply runs on the GPU, csrc/amg_vcycle.hip and csrc/amg_restrict.hip).
 
 The reference preconditions both Krylov solves with hypre BoomerAMG built from the assembled matrix
 (reference: src/knpemidg/solver.py:433, 505, 688, 767).  There is no assembled DG matrix here, so the
@@ -286,7 +286,7 @@ class ConformingSpaceP2:
 class Dist0Space:
     """Row distribution of the finest conforming level (space: ConformingSpace or ConformingSpaceP2 on the GLOBAL mesh) over the ranks of
     a cell partition `owner` [nc].  The reference's BoomerAMG is row-distributed by PETSc (src/knpemidg/solver.py:433, 688); here only the
-    finest level is, in the sub-assembled form of non-overlapping domain decomposition (csrc/amg.hip: dist0):
+    finest level is, in the sub-assembled form of non-overlapping domain decomposition (csrc/amg_vcycle.hip: dist0):
 
     * rank r's ELEMENTS are its owned cells and the membrane facets whose first cell it owns; its level-0 rows `verts` are the conforming
       dofs those elements touch (ascending global number = local number);

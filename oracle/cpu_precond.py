@@ -1,5 +1,5 @@
 """CPU application of the auxiliary-space preconditioner for bench.py's `cpu_baseline` leg (TEST / BENCH INFRASTRUCTURE: never
-imported by the product).  Same operator as the device applies (csrc/krylov.hip, csrc/amg.hip):
+imported by the product).  Same operator as the device applies (csrc/krylov.hip, csrc/amg_vcycle.hip, csrc/amg_restrict.hip):
 
     M^-1 r = B^-1 r + P V(P^T r),   B = cell-block diagonal of the DG matrix, P = injection of the conforming space,
     V = one V-cycle of the smoothed-aggregation hierarchy with Chebyshev-Jacobi smoothing and a dense coarse pseudo-inverse,

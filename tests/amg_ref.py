@@ -1,12 +1,12 @@
-"""Host replica of the auxiliary-space preconditioner (csrc/amg.hip, csrc/krylov.hip) -- test infrastructure.
+"""Host replica of the auxiliary-space preconditioner (csrc/amg_vcycle.hip, csrc/amg_restrict.hip, csrc/krylov.hip) -- test infrastructure.
 
   * `store`: a knpemidg.amg-style hierarchy as the device stores it -- CSR values of A, P, R and the coarse (pseudo-)inverse rounded to
-    fp32 (amg.hip: up_csr, amg_finish_impl), dinv / rho / cheb_lower in fp64 -- converted to a working precision: float64, or
+    fp32 (amg_upload.hip: up_csr, amg_finish_impl), dinv / rho / cheb_lower in fp64 -- converted to a working precision: float64, or
     np.longdouble where that has a 64-bit mantissa (`HP`; elsewhere the high-precision run sums its rows with math.fsum).
   * `vcycle`: amg_vcycle_eager, level by level, for [ncol, n] right-hand sides (the columns are independent).
   * `EmiPrecond` / `KnpPrecond`: the two-level preconditioners of pcg_impl / bicgstab_impl around it; `bj_lambda_max`.
   * `bicgstab`: k iterations in the form of bicgstab_impl (the PCG twin is krylov_ref.pcg with `precond` / `iters`).
-  * `launches`: which (kernel, G, NC) instantiations a hierarchy reaches (LAUNCH_BY_DENSITY / launch_csr_on).
+  * `launches`: which (kernel, G, NC) instantiations a hierarchy reaches (amg_vcycle.hip: by_density).
   * `synthetic`: seeded hand-built hierarchies (any density, any level size) for tests/test_amg_ref_host.py and a comparison on the device.
 A `mut = (name, level)` argument applies one deliberate error (MUTATIONS; drop_tail: (name, (level, matrix))) -- the CPU tests show
 that each one is far above the comparison bound (`bound`).
@@ -21,7 +21,7 @@ import scipy.sparse as sp
 
 HP = np.longdouble if np.finfo(np.longdouble).nmant >= 63 else None
 
-# average-row-length limits of LAUNCH_BY_DENSITY / launch_csr_on (csrc/amg.hip; the second one is g4_limit(), KNP_AMG_G4)
+# average-row-length limits of by_density (csrc/amg_vcycle.hip; the second one is g4_limit(), KNP_AMG_G4)
 BANDS = ((12.0, 1), (40.0, 4), (96.0, 8), (math.inf, 64))
 KERNELS = ("k_csr<0>", "k_csr<1>", "k_csr<2>", "k_csr_first", "k_cheb_first_res", "k_cheb_step")
 MUTATIONS = ("no_round_A", "drop_tail", "swap_columns", "short_post_smooth", "no_prolongation", "dense_last_row")
@@ -109,7 +109,7 @@ def store(levels, dtype=np.float64, mut=None, ncol=1):
 
 
 def smooth(L, x, b, zero_guess, steps=None):
-    """amg.hip: smooth() -- Chebyshev polynomial of D^-1 A on [cheb_lower * rho, rho]"""
+    """amg_vcycle.hip: smooth() / amg.hpp: Cheb -- Chebyshev polynomial of D^-1 A on [cheb_lower * rho, rho]"""
     lmax, lmin = L.rho, L.cheb_lower * L.rho
     theta, delta = (lmax + lmin) / 2, (lmax - lmin) / 2
     sigma = theta / delta
@@ -277,14 +277,14 @@ def bicgstab(As, bs, precond, iters, dtype=np.float64):
 
 # ---- which kernel instantiations a hierarchy reaches -----------------------------------------------------------------------------------
 def launches(levels, ncol):
-    """set of (kernel, G, NC) that amg_restrict_tail and amg_vcycle_eager launch through LAUNCH_BY_DENSITY / launch_csr_on"""
+    """set of (kernel, G, NC) that restrict_tail and amg_vcycle_eager launch through by_density"""
     nc = 2 if ncol % 2 == 0 else 1
     out = set()
 
     def hit(kernel, M):
         out.add((kernel, band_G(sp.csr_matrix(M)), nc))
     nl = len(levels)
-    if nl > 1 and levels[0].cheb_degree == 0:                           # amg_restrict_tail_impl
+    if nl > 1 and levels[0].cheb_degree == 0:                           # amg_restrict.hip: restrict_tail
         hit("k_csr<0>", levels[0].R)
     for l in range(nl - 1):                                             # the way down
         L = levels[l]

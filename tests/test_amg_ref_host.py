@@ -1,6 +1,6 @@
 """CPU checks of the host replica of the auxiliary-space preconditioner (tests/amg_ref.py), the reference a comparison of the device's
 k-iteration iterates is meant to use: the replica V-cycle is a symmetric positive operator that preconditions, it equals
-P Ac^-1 P^T where that is what it must be, the hand-built hierarchies reach every instantiation of the density-dispatched kernels of csrc/amg.hip, and each of six
+P Ac^-1 P^T where that is what it must be, the hand-built hierarchies reach every instantiation of the density-dispatched kernels of csrc/amg_vcycle.hip, and each of six
 deliberate errors in the replica moves the k-iteration result by at least 100 times the comparison bound (amg_ref.bound).
 For the KNP solve on the drift-free class table of solve.hip (build_bj_table): the replica's table blocks are one block per table key,
 to the bit; the two block sets give iterates at least 1e6 bounds apart; and the bound exists for every case the device runs.
@@ -92,7 +92,7 @@ def test_two_levels_without_smoothing_are_the_galerkin_correction():
 
 
 def test_hand_built_hierarchies_reach_every_kernel_instantiation():
-    """LAUNCH_BY_DENSITY / launch_csr_on (csrc/amg.hip) choose G in {1, 4, 8, 64} by the average row length (<= 12, <= 40, <= 96, above:
+    """by_density (csrc/amg_vcycle.hip) chooses G in {1, 4, 8, 64} by the average row length (<= 12, <= 40, <= 96, above:
     amg_ref.BANDS) and NC = 2 for an even column count; every synthetic hierarchy is meant to run with one column (EMI) and with two
     (KNP).  No combination is out of reach: k_csr<0> runs on R of every level above a transfer-only or the coarsest one and on P of a
     transfer-only level, k_csr_first on R above a smoothed level, the other four on A and P of smoothed levels."""

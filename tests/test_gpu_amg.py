@@ -1,5 +1,5 @@
-"""Every kernel variant of the AMG V-cycle (csrc/amg.hip) and the transfer / smoother kernels around it (csrc/krylov.hip) against the
-host replica tests/amg_ref.py, vector by vector.
+"""Every kernel variant of the AMG V-cycle (csrc/amg_vcycle.hip, csrc/amg_restrict.hip) and the transfer / smoother kernels around it
+(csrc/krylov.hip) against the host replica tests/amg_ref.py, vector by vector.
 
 The observable is the iterate x_k the device returns after k Krylov iterations from x_0 = 0 at a tolerance it cannot reach (status -3,
 KnpError "did not converge": the documented contract): a deterministic function of b, the operator and the preconditioner.  PCG (EMI,
@@ -53,7 +53,8 @@ Two production cases are ill-conditioned by the rule above and are not run: the 
 7.3e-9) and x_3 on the P2 box with the plain cell blocks (1.2e-9; x_1 and x_2 of that case, 4.1e-11 and 5.9e-10, are run).
 
 Each case also solves twice (same bits: graph replay, swapped x / d1 buffers) and, with several columns, changes one species'
-right-hand side (the others' iterates keep their bits)."""
+right-hand side (the others' iterates keep their bits).  The eager V-cycle (KNP_NO_GRAPH, read once per process; what runs whenever
+capture fails) has a child process of its own: same bound, and the bits of the graph replay."""
 import contextlib
 
 import numpy as np
@@ -269,6 +270,85 @@ def test_knp_iterates_one_hierarchy_per_species(hip_lib, mesh, ns, names):
 def test_knp_iterates_unfused_restriction(hip_lib, monkeypatch):
     monkeypatch.setenv("KNP_FUSE_RESTRICT", "0")
     _check_knp(_ctx("box_P1"), "bands", independent=False)
+
+
+# ---- the eager V-cycle -------------------------------------------------------------------------------------------------------------
+def _eager_cases(c):
+    """x_k of: EMI with `bands` and `bands_t0`, both DG smoothers, k = 1, 2, 3; KNP with `bands` shared by the two species, k = 1, 2 --
+    uploads and solves in the order of _check_emi / _check_knp.  Run by the test below (graph replay) and by its child process
+    tests/amg_eager_worker.py (KNP_NO_GRAPH=1)."""
+    dev, out = c.dev, {}
+    for name in ("bands", "bands_t0"):
+        for cheb in (False, True):
+            dev.emi_residual_target(0.0)
+            dev.amg_upload(0, c.host.dg2cg, c.levels(name))
+            dev.set_emi_dg_smoother(cheb)
+            try:
+                for k in (1, 2, 3):
+                    out["emi %s %d %d" % (name, cheb, k)] = c.emi(k, c.b_emi)
+            finally:
+                dev.set_emi_dg_smoother(None)
+                dev.amg_clear(0)
+                dev.upload(c.A.F_B_EMI, c.b_emi)
+    for s in range(c.ns):
+        dev.amg_clear(1 + s)
+    dev.amg_upload(1, c.host.dg2cg, c.levels("bands", True), ncol=c.ns)
+    try:
+        for k in (1, 2):
+            out["knp bands %d" % k] = c.knp(k, c.b_knp)
+    finally:
+        for s in range(c.ns):
+            dev.amg_clear(1 + s)
+        dev.upload(c.A.F_B_KNP, c.b_knp)
+        dev.upload(c.A.F_C, c.host.pb.c)
+    return out
+
+
+def test_eager_vcycle_matches_the_replica_and_the_graph_replay(hip_lib, tmp_path, monkeypatch, capfd):
+    """KNP_NO_GRAPH is read once per process, and the eager V-cycle is what runs whenever graph capture fails: one fresh child process
+    with KNP_NO_GRAPH=1 runs _eager_cases on box_P1 (it reports no capture).  Its iterates must lie within the replica's bound, exactly
+    as in _check_emi / _check_knp, and have the bits of this process's graph-replay run of the same cases: the same kernels in the
+    same order on the same data.  That this process did replay is asserted too: with KNP_DEBUG the library reports every capture, one per
+    uploaded hierarchy (four EMI uploads and the shared KNP one), each with an instantiated graph."""
+    import os
+    import subprocess
+    import sys
+    c = _ctx("box_P1")
+    assert c.ns == 2
+    out = str(tmp_path / "eager.npz")
+    env = dict(os.environ, KNP_NO_GRAPH="1", KNP_DEBUG="1")
+    run = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "amg_eager_worker.py"), out], env=env,
+                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=240)
+    assert run.returncode == 0, run.stdout[-3000:]
+    assert "graph capture" not in run.stdout and "BeginCapture" not in run.stdout, "the child captured a graph"
+    eager = dict(np.load(out))
+    monkeypatch.setenv("KNP_DEBUG", "1")                              # (read at every capture)
+    capfd.readouterr()
+    replay = _eager_cases(c)
+    captures = [l for l in capfd.readouterr().err.splitlines() if "V-cycle graph capture" in l]
+    monkeypatch.delenv("KNP_DEBUG")
+    assert len(captures) == 5 and all("rc=0 end=0 exec=0x" in l for l in captures), captures
+    assert sorted(eager) == sorted(replay) and len(eager) == 14
+    bad, other_bits = [], []
+    for key, x in eager.items():
+        system, name, *rest = key.split()
+        k = int(rest[-1])
+        if system == "emi":
+            cheb = bool(int(rest[0]))
+            x64 = ar.emi_xk(c.host, c.levels(name), cheb, k, b=c.b_emi)[None]
+            xhp = ar.emi_xk(c.host, c.levels(name), cheb, k, ar.hp_dtype(), b=c.b_emi)[None]
+        else:
+            x64 = ar.knp_xk(c.host, c.levels(name, True), k, bs=c.b_knp, blocks="cell")
+            xhp = ar.knp_xk(c.host, c.levels(name, True), k, ar.hp_dtype(), bs=c.b_knp, blocks="cell")
+        for s in range(len(x64)):
+            bd, err = ar.bound(x64[s], xhp[s]), np.abs(np.atleast_2d(x)[s] - x64[s]).max()
+            _report("eager %s species %d" % (key, s), k, bd, err, np.abs(xhp[s]).max())
+            if not err <= bd:
+                bad.append((key, s, err / bd))
+        if not np.array_equal(x, replay[key]):
+            other_bits.append((key, float(np.abs(x - replay[key]).max())))
+    assert not bad, bad
+    assert not other_bits, ("eager and replayed V-cycles gave other bits", other_bits)
 
 
 # ---- KNP on the drift-free class table (solve.hip: build_bj_table) -----------------------------------------------------------------

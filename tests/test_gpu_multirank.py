@@ -49,7 +49,7 @@ def _single_rank(n_axons, steps, method, degree=1):
                                                         (3, "thin", 4, 1), (2, "p2", 4, 1), (2, "slab", 4, 0)])
 def test_partitioned_solver_with_several_ranks_on_one_gpu(hip_lib, tmp_path, monkeypatch, world, method, n_axons, dist0):
     # dist0 = 1: the finest conforming level ROW-DISTRIBUTED (sub-assembled matrices, point-to-point exchange of the shared dofs, one
-    # all-reduce of the level-1 residual; csrc/amg.hip dist0) -- the default of a partitioned run; 0: replicated behind an all-reduce of
+    # all-reduce of the level-1 residual; csrc/amg_vcycle.hip dist0) -- the default of a partitioned run; 0: replicated behind an all-reduce of
     # the level-0 residual (rounds 1-2).  The small meshes get a coarse-size limit that leaves at least one level below the finest.
     steps = 3
     monkeypatch.setenv("KNP_AMG_DIST0", str(dist0))

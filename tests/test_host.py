@@ -167,6 +167,26 @@ def test_context_table_steps_on_the_host(tmp_path):
     assert run.returncode == 0 and "context tables ok" in run.stdout, run.stdout
 
 
+def test_restriction_tables_on_the_host(tmp_path):
+    """csrc/amg_tables.hpp holds the host steps of knp_amg_begin: the inverse of dg2cg and the tile / slot / part tables whose summation
+    order the tile-wise restriction and the two fused kernels of krylov.hip follow bit for bit.  tools/check_amg_tables.cpp, plain host
+    C++ without a HIP header, builds them on the one-axon box (all cells owned, and a third of them ghosts) for the built-in tile size,
+    1 cell, 3 cells and more cells than the mesh has, and checks their structure, the exact two-stage sum of an integer-valued vector
+    and the cases without tables.  (The same program is what a host sanitizer build runs: its header comment has the command line.)"""
+    import shutil
+    import subprocess
+    import sys
+    cxx = shutil.which(os.environ.get("CXX", "g++"))
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    mesh, exe = str(tmp_path / "small_3d.bin"), str(tmp_path / "check_amg_tables")
+    subprocess.run([sys.executable, os.path.join(ROOT, "tools", "dump_context_mesh.py"), mesh], check=True)
+    subprocess.run([cxx, "-std=c++17", "-O1", "-pthread", "-I", os.path.join(ROOT, "knp-emi-dg_amd", "csrc"),
+                    os.path.join(ROOT, "tools", "check_amg_tables.cpp"), "-o", exe], check=True)
+    run = subprocess.run([exe, mesh], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert run.returncode == 0 and "amg tables ok" in run.stdout, run.stdout
+
+
 def test_product_never_imports_oracle():
     """The oracle is test infrastructure: nothing under knp-emi-dg_amd/ may import or execute it."""
     pkg = os.path.join(ROOT, "knp-emi-dg_amd")

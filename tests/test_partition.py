@@ -138,7 +138,7 @@ def test_halo_exchange_gloo(world, method):
 
 @pytest.mark.parametrize("degree,world,method", [(1, 3, "slab"), (1, 4, "rcb"), (2, 2, "slab"), (2, 3, "rcb")])
 def test_row_distributed_level0_algebra(degree, world, method, monkeypatch):
-    """knpemidg/amg.py: Dist0Space (the row-distributed finest conforming level of a partitioned run, csrc/amg.hip dist0), emulated on
+    """knpemidg/amg.py: Dist0Space (the row-distributed finest conforming level of a partitioned run, csrc/amg_vcycle.hip dist0), emulated on
     the host with every rank's tables: the sub-assembled matrices add up to the global operator, the shared-dof tables of two peers list
     the same dofs in the same order, the rank-ordered accumulation gives every owner the same bits, and one level-0 visit of the V-cycle
     (smooth, residual, restriction, a replicated coarse map, prolongation, smooth) on the distributed data equals the global one."""
@@ -279,7 +279,7 @@ def share_count(D, n):
 def _dist0_worker(rank, world, port, q, method, degree):
     """One rank of test_row_distributed_level0_gloo: holds only ITS rows of the finest conforming level, exchanges the shared dofs with
     its peers through torch.distributed (gloo) and all-reduces the level-1 right-hand side -- the communication pattern of
-    csrc/comm.hip interface_accumulate + csrc/amg.hip amg_vcycle_dist0."""
+    csrc/comm.hip interface_accumulate + csrc/amg_vcycle.hip amg_vcycle_dist0."""
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     os.environ["KNP_AMG_MAXCOARSE"] = "60"

@@ -45,7 +45,8 @@ int main(int argc, char** argv) {
     std::ifstream fs(argv[1], std::ios::binary);
     std::vector<char> raw((std::istreambuf_iterator<char>(fs)), std::istreambuf_iterator<char>());
     if (raw.size() < 64) { std::printf("cannot read %s\n", argv[1]); return 2; }
-    // int64 dim, nv, nc, nc_owned, nf, n_membrane_tags, n_ions, 0; then the arrays below, each padded to 8 bytes
+    // int64 dim, nv, nc, nc_owned, nf, n_membrane_tags, n_ions, ncg; then the arrays below, each padded to 8 bytes (ncg > 0: behind them
+    // dg2cg [nc][NV], which tools/check_amg_tables.cpp reads)
     int64_t hd[8];
     memcpy(hd, raw.data(), sizeof(hd));
     const int dim = (int)hd[0], NV = dim + 1, nmt = (int)hd[5], ni = (int)hd[6];
@@ -58,6 +59,7 @@ int main(int argc, char** argv) {
     };
     auto coords = take(sizeof(double) * nv * dim), cells = take(4 * nc * NV), ctags = take(4 * nc), fcells = take(4 * 2 * nf);
     auto flocal = take(2 * nf), ftags = take(4 * nf), mtags = take(4 * nmt), Draw = take(sizeof(double) * ni * nc);
+    if (hd[7] > 0) take(4 * nc * NV);
     if (off != raw.size()) { std::printf("%s: unexpected size\n", argv[1]); return 2; }
     MeshIn in{dim, NV, nv, nc, nc_owned, nf, (const double*)coords.data(), (const int32_t*)cells.data(), (const uint32_t*)ctags.data(),
               (const int32_t*)fcells.data(), (const int8_t*)flocal.data(), (const uint32_t*)ftags.data(), nmt, (const uint32_t*)mtags.data()};

@@ -1,5 +1,7 @@
 """Writes the arrays knp_ctx_create and knp_set_params receive for the 768-tet one-axon box (tests/common.py: small_3d), in the
-caller's numbering, as the binary file tools/check_context_tables.cpp reads.   usage: python tools/dump_context_mesh.py OUT.bin"""
+caller's numbering, as the binary file tools/check_context_tables.cpp reads; behind them the map dg2cg of the conforming P1 space
+(the cell's vertices; ncg = number of vertices, in the header) that knp_amg_begin receives, for tools/check_amg_tables.cpp.
+usage: python tools/dump_context_mesh.py OUT.bin"""
 import os
 import sys
 
@@ -19,8 +21,10 @@ def main(out):
     mtags = np.asarray([1], dtype=np.uint32)
     arrays = [np.asarray(mesh.coords, dtype=np.float64), np.asarray(mesh.cells, dtype=np.int32), ctags,
               np.asarray(mesh.facet_cells, dtype=np.int32), np.asarray(mesh.facet_local, dtype=np.int8),
-              np.asarray(surf.array(), dtype=np.uint32), mtags, np.asarray(D, dtype=np.float64)]
-    head = np.asarray([mesh.gdim, mesh.coords.shape[0], nc, nc, arrays[3].shape[0], len(mtags), D.shape[0], 0], dtype=np.int64)
+              np.asarray(surf.array(), dtype=np.uint32), mtags, np.asarray(D, dtype=np.float64),
+              np.asarray(mesh.cells, dtype=np.int32)]                  # dg2cg [nc][nd] of P1
+    ncg = mesh.coords.shape[0]
+    head = np.asarray([mesh.gdim, mesh.coords.shape[0], nc, nc, arrays[3].shape[0], len(mtags), D.shape[0], ncg], dtype=np.int64)
     with open(out, "wb") as f:
         f.write(head.tobytes())
         for a in arrays:
