@@ -71,9 +71,9 @@ def solver_parameters(dim, resolution, **extra):
     return namedtuple('solver_params', names)(*vals)
 
 
-def make_solver(dim=3, resolution=0, n_axons=4, degree=1, dt=1.0e-4, verbose=False, mesh_tuple=None, ode_models=None):
+def make_solver(dim=3, resolution=0, n_axons=4, degree=1, dt=1.0e-4, verbose=False, mesh_tuple=None, ode_models=None, ode_method=None):
     """Build a ready-to-run solver for the 2D / 3D idealized geometry (ode_models: {tag: model module} instead of the
-    reference's HH membranes)."""
+    reference's HH membranes; ode_method: their ODE integrator, see Solver.setup_membrane_model)."""
     from knpemidg import setup_worker
     setup_worker.prestart(2)           # the hierarchy helpers start importing now, while the mesh is being built
     from knpemidg import _abi
@@ -92,6 +92,6 @@ def make_solver(dim=3, resolution=0, n_axons=4, degree=1, dt=1.0e-4, verbose=Fal
     S.setup_domain(mesh, subdomains, surfaces)
     S.setup_parameters()
     S.setup_FEM_spaces()
-    S.setup_membrane_model(stim_params, ode_models)
+    S.setup_membrane_model(stim_params, ode_models, ode_method=ode_method)
     _abi._stamp("make_solver: membrane models attached")
     return S

@@ -397,6 +397,22 @@ int knp_ode_step(knp_ctx* ctx, int handle, double t0, double dt, double rtol, do
 int knp_ode_rtc_compile(const char* src, const char* name, void** code, size_t* size, char* log, size_t logcap);
 void knp_ode_rtc_free(void* code);
 int knp_ode_register(knp_ctx* ctx, const void* code, size_t size, const char* kernel_name, int ns, int np);
+/* A second integrator beside Dormand-Prince for stiff models (csrc/ode_stiff.hpp): the extrapolated linearly implicit Euler method,
+ * order 8, with a forward-difference Jacobian; at most 11 states.  Same tables, stimulus, step-size carry-over, stream, asynchrony and
+ * failure flag as the default.
+ *  knp_ode_set_method    : method 0 = Dormand-Prince 5(4) (the default of knp_ode_create), 1 = stiff; knp_ode_step dispatches on it.
+ *                          -1 and the set unchanged for any other value, for more than 11 states under method 1, and for a
+ *                          registered model without a kernel of that method
+ *  knp_ode_register_method: loads the code object of a model's kernel for `method` (knpemidg/ode_rtc.py: source(ode, method)).
+ *                          model >= 1000: attaches it to that registered model (same ns / np, no kernel of that method yet) and
+ *                          returns its id; model < 0: registers a new model that has this kernel only.  knp_ode_register is
+ *                          method 0 on a new model
+ *  knp_ode_stats         : out[4] = accepted steps, rejected steps, right-hand-side calls (Jacobian columns included) and Jacobians,
+ *                          summed over the nodes and the knp_ode_step calls since knp_ode_create; only the stiff kernel counts.
+ *                          Waits for the stream (and reports a pending ODE failure as -4) */
+int knp_ode_set_method(knp_ctx* ctx, int handle, int method);
+int knp_ode_register_method(knp_ctx* ctx, int model, int method, const void* code, size_t size, const char* kernel_name, int ns, int np);
+int knp_ode_stats(knp_ctx* ctx, int handle, int64_t out[4]);
 
 /* ---- host-side setup kernels (no device work): threaded sparse products of the preconditioner setup (knpemidg/amg.py), the
  * counterpart of the BoomerAMG setup PETSc runs inside KSPSetUp (solver.py:433, 505, 688, 767).  CSR, int32 indices, fp64 values.

@@ -4,9 +4,12 @@
 // facets share the launch (ranks that both hold a cut facet compute bitwise identical outputs).
 // Stands in for the per-facet numbalsoda.lsoda loop (reference: src/knpemidg/membrane.py:84-119) for the
 // membrane models of the idealized examples (reference: examples/idealized-geometries/mm_hh.py:118-161).
+// A set may be switched to a second integrator for stiff models (knp_ode_set_method: ode_stiff.hpp, extrapolated linearly implicit
+// Euler); it shares the tables, the stimulus, the step-size carry-over and the failure flag, and adds four step / call counters.
 #include "../../include/knpemi_hip.h"
 #include "knpemi_internal.hpp"
 #include "ode_dp5.hpp"
+#include "ode_stiff.hpp"
 #include <hip/hiprtc.h>
 #include <cstdlib>
 #include <cstring>
@@ -26,6 +29,8 @@ struct OdeSet {
     double* h = nullptr;        // [n] last accepted step size
     int* fail = nullptr;        // device flag: the context's status word KNP_ODE_FAIL_SLOT (read back with the next status poll)
     uint8_t* stim_mask = nullptr;   // [n] rows on which the stimulus parameters are re-imposed every step (membrane.py:98-104)
+    int method = 0;             // integrator of knp_ode_step: 0 = Dormand-Prince 5(4) (ode_dp5.hpp), 1 = stiff (ode_stiff.hpp)
+    unsigned long long* stats = nullptr;   // [4] accepted, rejected, right-hand-side calls, Jacobians: added up by the stiff kernel
     int n_stim = 0;
     int stim_col[ODE_MAX_STIM] = {0};
     double stim_val[ODE_MAX_STIM] = {0};
@@ -34,9 +39,10 @@ struct OdeSet {
 static std::map<knp_ctx*, std::vector<OdeSet>> g_ode;
 
 // a model module's HIP_RHS compiled by hipRTC (knpemidg/ode_rtc.py) and loaded on one context's device
+#define ODE_N_METHODS 2
 struct RtcModel {
-    hipModule_t mod = nullptr;
-    hipFunction_t fn = nullptr;
+    hipModule_t mod[ODE_N_METHODS] = {nullptr, nullptr};     // one code object and kernel per method; either may be absent
+    hipFunction_t fn[ODE_N_METHODS] = {nullptr, nullptr};
     int ns = 0, np = 0;
 };
 static std::map<knp_ctx*, std::vector<RtcModel>> g_rtc;
@@ -207,6 +213,15 @@ __global__ __launch_bounds__(64) void k_ode_step(int64_t n, double t0, double t1
     ode_dp5_step<NS, NP>(BuiltinRhs<MODEL>(), n, t0, t1, rtol, atol, max_steps, states, params, hstore, fail, stim_mask, stim);
 }
 
+template <int MODEL, int NS, int NP>
+__global__ __launch_bounds__(64) void k_ode_step_stiff(int64_t n, double t0, double t1, double rtol, double atol, int max_steps,
+                                                       double* __restrict__ states, double* __restrict__ params,
+                                                       double* __restrict__ hstore, int* __restrict__ fail,
+                                                       const uint8_t* __restrict__ stim_mask, StimArgs stim,
+                                                       unsigned long long* __restrict__ stats) {
+    ode_stiff_step<NS, NP>(BuiltinRhs<MODEL>(), n, t0, t1, rtol, atol, max_steps, states, params, hstore, fail, stim_mask, stim, stats);
+}
+
 // table[node][col] <- facet_field[facet[node]]   (PDE -> ODE, membrane.py:122-139)
 __global__ void k_ode_from_facet(int64_t n, const int32_t* __restrict__ facet, const double* __restrict__ field, int stride,
                                  int col, double* __restrict__ table) {
@@ -300,7 +315,7 @@ void ode_destroy_all(knp_ctx* c) {
     rtc_unload_all(c);
     auto it = g_ode.find(c);
     if (it == g_ode.end()) return;
-    for (auto& S : it->second) { hipFree(S.facet); hipFree(S.states); hipFree(S.params); hipFree(S.h); hipFree(S.stim_mask); }
+    for (auto& S : it->second) { hipFree(S.facet); hipFree(S.states); hipFree(S.params); hipFree(S.h); hipFree(S.stim_mask); hipFree(S.stats); }
     g_ode.erase(it);
 }
 
@@ -308,7 +323,9 @@ static void rtc_unload_all(knp_ctx* c) {
     auto it = g_rtc.find(c);
     if (it == g_rtc.end()) return;
     host_stream_sync(c, c->stream);                // no launch of a registered kernel may still be in flight
-    for (auto& R : it->second) hipModuleUnload(R.mod);
+    for (auto& R : it->second)
+        for (int q = 0; q < ODE_N_METHODS; ++q)
+            if (R.mod[q]) hipModuleUnload(R.mod[q]);
     g_rtc.erase(it);
 }
 
@@ -339,6 +356,8 @@ int knp_ode_create(knp_ctx* c, int model, int64_t n, const int32_t* facets, int 
     HIPCHK(c, hipMemset(S.stim_mask, 0, m));
     S.fail = c->status + KNP_ODE_FAIL_SLOT;
     HIPCHK(c, hipMemset(S.h, 0, m * sizeof(double)));
+    HIPCHK(c, hipMalloc((void**)&S.stats, 4 * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemset(S.stats, 0, 4 * sizeof(unsigned long long)));
     if (n) {
         HIPCHK(c, host_memcpy(c, S.facet, facets, n * sizeof(int32_t), hipMemcpyHostToDevice));
         HIPCHK(c, host_memcpy(c, S.states, states, n * ns * sizeof(double), hipMemcpyHostToDevice));
@@ -434,12 +453,27 @@ int knp_ode_step(knp_ctx* c, int handle, double t0, double dt, double rtol, doub
         // a registered HIP_RHS kernel: same integrator text, block size, arguments and failure flag as k_ode_step
         const RtcModel* R = rtc_model(c, S->model);
         if (!R) { c->err = "ode_step: registered model is gone"; return -1; }
+        if (!R->fn[S->method]) { c->err = "ode_step: the registered model has no kernel for the set's method"; return -1; }
         int64_t n = S->n;
         double t1 = t0 + dt;
         int ms = max_steps;
         const uint8_t* mask = S->stim_mask;
-        void* args[] = {&n, &t0, &t1, &rtol, &atol, &ms, &S->states, &S->params, &S->h, &S->fail, &mask, &st};
-        HIPCHK(c, hipModuleLaunchKernel(R->fn, g.x, 1, 1, b.x, 1, 1, 0, c->stream, args, nullptr));
+        void* args[] = {&n, &t0, &t1, &rtol, &atol, &ms, &S->states, &S->params, &S->h, &S->fail, &mask, &st, &S->stats};   // the last one: stiff only
+        HIPCHK(c, hipModuleLaunchKernel(R->fn[S->method], g.x, 1, 1, b.x, 1, 1, 0, c->stream, args, nullptr));
+        return 0;
+    }
+    if (S->method == 1) {
+#define ODE_LAUNCH_STIFF(MODEL, NS, NP)                                                                                          \
+    hipLaunchKernelGGL((k_ode_step_stiff<MODEL, NS, NP>), g, b, 0, c->stream, S->n, t0, t0 + dt, rtol, atol, max_steps, S->states, \
+                       S->params, S->h, S->fail, (const uint8_t*)S->stim_mask, st, S->stats)
+        if (S->model == 1) ODE_LAUNCH_STIFF(1, 4, 17);
+        else if (S->model == 2) ODE_LAUNCH_STIFF(2, 4, 17);
+        else if (S->model == 3) ODE_LAUNCH_STIFF(3, 4, 17);
+        else if (S->model == 4) ODE_LAUNCH_STIFF(4, 1, 19);
+        else if (S->model == 5) ODE_LAUNCH_STIFF(5, 1, 15);
+        else ODE_LAUNCH_STIFF(6, 11, 12);
+#undef ODE_LAUNCH_STIFF
+        HIPCHK(c, hipGetLastError());
         return 0;
     }
 #define ODE_LAUNCH(MODEL, NS, NP)                                                                                          \
@@ -501,26 +535,78 @@ int knp_ode_rtc_compile(const char* src, const char* name, void** code, size_t* 
 
 void knp_ode_rtc_free(void* code) { free(code); }
 
-// load a code object of knp_ode_rtc_compile on the context's device; the returned id (>= 1000) is a model id for knp_ode_create
-int knp_ode_register(knp_ctx* c, const void* code, size_t size, const char* kernel_name, int ns, int np) {
+// load a code object of knp_ode_rtc_compile on the context's device as the kernel of `method`; model < 0: of a new model, whose id
+// (>= 1000, a model id for knp_ode_create) is returned; else of the registered model `model`, which has none for that method yet
+static int rtc_register(knp_ctx* c, int model, int method, const void* code, size_t size, const char* kernel_name, int ns, int np) {
     if (!c) return -1;
     if (!code || !size || !kernel_name) { c->err = "ode_register: no code object / kernel name"; return -1; }
     if (ns < 1 || ns > 32 || np < 1 || np > 64) { c->err = "ode_register: 1..32 states and 1..64 parameters"; return -1; }
+    if (method == 1 && ns > ODE_STIFF_MAX_STATES) { c->err = "ode_register: the stiff integrator takes at most 11 states"; return -1; }
+    if (model >= 0) {
+        const RtcModel* R = rtc_model(c, model);
+        if (!R) { c->err = "ode_register: model id not registered on this context"; return -1; }
+        if (R->ns != ns || R->np != np) { c->err = "ode_register: state / parameter counts differ from the registered model's"; return -1; }
+        if (R->fn[method]) { c->err = "ode_register: the model already has a kernel for this method"; return -1; }
+    }
     (void)size;                                      // hipModuleLoadData reads the ELF's own size
     HIPCHK(c, hipSetDevice(c->device));
-    RtcModel R;
-    R.ns = ns;
-    R.np = np;
-    HIPCHK(c, hipModuleLoadData(&R.mod, code));
-    const hipError_t e = hipModuleGetFunction(&R.fn, R.mod, kernel_name);
+    hipModule_t mod = nullptr;
+    hipFunction_t fn = nullptr;
+    HIPCHK(c, hipModuleLoadData(&mod, code));
+    const hipError_t e = hipModuleGetFunction(&fn, mod, kernel_name);
     if (e != hipSuccess) {
-        hipModuleUnload(R.mod);
+        hipModuleUnload(mod);
         c->err = std::string("ode_register: kernel ") + kernel_name + " not in the code object: " + hipGetErrorString(e);
         return -2;
     }
     auto& v = g_rtc[c];
-    v.push_back(R);
-    return ODE_RTC_ID0 + (int)v.size() - 1;
+    if (model < 0) {
+        RtcModel R;
+        R.ns = ns;
+        R.np = np;
+        v.push_back(R);
+        model = ODE_RTC_ID0 + (int)v.size() - 1;
+    }
+    v[model - ODE_RTC_ID0].mod[method] = mod;
+    v[model - ODE_RTC_ID0].fn[method] = fn;
+    return model;
+}
+
+int knp_ode_register(knp_ctx* c, const void* code, size_t size, const char* kernel_name, int ns, int np) {
+    return rtc_register(c, -1, 0, code, size, kernel_name, ns, np);
+}
+
+// the kernel of one method (ode_rtc.source(ode, method)) for a registered model, or (model < 0) for a new one that has this kernel only
+int knp_ode_register_method(knp_ctx* c, int model, int method, const void* code, size_t size, const char* kernel_name, int ns, int np) {
+    if (!c) return -1;
+    if (method < 0 || method >= ODE_N_METHODS) { c->err = "ode_register_method: 0 = DP5, 1 = stiff"; return -1; }
+    return rtc_register(c, model, method, code, size, kernel_name, ns, np);
+}
+
+// 0 = Dormand-Prince 5(4), the default; 1 = stiff.  -1 and the set unchanged for anything else, or (with the context's error text) for a
+// registered model that has no kernel of that method
+int knp_ode_set_method(knp_ctx* c, int handle, int method) {
+    OdeSet* S = get_set(c, handle);
+    if (!S) return -1;
+    if (method < 0 || method >= ODE_N_METHODS) { c->err = "ode_set_method: 0 = DP5, 1 = stiff"; return -1; }
+    if (method == 1 && S->ns > ODE_STIFF_MAX_STATES) { c->err = "ode_set_method: the stiff integrator takes at most 11 states"; return -1; }
+    if (S->model >= ODE_RTC_ID0) {
+        const RtcModel* R = rtc_model(c, S->model);
+        if (!R || !R->fn[method]) { c->err = "ode_set_method: the registered model has no kernel for this method"; return -1; }
+    }
+    S->method = method;
+    return 0;
+}
+
+// counters of the stiff kernel since the set was created: accepted steps, rejected steps, right-hand-side calls, Jacobians (zeros under DP5)
+int knp_ode_stats(knp_ctx* c, int handle, int64_t out[4]) {
+    OdeSet* S = get_set(c, handle);
+    if (!S || !out) return -1;
+    { const int rc_ = sync_check_ode(c); if (rc_) return rc_; }
+    unsigned long long v[4];
+    HIPCHK(c, host_memcpy(c, v, S->stats, sizeof(v), hipMemcpyDeviceToHost));
+    for (int q = 0; q < 4; ++q) out[q] = (int64_t)v[q];
+    return 0;
 }
 
 }  // extern "C"

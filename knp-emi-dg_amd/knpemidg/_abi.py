@@ -98,6 +98,9 @@ SIGNATURES = {
     "knp_ode_rtc_compile": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]),
     "knp_ode_rtc_free": (None, [C.c_void_p]),
     "knp_ode_register": (C.c_int, [_ctxp, C.c_char_p, C.c_size_t, C.c_char_p, C.c_int, C.c_int]),
+    "knp_ode_set_method": (C.c_int, [_ctxp, C.c_int, C.c_int]),
+    "knp_ode_register_method": (C.c_int, [_ctxp, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_int, C.c_int]),
+    "knp_ode_stats": (C.c_int, [_ctxp, C.c_int, _i64p]),
     "knp_amg_begin": (C.c_int, [_ctxp, C.c_int, C.c_int64, _i32p, _i32p, _i32p]),
     "knp_amg_columns": (C.c_int, [_ctxp, C.c_int, C.c_int]),
     "knp_amg_level": (C.c_int, [_ctxp, C.c_int, C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_double, C.c_int, C.c_double,
@@ -488,6 +491,7 @@ class Device:
         self.degree = int(degree)
         self._pending = []                 # queued PDE<->ODE column copies: (handle, to_facet, what, col, field, offset)
         self._rtc_ids = {}                 # kernel name of a registered HIP_RHS model -> its device model id (knp_ode_register)
+        self._rtc_methods = {}             # device model id -> the methods whose kernels are loaded (knp_ode_register_method)
         self._tmp_slot = -1                # rotating scratch slot of facet_trace results
         self._tmp_gen = [0] * FACET_TMP_SLOTS
         if degree != 1:
@@ -787,18 +791,37 @@ class Device:
         """Asynchronous (no host round trip); a failed node surfaces as KnpError at the next solve / sync / table read."""
         self._chk(self.lib.knp_ode_step(self.ctx, handle, t0, dt, rtol, atol), "knp_ode_step")
 
-    def ode_register(self, ode):
-        """Device model id (>= 1000) of a model module that carries its right-hand side as HIP_RHS (knpemidg/ode_rtc.py):
-        compiled once per process (or taken from the compile `ode_rtc.prefetch` started), loaded once per context.
-        A compile error raises KnpError with the hipRTC log."""
+    def ode_register(self, ode, method="dp5"):
+        """Device model id (>= 1000) of a model module that carries its right-hand side as HIP_RHS (knpemidg/ode_rtc.py), with the
+        kernel of `method` ("dp5" or "stiff") loaded: compiled once per process (or taken from the compile `ode_rtc.prefetch`
+        started), loaded once per context; only the methods asked for are compiled.  A compile error raises KnpError with the
+        hipRTC log."""
         from knpemidg import ode_rtc
-        kernel, ns, np_, code = ode_rtc.compiled(ode)
-        if kernel not in self._rtc_ids:
-            mid = self.lib.knp_ode_register(self.ctx, code, len(code), kernel.encode(), ns, np_)
+        from knpemidg.membrane import ODE_METHODS, check_ode_method
+        method = check_ode_method(method)
+        key = ode_rtc.source(ode)[1]                 # the DP5 kernel's name: a hash of everything that defines the model
+        mid = self._rtc_ids.get(key, -1)
+        if method not in self._rtc_methods.get(mid, ()):
+            kernel, ns, np_, code = ode_rtc.compiled(ode, method)
+            mid = self.lib.knp_ode_register_method(self.ctx, mid, ODE_METHODS.index(method), code, len(code), kernel.encode(), ns, np_)
             if mid < 0:
-                self._chk(mid, "knp_ode_register")
-            self._rtc_ids[kernel] = mid
-        return self._rtc_ids[kernel]
+                self._chk(mid, "knp_ode_register_method")
+            self._rtc_ids[key] = mid
+            self._rtc_methods.setdefault(mid, set()).add(method)
+        return mid
+
+    def ode_set_method(self, handle, method):
+        """Integrator of a set: 0 / "dp5" (the default) or 1 / "stiff"."""
+        if isinstance(method, str):
+            from knpemidg.membrane import ODE_METHODS, check_ode_method
+            method = ODE_METHODS.index(check_ode_method(method))
+        self._chk(self.lib.knp_ode_set_method(self.ctx, handle, int(method)), "knp_ode_set_method")
+
+    def ode_stats(self, handle):
+        """[accepted steps, rejected steps, right-hand-side calls, Jacobians] of the stiff kernel since the set was created."""
+        out = np.zeros(4, dtype=np.int64)
+        self._chk(self.lib.knp_ode_stats(self.ctx, handle, _p(out, _i64p)), "knp_ode_stats")
+        return out
 
     # -- auxiliary-space AMG (knpemidg/amg.py builds, csrc/amg_upload.hip receives, csrc/amg_vcycle.hip applies) ------------------
     def amg_interface(self, n_local, peers, lists, uvtx, aptr, asrc):

@@ -88,6 +88,134 @@ def integrate_batch(rhs, t0, t1, y, params, rtol=1.0e-8, atol=1.0e-12, h0=None, 
     return y, h
 
 
+# --- the stiff integrator (csrc/ode_stiff.hpp restated in numpy): extrapolated linearly implicit Euler
+ODE_METHODS = ("dp5", "stiff")
+ODE_STIFF_K = 8                      # columns of the extrapolation table = order of the step (ODE_STIFF_K of csrc/ode_stiff.hpp)
+ODE_STIFF_MAX_STATES = 11            # the device kernel unrolls J, LU and the table over the states (ODE_STIFF_MAX_STATES there)
+ODE_STIFF_FD_REL = 2.0 ** -26        # sqrt(eps) of a double, and the smallest |y_j| the Jacobian increment is scaled by
+ODE_STIFF_FD_FLOOR = 1.0e-5
+ODE_STATS = ("accepted", "rejected", "rhs_calls", "jacobians")
+
+
+def check_ode_method(method):
+    """`method` as one of ODE_METHODS (None = the default, "dp5"); ValueError naming the allowed values otherwise."""
+    if method is None:
+        return ODE_METHODS[0]
+    if not isinstance(method, str) or method not in ODE_METHODS:
+        raise ValueError("ODE method %r: allowed values are %s" % (method, ", ".join(repr(m) for m in ODE_METHODS)))
+    return method
+
+
+def _lu_rows(A):
+    """In-place LU with partial pivoting of every A[i] ([n, NS, NS]), elementwise over the rows of the batch; returns piv [n, NS]."""
+    n, ns, _ = A.shape
+    ar = np.arange(n)
+    piv = np.empty((n, ns), dtype=np.int64)
+    for c in range(ns):
+        p = c + np.argmax(np.abs(A[:, c:, c]), axis=1)              # the first largest entry, as the kernel's strict `>`
+        piv[:, c] = p
+        rc, rp = A[ar, c, :].copy(), A[ar, p, :].copy()
+        A[ar, c, :] = rp
+        A[ar, p, :] = rc
+        for r in range(c + 1, ns):
+            l = A[:, r, c] / A[:, c, c]
+            A[:, r, c] = l
+            A[:, r, c + 1:] -= l[:, None] * A[:, c, c + 1:]
+    return piv
+
+
+def _lu_solve_rows(A, piv, b):
+    """x of (LU) x = P b for every row, in place in b [n, NS]."""
+    n, ns = b.shape
+    ar = np.arange(n)
+    for c in range(ns):
+        bc, bp = b[ar, c].copy(), b[ar, piv[:, c]].copy()
+        b[ar, c] = bp
+        b[ar, piv[:, c]] = bc
+    for r in range(1, ns):
+        for c in range(r):
+            b[:, r] -= A[:, r, c] * b[:, c]
+    for r in range(ns - 1, -1, -1):
+        for c in range(r + 1, ns):
+            b[:, r] -= A[:, r, c] * b[:, c]
+        b[:, r] /= A[:, r, r]
+    return b
+
+
+def integrate_batch_stiff(rhs, t0, t1, y, params, rtol=1.0e-8, atol=1.0e-12, h0=None, max_steps=100000, K=ODE_STIFF_K,
+                          fixed_h=None, stats=None):
+    """Advance all rows of `y` from t0 to t1 with the extrapolated linearly implicit Euler method of csrc/ode_stiff.hpp (the same
+    arithmetic, step by step): per basic step H one forward-difference Jacobian J at (t, y), and for the substep counts n = 1..K the
+    n linearly implicit Euler steps  (I - (H/n) J) d = (H/n) f(t_m + H/n, y_m),  y_{m+1} = y_m + d;  the K results are extrapolated in
+    an Aitken-Neville table to T_KK (order K), the error estimate is T_KK - T_K,K-1 in the weighted max norm of integrate_batch, the
+    next step is H 0.9 err^(-1/K) clipped to [0.2, 5] H.  Every table entry has R(inf) = 0 and is A(alpha)-stable with alpha above
+    89 degrees for the harmonic sequence (Hairer & Wanner, Solving ODEs II, section IV.9).  Like integrate_batch every row carries its
+    own time and step and only elementwise operations touch the batch, so a row's result does not depend on the other rows.
+    fixed_h: take steps of exactly this size (the last one shortened to end on t1), all accepted -- for order measurements.
+    stats: a dict that receives the sums over the rows of ODE_STATS."""
+    n, ns = y.shape
+    y = y.copy()
+    t = np.full(n, float(t0))
+    h = np.full(n, (t1 - t0) / 16) if h0 is None else np.array(h0, dtype=np.float64, copy=True)
+    if h.shape != (n,):
+        h = np.full(n, (t1 - t0) / 16)
+    h = np.where(h > 0.0, h, (t1 - t0) / 16)
+    if fixed_h is not None:
+        h = np.full(n, float(fixed_h))
+    done = np.zeros(n, dtype=bool)
+    tiny = 1e-14 * max(abs(t1), 1e-30)
+    steps = 0
+    count = np.zeros(4, dtype=np.int64)
+    eye = np.eye(ns)
+    J = np.empty((n, ns, ns))
+    T = [None] * K
+    while not done.all() and steps < max_steps:
+        hh = np.where(done, 0.0, np.minimum(h, t1 - t))
+        f0 = rhs(t, y, params)
+        for c in range(ns):
+            d = ODE_STIFF_FD_REL * np.maximum(np.abs(y[:, c]), ODE_STIFF_FD_FLOOR)
+            yp = y.copy()
+            yp[:, c] = y[:, c] + d
+            J[:, :, c] = (rhs(t, yp, params) - f0) / d[:, None]
+        for j in range(K):
+            hs = hh / (j + 1)
+            A = eye - hs[:, None, None] * J
+            piv = _lu_rows(A)
+            yy = y
+            for m in range(j + 1):
+                b = hs[:, None] * rhs(t + (m + 1) * hs, yy, params)
+                yy = yy + _lu_solve_rows(A, piv, b)
+            T[j] = yy
+            for k in range(j - 1, -1, -1):                           # T[k] <- T_{j, j-k+1}: in place, the row above still in T[k]
+                T[k] = T[k + 1] + (T[k + 1] - T[k]) / ((j + 1.0) / (k + 1.0) - 1.0)
+        ynew = T[0]
+        scale = np.maximum(atol + rtol * np.maximum(np.abs(y), np.abs(ynew)), 1e-300)
+        e = np.max(np.abs(T[0] - T[1]) / scale, axis=1)
+        e = np.where(np.isfinite(e), e, 1e10)
+        steps += 1
+        ok = (e <= 1.0) | (hh < tiny)
+        if fixed_h is not None:
+            ok = np.ones(n, dtype=bool)
+        acc = ok & ~done
+        live = int((~done).sum())
+        count += (int(acc.sum()), live - int(acc.sum()), live * (1 + ns + K * (K + 1) // 2), live)
+        t = np.where(acc, t + hh, t)
+        y = np.where(acc[:, None], ynew, y)
+        done |= acc & (t >= t1 - 1e-15 * abs(t1))
+        fac = np.clip(0.9 * (1.0 / np.maximum(e, 1e-10)) ** (1.0 / K), 0.2, 5.0)
+        if fixed_h is None:
+            h = np.where(done, h, hh * fac)
+    if stats is not None:
+        for name, v in zip(ODE_STATS, count):
+            stats[name] = stats.get(name, 0) + int(v)
+    if steps >= max_steps and not done.all():
+        raise AssertionError("ODE integrator did not reach the end time")   # `assert success`, membrane.py:113
+    rhs(np.full(n, float(t1)), y, params)                 # leave I_ch_k evaluated at the end state
+    if stats is not None:
+        stats["rhs_calls"] += n
+    return y, h
+
+
 def _EVERYWHERE(x):
     return True
 
@@ -95,7 +223,11 @@ def _EVERYWHERE(x):
 class MembraneModel:
     """ODE on the membrane facets where facet_f == tag (reference: membrane.py:7-41)."""
 
-    def __init__(self, ode, facet_f, tag, V):
+    def __init__(self, ode, facet_f, tag, V, ode_method=None):
+        """ode_method: "dp5" (Dormand-Prince 5(4)) or "stiff" (extrapolated linearly implicit Euler); None takes the module's
+        ODE_METHOD, and "dp5" if it has none."""
+        self._method = check_ode_method(ode_method if ode_method is not None else getattr(ode, "ODE_METHOD", None))
+        self._host_stats = {}
         mesh = facet_f.mesh()
         assert mesh.gdim - 1 == facet_f.dim()
         assert isinstance(tag, int)
@@ -129,14 +261,28 @@ class MembraneModel:
         if model is None:
             if getattr(self.ode, "HIP_RHS", None) is None:
                 return False
-            model = dev.ode_register(self.ode)
+            model = dev.ode_register(self.ode, self._method)
         self._handle = dev.ode_create(model, self.indices, self._states, self._parameters)
+        if self._method != ODE_METHODS[0]:
+            dev.ode_set_method(self._handle, self._method)
         self._dev = dev
         return True
 
     @property
     def on_device(self):
         return self._dev is not None
+
+    @property
+    def ode_method(self):
+        """The integrator this model is stepped with: "dp5" or "stiff"."""
+        return self._method
+
+    def ode_stats(self):
+        """Counters of the stiff integrator since the model was set up, summed over its nodes: {'accepted', 'rejected', 'rhs_calls',
+        'jacobians'} (steps, right-hand-side calls with the Jacobian columns, Jacobians); zeros under "dp5"."""
+        if self.on_device:
+            return dict(zip(ODE_STATS, (int(v) for v in self._dev.ode_stats(self._handle))))
+        return {name: int(self._host_stats.get(name, 0)) for name in ODE_STATS}
 
     @property
     def handle(self):
@@ -241,7 +387,10 @@ class MembraneModel:
         mask = np.fromiter(map(stimulus_locator, self.dof_locations), dtype=bool, count=self.nodes)
         for key, value in stimulus.items():
             self._parameters[mask, self.ode.parameter_indices(key)] = value
-        if self.nodes:
+        if self.nodes and self._method == "stiff":
+            self._states, self._h = integrate_batch_stiff(self.ode.rhs, self.time, self.time + dt, self._states, self._parameters,
+                                                          rtol=1.0e-8, atol=0.0, h0=self._h, stats=self._host_stats)
+        elif self.nodes:
             self._states, self._h = integrate_batch(self.ode.rhs, self.time, self.time + dt, self._states,
                                                     self._parameters, rtol=1.0e-8, atol=0.0, h0=self._h)
         self.time = self.time + dt

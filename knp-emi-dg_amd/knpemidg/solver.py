@@ -207,16 +207,28 @@ class Solver:
         return np.concatenate([x, np.stack(mids, axis=1)], axis=1)
 
     # ------------------------------------------------------------------ setup_membrane_model (solver.py:228-267)
-    def setup_membrane_model(self, stim_params, odes):
+    def setup_membrane_model(self, stim_params, odes, ode_method=None):
+        """ode_method: the ODE integrator, "dp5" or "stiff" (membrane.ODE_METHODS), for every model or as {tag: method}; None, or a tag
+        the dict leaves out, takes the model module's ODE_METHOD (default "dp5").  Anything else raises ValueError."""
+        from knpemidg.membrane import check_ode_method
+        if isinstance(ode_method, dict):
+            unknown = [t for t in ode_method if int(t) not in [int(u) for u in odes.keys()]]
+            if unknown:
+                raise ValueError("ode_method names tags %s that have no membrane model" % unknown)
+            by_tag = {int(t): m for t, m in ode_method.items()}
+        else:
+            by_tag = {int(t): ode_method for t in odes.keys()}
+        methods = {int(t): check_ode_method(by_tag.get(int(t)) if by_tag.get(int(t)) is not None else getattr(ode, "ODE_METHOD", None))
+                   for t, ode in odes.items()}
         self.stimulus = stim_params.stimulus
         self.stimulus_locator = stim_params.stimulus_locator
         self.mem_models = []
         if self.use_device_ode:
             # HIP_RHS models compile (host only) on a worker thread while the context and the helpers start; attach_device joins
-            ode_rtc.prefetch(odes.values())
+            ode_rtc.prefetch(odes.values(), [methods[int(t)] for t in odes.keys()])
         self._ensure_device(membrane_tags=[int(t) for t in odes.keys()])
         for tag, ode in odes.items():
-            ode_model = MembraneModel(ode, facet_f=self.surfaces, tag=int(tag), V=self.Q)
+            ode_model = MembraneModel(ode, facet_f=self.surfaces, tag=int(tag), V=self.Q, ode_method=methods[int(tag)])
             ode_model.set_parameter_values({'Cm': lambda x: self.params.C_M})
             on_dev = self.use_device_ode and ode_model.attach_device(self.dev)
             I_ch_k = {}
@@ -1064,6 +1076,9 @@ class Solver:
         models = [{"name": getattr(m['ode'].ode, "__name__", "ode").split(".")[-1], "tag": int(m['ode'].tag), "nodes": int(m['ode'].nodes),
                    "on_device": bool(m['ode'].on_device), "states": _names(m['ode'].ode, "state"), "parameters": _names(m['ode'].ode, "parameter")}
                   for m in self.mem_models]
+        for entry, m in zip(models, self.mem_models):        # only when it is not the default: files from before the choice keep loading
+            if m['ode'].ode_method != "dp5":
+                entry["ode_method"] = m['ode'].ode_method
         sp = getattr(self, "solver_params", None)
         ref = getattr(self, "_amg_refresh", None) or {}
         return {
