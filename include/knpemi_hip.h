@@ -331,6 +331,34 @@ int knp_rec_add_states_part(knp_ctx* ctx, int64_t n_channels, const int64_t* cha
 int knp_rec_add_map_part(knp_ctx* ctx, int64_t n_global, int64_t n, const int32_t* facets, const int64_t* positions, double threshold,
                          double repolarisation);
 
+/* ---- fields on a regular voxel grid (csrc/grid.hip) ---------------------------------------
+ * Between the recorder's few probes and a download of every DoF: phi and the concentrations sampled at the points of a regular
+ * grid, a dense frame [n_fields][nz][ny][nx] ([n_fields][ny][nx] in 2D; x runs fastest) whose size the caller chooses.  Point i of
+ * axis k is lo[k] + i h[k]; an axis with shape[k] = 1 sits at lo[k] (a slice of a 3D mesh).  The owner of a point is, among the cells
+ * whose smallest barycentric coordinate is >= -tol (and, with n_tags > 0, whose subdomain tag is one of tags), the one with the lowest
+ * id in the CALLER's numbering (knp_state_cell_order; the rule of knpemidg/recorder.py: locate_points); a point no cell contains has
+ * owner -1, tag -1 and NaN in every field -- not an error, a grid may stick out of the mesh.  Value = sum_a w_a(lambda) u[cell nd + a]
+ * with the nodal basis in the local dof order of knp_set_tabulation.  The grid holds no step-to-step state: knp_state_describe
+ * reports the same blocks with and without one.
+ *  knp_grid_create : field ids: 0 = phi, 1 + k = solved concentration k, n_ions = the eliminated ion; f32 != 0: frames in fp32.
+ *                    Everything is checked before anything is allocated (finite lo and h, h > 0 where shape > 1, shape >= 1, fewer
+ *                    than 2^31 points, tol >= 0, at most 8 tags, known field ids, at most 8 grids per context); a failure leaves the
+ *                    context as it was.  Runs the locate pass (one thread per cell, integer atomicMin per point: deterministic) and the
+ *                    weights pass, and waits for them.  Returns the handle >= 0, or a negative status; -7 with a communicator active
+ *                    (several ranks), without entering a collective.
+ *  knp_grid_points : owner[npts] (caller's cell ids) and tag[npts] of the points; either may be null
+ *  knp_grid_sample : one frame of the fields as they are now: kernel, asynchronous copy into one of two pinned host buffers and an
+ *                    event, all on the context's stream; -5 while two frames wait to be fetched
+ *  knp_grid_fetch  : waits for the event of the oldest waiting frame only and copies it to out[bytes], bytes = n_fields x npts x 8 (4)
+ *  knp_grid_timing : device milliseconds of the locate and weights passes, and of the kernel and the copy of the last fetched frame */
+int knp_grid_create(knp_ctx* ctx, const double* lo, const double* h, const int64_t* shape, double tol, int n_tags, const uint32_t* tags,
+                    int n_fields, const int32_t* fields, int f32);
+int knp_grid_points(knp_ctx* ctx, int grid, int32_t* owner, int32_t* tag);
+int knp_grid_sample(knp_ctx* ctx, int grid);
+int knp_grid_fetch(knp_ctx* ctx, int grid, void* out, size_t bytes);
+int knp_grid_destroy(knp_ctx* ctx, int grid);
+int knp_grid_timing(knp_ctx* ctx, int grid, float* locate_ms, float* weights_ms, float* sample_ms, float* copy_ms);
+
 /* ---- checkpoint of the step-to-step state (csrc/state.hip; DESIGN.md section 4.3 lists every member saved or rebuilt).
  * A snapshot is one host buffer: a 32-byte prologue (magic "KNPSTATE", version, block count, payload bytes), the block table
  * (one knp_state_block per block) and the payloads at the table's offsets.  A block is [ncomp][count][width] elements:

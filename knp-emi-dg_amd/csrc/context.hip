@@ -150,6 +150,7 @@ int knp_ctx_create(knp_ctx** out, int device, int dim, int degree, int n_ions, i
     if (const char* why = facet_tables(in, T)) return create_failed(c, -1, why);
     stamp("facet flags, neighbours");
     c->h_fflag = T.fflag;
+    c->h_ctag.assign(cell_tags, cell_tags + nc);
     c->h_mf_mask.assign((size_t)nf, 0);
     for (size_t i = 0; i < T.mf.size(); i += 6) c->h_mf_mask[(size_t)T.mf[i + 4]] = 1;
     MeshDev& m = c->m;
@@ -180,6 +181,7 @@ void knp_ctx_destroy(knp_ctx* c) {
     if (c->fork_event) hipEventDestroy(c->fork_event);
     ode_destroy_all(c);
     rec_destroy(c);
+    grid_destroy_all(c);
     state_destroy(c);
     tab_free(c);
     Fields& fl = c->fields;

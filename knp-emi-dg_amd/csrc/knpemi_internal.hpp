@@ -140,6 +140,7 @@ struct knp_ctx {
     // material (distinct D tuple, any count up to 65535; empty = too many), flag bytes (facet kinds)
     std::vector<uint16_t> h_cls, h_mat;
     std::vector<uint32_t> h_fflag;
+    std::vector<uint32_t> h_ctag;    // [nc] subdomain tag of every cell, device order: the table the grid sampler's tag filter and tag volume read (grid.hip)
     std::vector<uint8_t> h_mf_mask;  // [nf] 1 on membrane facets: what knp_rec_create checks the caller's facet sets against
     int* halo_ctr = nullptr;       // [KNP_HALO_CTR_INTS] block counters of the persistent halo-staged applies (apply_p1_halo.hpp)
     int halo_flip[2] = {0, 0};
@@ -353,6 +354,7 @@ int fields_state_prepare_load(knp_ctx* c);                         // solve.hip:
 int ode_state_blocks(knp_ctx* c, std::vector<StateBlk>& out);      // ode.hip: state / parameter tables and step sizes of every model
 int rec_state_blocks(knp_ctx* c, std::vector<StateBlk>& out);      // record.hip: ring, row counter, map accumulators
 void state_destroy(knp_ctx* c);                                    // state.hip: staging buffers of the context
+const int32_t* state_cell_rank(knp_ctx* c);                        // state.hip: device [nc] caller's cell id -> device cell, or null = identity
 template <typename T> inline void state_push_host(StateBlk& b, const T* v, int64_t n) {
     b.count = n;
     b.host.assign((const char*)v, (const char*)v + sizeof(T) * (size_t)n);
@@ -360,6 +362,7 @@ template <typename T> inline void state_push_host(StateBlk& b, const T* v, int64
 
 void ode_destroy_all(knp_ctx* c);   // ode.hip: frees the context's membrane models and runtime-compiled kernels
 void rec_destroy(knp_ctx* c);       // record.hip: frees the context's time-series recorder, if any
+void grid_destroy_all(knp_ctx* c);  // grid.hip: frees the context's voxel-grid samplers, if any
 int ode_check_failed(knp_ctx* c);   // ode.hip: reads and clears the ODE failure flag (stream idle); sets c->err
 int status_look(knp_ctx* c);        // krylov.hip: head of the status block -> c->pinned, one copy and one stream wait
 int sync_check_ode(knp_ctx* c);     // ode.hip: waits for the stream and checks the ODE failure flag (0, -2 HIP error, -4 ODE failure)

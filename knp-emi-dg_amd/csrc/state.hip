@@ -143,6 +143,11 @@ void state_destroy(knp_ctx* c) {
     g_state.erase(it);
 }
 
+const int32_t* state_cell_rank(knp_ctx* c) {
+    auto it = g_state.find(c);
+    return it == g_state.end() ? nullptr : it->second.rank;
+}
+
 extern "C" {
 
 int knp_state_cell_order(knp_ctx* c, const int64_t* order) {

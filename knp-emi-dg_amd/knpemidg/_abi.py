@@ -133,6 +133,12 @@ SIGNATURES = {
     "knp_rec_add_map_part": (C.c_int, [_ctxp, C.c_int64, C.c_int64, _i32p, _i64p, C.c_double, C.c_double]),
     "knp_rec_map_arm": (C.c_int, [_ctxp, C.c_double]),
     "knp_rec_map_read": (C.c_int, [_ctxp, C.c_int64, _f64p, _f64p, _f64p, _f64p, _i32p]),
+    "knp_grid_create": (C.c_int, [_ctxp, _f64p, _f64p, _i64p, C.c_double, C.c_int, _u32p, C.c_int, _i32p, C.c_int]),
+    "knp_grid_points": (C.c_int, [_ctxp, C.c_int, _i32p, _i32p]),
+    "knp_grid_sample": (C.c_int, [_ctxp, C.c_int]),
+    "knp_grid_fetch": (C.c_int, [_ctxp, C.c_int, C.c_void_p, C.c_size_t]),
+    "knp_grid_destroy": (C.c_int, [_ctxp, C.c_int]),
+    "knp_grid_timing": (C.c_int, [_ctxp, C.c_int, _f32p, _f32p, _f32p, _f32p]),
     "knp_state_cell_order": (C.c_int, [_ctxp, _i64p]),
     "knp_state_describe": (C.c_int64, [_ctxp, C.c_void_p, C.c_int64, _i64p]),
     "knp_state_save": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t]),
@@ -991,6 +997,52 @@ class Device:
     def rec_destroy(self):
         self._chk(self.lib.knp_rec_destroy(self.ctx), "knp_rec_destroy")
 
+    # -- fields on a regular voxel grid (csrc/grid.hip; knpemidg/grid.py holds the host side) ------------------------------
+    def grid_create(self, lo, h, shape, fields, tol=1.0e-12, tags=None, f32=False):
+        """Locate the points of the grid lo + i h, i < shape (axis order x, y[, z]) and keep their cells and barycentric coordinates
+        on the device; fields = field ids (0 phi, 1 + k solved concentration k, n_ions the eliminated ion).  Returns the handle."""
+        lo = np.ascontiguousarray(lo, dtype=np.float64)
+        h = np.ascontiguousarray(h, dtype=np.float64)
+        shape = np.ascontiguousarray(shape, dtype=np.int64)
+        if not (lo.shape == h.shape == shape.shape == (self.dim,)):
+            raise KnpError("grid_create: lo, h and shape must hold one entry per mesh dimension")
+        tg = np.ascontiguousarray([] if tags is None else list(tags), dtype=np.uint32)
+        fl = np.ascontiguousarray(fields, dtype=np.int32)
+        rc = self.lib.knp_grid_create(self.ctx, _p(lo, _f64p), _p(h, _f64p), _p(shape, _i64p), float(tol), len(tg), _p(tg, _u32p), len(fl),
+                                      _p(fl, _i32p), int(bool(f32)))
+        if rc < 0:
+            self._chk(rc, "knp_grid_create")
+        return int(rc)
+
+    def grid_points(self, grid, npts):
+        """(owner [npts] in the caller's cell numbering, subdomain tag [npts]); -1 where no cell contains the point."""
+        owner, tag = np.empty(npts, dtype=np.int32), np.empty(npts, dtype=np.int32)
+        self._chk(self.lib.knp_grid_points(self.ctx, grid, _p(owner, _i32p), _p(tag, _i32p)), "knp_grid_points")
+        return owner, tag
+
+    def grid_sample(self, grid):
+        """Enqueue one frame of the fields as they are now (asynchronous; at most two frames may wait)."""
+        self._chk(self.lib.knp_grid_sample(self.ctx, grid), "knp_grid_sample")
+
+    def grid_fetch(self, grid, n_fields, npts, dtype=np.float64, out=None):
+        """The oldest waiting frame, [n_fields, npts]; waits for that frame's copy only.  out: a C-contiguous array of that shape
+        and type to fill instead of a new one (a time loop that writes every frame to a file reuses one)."""
+        if out is None:
+            out = np.empty((n_fields, npts), dtype=dtype)
+        elif out.shape != (n_fields, npts) or out.dtype != np.dtype(dtype) or not out.flags.c_contiguous:
+            raise KnpError("grid_fetch: out must be a C-contiguous [n_fields, npts] array of the grid's type")
+        self._chk(self.lib.knp_grid_fetch(self.ctx, grid, out.ctypes.data_as(C.c_void_p), out.nbytes), "knp_grid_fetch")
+        return out
+
+    def grid_destroy(self, grid):
+        self._chk(self.lib.knp_grid_destroy(self.ctx, grid), "knp_grid_destroy")
+
+    def grid_timing(self, grid):
+        """(locate ms, weights ms, sample kernel ms, frame copy ms): the two passes of grid_create and the last fetched frame."""
+        v = [C.c_float(0) for _ in range(4)]
+        self._chk(self.lib.knp_grid_timing(self.ctx, grid, *[C.byref(x) for x in v]), "knp_grid_timing")
+        return tuple(x.value for x in v)
+
     # -- checkpoint of the step-to-step state (csrc/state.hip; knpemidg/checkpoint.py reads and writes the files) ----------
     def state_describe(self):
         """(block table as a structured array of checkpoint.BLOCK_DTYPE, size of a snapshot in bytes)."""
@@ -1038,7 +1090,7 @@ for _name in ("close", "set_params", "set_mms", "upload", "download", "copy_fiel
               "knp_apply", "emi_rhs", "knp_rhs", "emi_solve", "knp_solve", "step_updates", "picard_updates", "max_abs_diff",
               "nernst", "sync", "timer_begin", "timer_end", "bench_apply", "ode_table", "ode_step", "ode_set_stimulus",
               "amg_upload", "amg_interface", "halo_exchange", "knp_load_measure", "apply_timing_read", "comm_init", "set_interior", "rec_sample",
-              "rec_read", "rec_add_states", "rec_map_arm", "rec_map_read", "state_save", "state_load"):
+              "rec_read", "rec_add_states", "rec_map_arm", "rec_map_read", "state_save", "state_load", "grid_sample"):
     setattr(Device, _name, _flushing(getattr(Device, _name)))
 
 

@@ -97,6 +97,7 @@ class Solver:
         self.use_device_ode = os.environ.get("KNP_HOST_ODE", "0") != "1"
         self.max_it_knp = 5000
         self.recorder = None             # time-series recorder (Solver.record), sampled after step III of every time step
+        self.grids = None                # voxel-grid samplers (Solver.record_grid); None = off: the time loops test this once per step
 
     # ------------------------------------------------------------------ setup_domain (solver.py:85-121)
     def setup_domain(self, mesh, subdomains, surfaces):
@@ -276,6 +277,8 @@ class Solver:
         _abi._stamp("solver: initial fields and parameters on the device")
         if self.recorder is not None:
             self.recorder.attach(dev, self.membrane_tags)
+        for g in self.grids or ():
+            g.attach(dev)
 
     # ------------------------------------------------------------------ time series (no reference counterpart: knpemidg/recorder.py)
     def record(self, points=None, membrane_sets=None, regions=True, capacity=256, point_tags=None, membrane_states=None,
@@ -324,6 +327,56 @@ class Solver:
             rec.attach(self.dev, models=[m['ode'] for m in self.mem_models] if self.mem_models else None)
         self.recorder = rec
         return rec
+
+    # ------------------------------------------------------------------ fields on a voxel grid (no reference counterpart: knpemidg/grid.py)
+    def record_grid(self, lo, hi, shape, fields=("phi",), every=1, tags=None, dtype=np.float64, name="grid", tol=1.0e-12):
+        """Sample fields on the regular grid lo + i (hi - lo) / (shape - 1), i < shape (axis order x, y[, z]; an axis with
+        shape 1 sits at lo: a slice of a 3D mesh) on the device (csrc/grid.hip) -- the images and coarse volumes the reference's figure
+        scripts rebuild from results.h5 with FEniCS (examples/*/make_figures*.py).  Callable once setup_domain has run; the points are
+        located as soon as the device context exists.  Returns the `knpemidg.grid.GridSampler`; up to 8 grids per solver.
+          fields   out of "phi" and the ion names (the eliminated ion included)
+          every    the time loops write frame 0 for the state they start from, then one frame every `every` steps, to
+                   `<filename><name>.h5` (+ `<name>.xdmf` for ParaView), next to timeseries.h5; a resumed run writes
+                   `<name>_from<k>.h5` with /step_offset, as the field output does
+          tags     restrict the candidate cells to these subdomains: the side of a point on a membrane, ECS- or ICS-only images
+          dtype    np.float64 or np.float32 frames
+        A point that no cell contains is NaN in every field (owner -1): a grid may stick out of the mesh.  `sampler.sample()` returns
+        {field: array [nz, ny, nx]} ([ny, nx] in 2D) of the fields as they are now; `sampler.cells` / `sampler.tags` are the owner and
+        subdomain volumes.  Without a call nothing is allocated or launched.  Partitioned solvers are not supported."""
+        from knpemidg.grid import GridSpec, GridSampler, resolve_fields
+        if getattr(self, "local_mesh", None) is not None or getattr(self, "nc_owned", None) is not None or \
+                (self.dev is not None and self.dev.nranks > 1):
+            raise _abi.KnpError("record_grid: not supported with several ranks (sample the grid in a one-GPU run)")
+        if getattr(self, "mesh", None) is None:
+            raise _abi.KnpError("Solver.record_grid: call setup_domain first")
+        try:
+            spec = GridSpec(self.mesh.gdim, lo, hi, shape, tol=tol, tags=tags)
+            ids = resolve_fields(fields, [ion['name'] for ion in self.ion_list])
+            names = [fields] if isinstance(fields, str) else list(fields)
+            g = GridSampler(spec, names, ids, every=every, dtype=dtype, name=name)
+        except ValueError as e:
+            raise _abi.KnpError(str(e))
+        if any(o.name == g.name for o in self.grids or ()):
+            raise _abi.KnpError("record_grid: a grid named %r exists already" % g.name)
+        if len(self.grids or ()) >= 8:
+            raise _abi.KnpError("record_grid: at most 8 grids per solver")
+        if self.dev is not None:
+            g.attach(self.dev)
+        self.grids = (self.grids or []) + [g]
+        return g
+
+    def _grids_begin(self, k0, t):
+        if self.filename is not None:
+            for g in self.grids:
+                g.begin(self.filename, k0, float(t))
+
+    def _grids_step(self, steps_done, t):
+        for g in self.grids:
+            g.after_step(steps_done, float(t))
+
+    def _grids_finish(self):
+        for g in self.grids:
+            g.finish()
 
     def _save_timeseries(self):
         if self.recorder is not None and self.filename is not None:
@@ -995,14 +1048,20 @@ class Solver:
         self._check_output_args(filename)
         if self.recorder is not None and k0 == 0:
             self.recorder.arm(float(t))
+        if self.grids is not None:
+            self._grids_begin(k0, t)
         for k in range(k0, int(round(Tstop / float(self.dt)))):
             self.solve_for_time_step(k, t)
             if (k % self.sf) == 0 and self.save_fields:
                 self.save_h5()
+            if self.grids is not None:
+                self._grids_step(k + 1, t)
             if ckpt is not None and (k + 1) % ckpt[0] == 0:
                 self.save_checkpoint(ckpt[1])
         if self.save_fields:
             self.close_h5()
+        if self.grids is not None:
+            self._grids_finish()
         self._save_timeseries()
         if self.save_solver_stats:
             self.close_solver_stats()
@@ -1028,6 +1087,8 @@ class Solver:
         self.setup_solver_knp()
         k0 = self.load_checkpoint(resume, t=t) if resume is not None else 0
         self._check_output_args(filename)
+        if self.grids is not None:
+            self._grids_begin(k0, t)
         for k in range(k0, int(round(Tstop / float(self.dt)))):
             self.step_membrane_models(k)
             if k == 0 and self.recorder is not None:
@@ -1037,10 +1098,14 @@ class Solver:
             self.solve_for_time_step(k, t)
             if (k % self.sf) == 0 and self.save_fields:
                 self.save_h5()
+            if self.grids is not None:
+                self._grids_step(k + 1, t)
             if ckpt is not None and (k + 1) % ckpt[0] == 0:
                 self.save_checkpoint(ckpt[1])
         if self.save_fields:
             self.close_h5()
+        if self.grids is not None:
+            self._grids_finish()
         self._save_timeseries()
         if self.save_solver_stats:
             self.close_solver_stats()
