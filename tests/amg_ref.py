@@ -6,6 +6,8 @@
   * `vcycle`: amg_vcycle_eager, level by level, for [ncol, n] right-hand sides (the columns are independent).
   * `EmiPrecond` / `KnpPrecond`: the two-level preconditioners of pcg_impl / bicgstab_impl around it; `bj_lambda_max`.
   * `bicgstab`: k iterations in the form of bicgstab_impl (the PCG twin is krylov_ref.pcg with `precond` / `iters`).
+  * `gmres` / `gmres_free`: restarted GMRES in the form of gmres_impl / gm_scalar_op -- k iterations, or to convergence by the device's
+    rules with the distance of every decision from its threshold; GM_CASES / GM_FREE_CASES: what the device is compared on.
   * `launches`: which (kernel, G, NC) instantiations a hierarchy reaches (amg_vcycle.hip: by_density).
   * `synthetic`: seeded hand-built hierarchies (any density, any level size) for tests/test_amg_ref_host.py and a comparison on the device.
 A `mut = (name, level)` argument applies one deliberate error (MUTATIONS; drop_tail: (name, (level, matrix))) -- the CPU tests show
@@ -235,11 +237,12 @@ class KnpPrecond(_TwoLevel):
         self.shared = not isinstance(Hs[0], list)
         self.Hs, self.lmax, self.mut = Hs, lmax, mut
 
-    def __call__(self, R):
+    def __call__(self, R, block_scale=None):
+        """block_scale: (a mutation of the GMRES replica) the first pass over the cell blocks sees r_s times block_scale[s]"""
         cr, ctt, theta = _cheb2_coefficients(self.lmax, self.wd)
         Z, C = [], []
-        for A, Bi, r in zip(self.A, self.binv, R):
-            t = A @ _blocks(Bi, r)
+        for s, (A, Bi, r) in enumerate(zip(self.A, self.binv, R)):
+            t = A @ _blocks(Bi, r if block_scale is None else block_scale[s] * r)
             Z.append(_blocks(Bi, cr * r - ctt * t))
             C.append(self.Pdt @ (r - (1 / theta) * t))
         E = vcycle(self.Hs, np.stack(C), self.mut) if self.shared else [vcycle(H, c, self.mut) for H, c in zip(self.Hs, C)]
@@ -273,6 +276,187 @@ def bicgstab(As, bs, precond, iters, dtype=np.float64):
         beta = [(rho_new[s] / rho[s]) * (alpha[s] / omega[s]) for s in range(ns)]
         rho = rho_new
     return np.stack(x)
+
+
+# ---- restarted GMRES (krylov.hip: gmres_impl, krylov_scalar.hpp: gm_scalar_op) -----------------------------------------------------------
+GM_BATCH = 8                                                            # inner products per k_gm_dots pass
+GM_MUTATIONS = ("dots_past_8", "partial_batch", "skip_rotation", "no_normalise", "update_from_V", "short_backsub", "swap_y",
+                "stale_restart")
+_RUNNING, _CONVERGED, _CYCLE_DONE = 0, 1, 4                             # KrylovStatus
+
+
+class _GmSystem:
+    """one species: its iterate, basis, Hessenberg columns, rotations and scalars"""
+
+    def __init__(self, wd, x0):
+        self.wd, self.x = wd, x0
+        self.flag, self.iter, self.cycles, self.margin = _RUNNING, 0, [], math.inf
+        self.res = self.tol = self.t2 = self.beta = None
+
+    def new_cycle(self, r, rr):
+        wd = self.wd
+        self.beta = np.sqrt(rr)
+        self.V, self.Z, self.H = [r * (1 / self.beta)], [], []          # (k_gm_scale_binv: times the reciprocal, KS_ALPHA)
+        self.cs, self.sn, self.g = [], [], [self.beta]
+        self.k = 0
+        need = self.tol / self.res if self.res > 0 else wd(1)
+        self.t2 = self.beta * min(wd(0.5) * need, wd(0.1))
+
+    def decide(self, value, threshold):
+        """value <= threshold, and how far from flipping (relative to the threshold)"""
+        if threshold > 0:
+            self.margin = min(self.margin, float(abs(value - threshold) / threshold))
+        return value <= threshold
+
+    def y(self, mut=None):
+        """OP_GM_SOLVE: back substitution over the cycle's k columns"""
+        k = self.k - 1 if mut == "short_backsub" else self.k
+        y = [self.wd(0)] * self.k
+        for i in range(k - 1, -1, -1):
+            t = self.g[i]
+            for l in range(i + 1, k):
+                t = t - self.H[l][i] * y[l]
+            y[i] = t / self.H[i][i] if self.H[i][i] != 0 else self.wd(0)
+        return y
+
+
+def _gm_update(S, ys, mut):
+    """k_gm_lincomb: x + sum_i y_i Z_i of every species that is running or has its cycle done"""
+    out = []
+    for s, (st, y) in enumerate(zip(S, ys)):
+        x = st.x
+        if st.flag in (_RUNNING, _CYCLE_DONE):
+            for yi, zi, vi in zip(y, st.Z, st.V):
+                x = x + yi * (vi if mut == "update_from_V" else zi)
+        out.append(x)
+    return out
+
+
+def gmres_run(As, bs, precond, maxit, restart, dtype, mut=None, x0=None, tols=None, min_it=0, norm=None, reverse=False, snapshots=()):
+    """The lockstep loop of gmres_impl with a look after every column (check_every = 1; what the host sees does not change the
+    result: tests/test_gpu_krylov.py).  tols: per species the tolerance of the test on the true residual in `norm` (None: one that
+    cannot be reached -- every cycle then has `restart` columns).  reverse: inner products and norms summed from the other end.
+    Returns (the species' _GmSystem, {k: iterates had the solve ended with maxit = k} for k in snapshots)."""
+    wd = np.float64 if dtype == "fsum" else dtype
+    A = [_FsumCsr(M) if dtype == "fsum" else sp.csr_matrix(M).astype(wd) for M in As]
+    ns, m = len(A), int(restart)
+    b = [np.asarray(v).astype(wd) for v in bs]
+    assert 2 <= m <= 30 and mut in (None,) + GM_MUTATIONS
+
+    def dot(u, v):
+        return np.dot(u[::-1].copy(), v[::-1].copy()) if reverse else np.dot(u, v)
+
+    free = tols is not None
+    S = [_GmSystem(wd, np.zeros_like(b[s]) if x0 is None else np.asarray(x0[s]).astype(wd)) for s in range(ns)]
+
+    def residual(first, stale=None):                                    # residual(): k_bi_init behind the operator, OP_GM_INIT / OP_GM_RESTART
+        for s, st in enumerate(S):
+            if st.flag == _CONVERGED:
+                continue
+            r = b[s] - A[s] @ (st.x if stale is None else stale[s])
+            rr = dot(r, r)
+            if free:
+                st.res = wd(norm(r))
+                if first:
+                    st.tol = wd(tols[s])
+            else:
+                st.res, st.tol = np.sqrt(rr), wd(0)
+            if rr == 0 or (free and st.iter >= min_it and st.decide(st.res, st.tol)):
+                st.flag = _CONVERGED
+                continue
+            st.flag = _RUNNING
+            st.new_cycle(r, rr)
+
+    residual(True)
+    snap, it = {}, 0
+    if 0 in snapshots:
+        snap[0] = np.stack([st.x for st in S])
+    while any(st.flag != _CONVERGED for st in S) and it < maxit:
+        j = 0
+        while j < m and any(st.flag == _RUNNING for st in S) and it < maxit:
+            run = [s for s in range(ns) if S[s].flag == _RUNNING]
+            # an idle species' column of the shared preconditioner call carries nothing the others read (the columns are independent)
+            Vj = [S[s].V[j] if s in run else np.zeros_like(b[s]) for s in range(ns)]
+            if mut == "no_normalise":                                   # k_gm_scale_binv: y = Binv v before v *= 1 / h_{j,j-1} (1 / beta)
+                Zj = precond(Vj, block_scale=[(S[s].beta if j == 0 else S[s].hn) if s in run else wd(1) for s in range(ns)])
+            else:
+                Zj = precond(Vj)
+            for s in run:
+                st = S[s]
+                st.Z.append(Zj[s])
+                w = A[s] @ Zj[s]
+                h = [dot(w, st.V[i]) for i in range(j + 1)]             # k_gm_dots: all from the unmodified w
+                if mut == "dots_past_8":
+                    h[GM_BATCH:] = [wd(0)] * len(h[GM_BATCH:])
+                if mut == "partial_batch" and (j + 1) % GM_BATCH:
+                    lo = (j + 1) // GM_BATCH * GM_BATCH
+                    h[lo:] = [wd(0)] * (j + 1 - lo)
+                for i in range(j + 1):                                  # k_gm_update
+                    w = w - h[i] * st.V[i]
+                hn = np.sqrt(dot(w, w))
+                h.append(hn)                                            # OP_GM_NORM
+                for i in range(j):
+                    if mut == "skip_rotation" and i == 0:
+                        continue
+                    t = st.cs[i] * h[i] + st.sn[i] * h[i + 1]
+                    h[i + 1] = -st.sn[i] * h[i] + st.cs[i] * h[i + 1]
+                    h[i] = t
+                den = np.sqrt(h[j] * h[j] + hn * hn)
+                st.cs.append(h[j] / den if den > 0 else wd(1))
+                st.sn.append(hn / den if den > 0 else wd(0))
+                h[j] = den
+                st.g.append(-st.sn[j] * st.g[j])
+                st.g[j] = st.cs[j] * st.g[j]
+                st.H.append(h)
+                st.hn = hn
+                st.V.append(w * ((1 / hn) if hn > 0 else wd(0)))        # (KS_OMEGA)
+                st.k = j + 1
+                st.iter += 1
+                est = abs(st.g[j + 1])
+                early = st.iter >= min_it and (hn == 0 or (free and j + 1 < m and st.decide(est, st.t2)))
+                if early or j + 1 >= m:
+                    st.flag = _CYCLE_DONE
+            j += 1
+            it += 1
+            if it in snapshots and it < maxit:
+                ys = [st.y(mut) if st.flag in (_RUNNING, _CYCLE_DONE) else None for st in S]
+                snap[it] = np.stack(_gm_update(S, ys, None if mut == "swap_y" else mut))
+        ys = [st.y(mut) if st.flag in (_RUNNING, _CYCLE_DONE) else None for st in S]
+        if mut == "swap_y" and ys[0] is not None and ys[1] is not None:
+            assert len(ys[0]) == len(ys[1])
+            ys[0], ys[1] = ys[1], ys[0]
+        old = [st.x for st in S]
+        for st, x in zip(S, _gm_update(S, ys, mut)):
+            if st.flag in (_RUNNING, _CYCLE_DONE):
+                st.cycles.append(st.k)
+                st.Z_done = st.Z                                        # (kept for the CPU tests: the next cycle starts a new list)
+            st.x = x
+        residual(False, old if mut == "stale_restart" else None)
+    if maxit in snapshots:
+        snap[maxit] = np.stack([st.x for st in S])
+    return S, snap
+
+
+def gmres(As, bs, precond, iters, restart=30, dtype=np.float64, mut=None, x0=None, reverse=False):
+    """x after `iters` columns of gmres_impl from x0 (default 0) at a tolerance that cannot be reached: right preconditioning with the
+    Z_j = M^-1 V_j kept, one classical Gram-Schmidt pass, the Givens rotations of gm_scalar_op, back substitution over the columns of
+    the (possibly unfinished) cycle, x += sum y_i Z_i, restart from the true residual after `restart` columns.  The species' scalars
+    are separate, the preconditioner sees all of them.  iters: a count -> [nsys, n]; a sequence of counts -> {count: [nsys, n]} from
+    one run (the iterate after k columns is what a solve with maxit = k returns: the update of the unfinished cycle is applied).
+    mut: one of GM_MUTATIONS; the snapshots of a run apply all of them but swap_y and stale_restart (the last count has those too)."""
+    ks = (iters,) if np.isscalar(iters) else tuple(iters)
+    _, snap = gmres_run(As, bs, precond, max(ks), restart, dtype, mut=mut, x0=x0, reverse=reverse, snapshots=ks)
+    return snap[iters] if np.isscalar(iters) else snap
+
+
+def gmres_free(As, bs, precond, tols, norm, restart=30, dtype=np.float64, min_it=0, maxit=1000, reverse=False):
+    """the solve as the device runs it to convergence: T2 = beta min(0.5 tol / res, 0.1); a species' cycle ends at the first column
+    whose estimate is <= T2 (iteration count >= min_it) or at column `restart`; it then idles until every species' cycle is done, all
+    update and restart together, and the true residual in `norm` against tols[s] decides.  Per species a dict: x, niter, cycles (the
+    column count of every cycle), margin (the smallest relative distance of a decision from its threshold), res (the last norm)."""
+    S, _ = gmres_run(As, bs, precond, maxit, restart, dtype, tols=tols, min_it=min_it, norm=norm, reverse=reverse)
+    assert all(st.flag == _CONVERGED for st in S), "the replica did not converge"
+    return [dict(x=st.x, niter=st.iter, cycles=tuple(st.cycles), margin=st.margin, res=float(st.res)) for st in S]
 
 
 # ---- which kernel instantiations a hierarchy reaches -----------------------------------------------------------------------------------
@@ -570,12 +754,8 @@ def knp_lmax(host, blocks, bs):
     return bj_lambda_max(host.knp()[0], host.blocks(blocks), [np.asarray(b, dtype=np.float64).ravel() for b in bs])
 
 
-def knp_xk(host, levels, k, dtype=np.float64, bs=None, lmax_bs=None, mut=None, blocks="cell", lmax=None):
-    """x_k [nsys, ndof] of the device's KNP BiCGStab from x_0 = 0.  levels: one hierarchy shared by the species (its columns), or a
-    list with one hierarchy per species.  lmax_bs: the right-hand sides the spectral bound was estimated from (default: bs).
-    blocks: the cell blocks of the preconditioner and of the spectral bound -- "cell" (per-cell inverses with the drift), "table" (the
-    drift-free class table of solve.hip) or an explicit list (lagged inverses of another potential: `Host.variant(...).blocks`).
-    lmax: the spectral bound itself, where the device keeps one estimated on other matrices (`knp_lmax`)."""
+def _knp_system(host, levels, dtype, bs, lmax_bs, mut, blocks, lmax):
+    """(A_s, b_s, the two-level preconditioner) of a KNP solve on `host`'s matrices: the arguments of knp_xk"""
     As, _, b0 = host.knp()
     binvs = host.blocks(blocks)
     bs = b0 if bs is None else [np.asarray(b, dtype=np.float64).ravel() for b in bs]
@@ -583,8 +763,97 @@ def knp_xk(host, levels, k, dtype=np.float64, bs=None, lmax_bs=None, mut=None, b
     if lmax is None:
         lmax = bj_lambda_max(As, binvs, bs if lmax_bs is None else lmax_bs)
     shared = hasattr(levels[0], "A")
-    Hs = store(levels, dtype, mut, ncol=ns) if shared else [store(lv, dtype, mut) for lv in levels]
-    return bicgstab(As, bs, KnpPrecond(As, binvs, host.dg2cg, Hs, lmax, dtype, mut), k, dtype)
+    amg_mut = mut if isinstance(mut, tuple) else None       # (a name alone: one of GM_MUTATIONS)
+    Hs = store(levels, dtype, amg_mut, ncol=ns) if shared else [store(lv, dtype, amg_mut) for lv in levels]
+    return As, bs, KnpPrecond(As, binvs, host.dg2cg, Hs, lmax, dtype, amg_mut)
+
+
+def knp_xk(host, levels, k, dtype=np.float64, bs=None, lmax_bs=None, mut=None, blocks="cell", lmax=None, method="bicgstab",
+           reverse=False):
+    """x_k [nsys, ndof] of the device's KNP solve from x_0 = 0.  levels: one hierarchy shared by the species (its columns), or a
+    list with one hierarchy per species.  lmax_bs: the right-hand sides the spectral bound was estimated from (default: bs).
+    blocks: the cell blocks of the preconditioner and of the spectral bound -- "cell" (per-cell inverses with the drift), "table" (the
+    drift-free class table of solve.hip) or an explicit list (lagged inverses of another potential: `Host.variant(...).blocks`).
+    lmax: the spectral bound itself, where the device keeps one estimated on other matrices (`knp_lmax`).
+    method: "bicgstab", or ("gmres", m) for GMRES restarted after m columns -- k may then be a sequence of counts (`gmres`), mut one
+    of GM_MUTATIONS, and reverse sums the inner products from the other end."""
+    As, bs, M = _knp_system(host, levels, dtype, bs, lmax_bs, mut, blocks, lmax)
+    if method == "bicgstab":
+        return bicgstab(As, bs, M, k, dtype)
+    assert method[0] == "gmres"
+    return gmres(As, bs, M, k, method[1], dtype, mut=mut if isinstance(mut, str) else None, reverse=reverse)
+
+
+def knp_gmres_free(host, levels, rtol, m, dtype=np.float64, bs=None, blocks="table", min_it=0, reverse=False):
+    """the converged GMRES(m) solve of knp_knp_solve from x_0 = 0 at `rtol`: the stopping test is on the order-8 norm of the residual's
+    density against KNP_D8_FACTOR rtol times that of the load (solve.hip).  Returns `gmres_free`'s list."""
+    import krylov_ref as kr
+    As, bs, M = _knp_system(host, levels, dtype, bs, None, None, blocks, None)
+    tols = [kr.KNP_D8_FACTOR * rtol * host.ref.norm_d8(b) for b in bs]
+    return gmres_free(As, bs, M, tols, host.ref.norm_d8, m, dtype, min_it=min_it, reverse=reverse)
+
+
+# the GMRES cases the device runs (tests/test_gpu_amg.py): (mesh, solved species, hierarchy or one per species, block set, restart
+# length m, the iteration counts k) -- "cell" at the synthetic potential, "table" at TABLE_PHI_SCALE times it.  With m = 30 the counts
+# 9 / 10, 17 and 25 end in the second, third and fourth pass of k_gm_dots with 1 / 2, 1 and 1 inner products in it (cnt < 8), 30 is
+# the full cycle (four passes, six in the last one) and 33 the first restart; m = 3 and m = 8 restart once and twice, the second
+# time in an unfinished cycle.  tests/test_amg_ref_host.py asserts that every case has its bound and what the counts reach.
+GM_KS = (1, 2, 9, 10, 17, 25, 30, 33)
+GM_CASES = (("box_P1", 2, "coarse_257", "cell", 30, GM_KS),
+            ("box_P1", 2, "coarse_257", "table", 30, GM_KS), ("box_P1", 2, "mid", "table", 30, GM_KS),
+            ("box_P1", 2, "coarse_257", "table", 3, (5, 7)), ("box_P1", 2, "mid", "table", 3, (5, 7)),
+            ("box_P1", 2, "coarse_257", "table", 8, (20,)), ("box_P1", 2, "mid", "table", 8, (20,)),
+            ("box_P1", 3, "coarse_257", "cell", 30, (2, 10, 33)), ("box_P1", 3, "mid", "table", 30, (2, 10, 33)),
+            ("box_P1", 2, ("coarse_257", "mid"), "cell", 30, (2, 10, 33)), ("box_P1", 2, ("coarse_257", "mid"), "table", 30, (2, 10, 33)),
+            ("box_P2", 2, "coarse_769", "cell", 30, (3, 10)), ("box_P2", 2, "coarse_257", "table", 30, (3, 10)),
+            ("2D_P1", 2, "mid", "cell", 30, (3, 10)), ("2D_P1", 2, "bands", "cell", 30, (3, 10)))
+# converged solves on box_P1, two species, the class table: (hierarchy, rtol, m).  rtol 0.01 / 0.0025 / 0.001 put the test on the
+# order-8 density norm at 0.2 / 0.05 / 0.02 of the load's
+GM_FREE_CASES = (("coarse_257", 0.01, 30), ("mid", 0.01, 30), ("coarse_257", 0.0025, 8), ("mid", 0.0025, 8), ("coarse_257", 0.001, 30),
+                 ("mid", 0.001, 30))
+
+
+def gm_host_args(case):
+    """the arguments of `Host` for one of GM_CASES"""
+    mesh, ns, _, blocks = case[:4]
+    return mesh, IONS[ns], (1.0 if blocks == "cell" else TABLE_PHI_SCALE), False
+
+
+def gm_levels(sets, names):
+    return sets[names] if isinstance(names, str) else [sets[n] for n in names]
+
+
+def gm_columns(k, m):
+    """the columns (within their cycles) that k iterations of GMRES(m) run"""
+    return [it % m for it in range(k)]
+
+
+def gm_batches(j):
+    """(passes of k_gm_dots for column j, whether the last one is partial: cnt < 8)"""
+    return -(-(j + 1) // GM_BATCH), (j + 1) % GM_BATCH != 0
+
+
+def gm_reference(host, levels, blocks, m, ks, bs=None):
+    """{k: (x64 [nsys, n], bounds [nsys], scales [nsys])}: the float64 replica of GMRES(m) after k iterations and the comparison bound
+    per species -- `bound` over the float64 run, the float64 run with reversed sums and the extended-precision run"""
+    ks = tuple(ks)
+    run = lambda dtype, rev: knp_xk(host, levels, ks, dtype, bs=bs, blocks=blocks, method=("gmres", m), reverse=rev)
+    x64, xrev, xhp = run(np.float64, False), run(np.float64, True), run(hp_dtype(), False)
+    return {k: (x64[k], [bound(x64[k][s], xhp[k][s], xrev[k][s]) for s in range(len(x64[k]))],
+                [float(np.abs(xhp[k][s]).max()) for s in range(len(x64[k]))]) for k in ks}
+
+
+def gm_free_reference(host, levels, rtol, m, bs=None):
+    """the converged solve three times (float64, float64 with reversed sums, extended precision): (the float64 run's list of
+    `gmres_free`, bounds [nsys], scales [nsys], smallest decision margin of the three runs); the three runs must take the same
+    decisions (iteration and cycle counts), else no comparison of iterates means anything"""
+    r64 = knp_gmres_free(host, levels, rtol, m, bs=bs)
+    rrev = knp_gmres_free(host, levels, rtol, m, bs=bs, reverse=True)
+    rhp = knp_gmres_free(host, levels, rtol, m, hp_dtype(), bs=bs)
+    for a, b, c in zip(r64, rrev, rhp):
+        assert a["niter"] == b["niter"] == c["niter"] and a["cycles"] == b["cycles"] == c["cycles"], (a["cycles"], b["cycles"], c["cycles"])
+    margin = min(r["margin"] for run in (r64, rrev, rhp) for r in run)
+    return (r64, [bound(a["x"], c["x"], b["x"]) for a, b, c in zip(r64, rrev, rhp)], [float(np.abs(c["x"]).max()) for c in rhp], margin)
 
 
 def at_peclet(host, pe):
@@ -644,11 +913,13 @@ def hp_dtype():
     return HP if HP is not None else "fsum"
 
 
-def bound(x64, xhp):
+def bound(x64, xhp, *more64):
     """the comparison bound of DESIGN.md ("V-cycle parity"), measured on the reference itself: 32 times the rounding error of the
-    float64 replica against the extended-precision one, at least 1e-13 of the result; above 1e-9 the case is ill-conditioned"""
-    x64, xhp = np.asarray(x64), np.asarray(xhp)
+    float64 replica against the extended-precision one, at least 1e-13 of the result; above 1e-9 the case is ill-conditioned.
+    more64: further float64 runs of the same replica (GMRES: the inner products summed from the other end); the largest error counts."""
+    xhp = np.asarray(xhp)
     scale = float(np.abs(xhp).max())
-    bd = max(32.0 * float(np.abs(x64 - xhp).max()), 1e-13 * scale)
+    err = max(float(np.abs(np.asarray(x) - xhp).max()) for x in (x64,) + more64)
+    bd = max(32.0 * err, 1e-13 * scale)
     assert bd <= 1e-9 * scale, "ill-conditioned case: bound %.3g of the result" % (bd / scale)
     return bd

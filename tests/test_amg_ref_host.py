@@ -4,6 +4,9 @@ P Ac^-1 P^T where that is what it must be, the hand-built hierarchies reach ever
 deliberate errors in the replica moves the k-iteration result by at least 100 times the comparison bound (amg_ref.bound).
 For the KNP solve on the drift-free class table of solve.hip (build_bj_table): the replica's table blocks are one block per table key,
 to the bit; the two block sets give iterates at least 1e6 bounds apart; and the bound exists for every case the device runs.
+For restarted GMRES (amg_ref.gmres): the replica minimises the residual over the stored Z_j, restarts exactly, every case the device
+runs has its bound and reaches the passes of the inner products it is meant to, eight deliberate errors are far above the bound, and
+the converged cases take every decision by a margin.
 No GPU is needed, but knpemidg.amg builds its hierarchies with the host routines of the built library (as tests/test_host.py does)."""
 import os
 
@@ -352,3 +355,160 @@ def test_switch_cases_of_the_device_tell_the_rule_from_a_broken_one():
             _apart(st["host"], levels, 1, bs, (st["blocks"], st["lmax"]), wrong, "step %s / %s" % (st["tag"], what))
     for what, h in (("dt", lo.variant(dt=lo.pb.dt / 2)), ("materials", lo.variant(D=ar.four_materials(lo.pb)))):
         _apart(h, levels, 1, bs, ("table", None), (lo.blocks("table"), None), "new %s / table of the old ones" % what)
+
+
+# ---- the GMRES replica (amg_ref.gmres: krylov.hip gmres_impl, krylov_scalar.hpp gm_scalar_op) -----------------------------------------------
+_GM_HOSTS, _GM_REF = {}, {}
+
+
+def _gm_host(case):
+    key = ar.gm_host_args(case)
+    if key not in _GM_HOSTS:
+        h = ar.Host(*key)
+        _GM_HOSTS[key] = (h, ar.synthetic_set(h.ncg, h.scale(knp=True)))
+    return _GM_HOSTS[key]
+
+
+def _gm_ref(case):
+    """amg_ref.gm_reference of a case of GM_CASES, computed once"""
+    if case not in _GM_REF:
+        h, S = _gm_host(case)
+        _GM_REF[case] = ar.gm_reference(h, ar.gm_levels(S, case[2]), case[3], case[4], case[5])
+    return _GM_REF[case]
+
+
+_GM_ID = lambda c: "-".join(str(v) for v in c[:5])
+
+
+@pytest.mark.parametrize("blocks", ["cell", "table"])
+@pytest.mark.parametrize("mesh,name", [("box_P1", "coarse_257"), ("2D_P1", "mid")])
+def test_gmres_replica_minimises_the_residual(mesh, name, blocks):
+    """within one cycle x_k = x_0 + Z y with y the minimiser of ||r_0 - A Z y||_2 over the k stored Z_j = M^-1 V_j: the replica's y
+    (Hessenberg matrix, rotations, back substitution) against the dense least-squares solution of LAPACK.  The extended-precision
+    replica carries no error of its own at this level; the float64 least-squares solve has a relative error of about
+    eps cond(A Z) (1 + cond(A Z) ||r_k|| / ||r_0||) in y (Golub & Van Loan, Matrix Computations, 5.3.7), and Z y is compared in
+    units of ||Z||_2 ||y||_2: the tolerance is 10 eps cond(A Z)^2 of that."""
+    case = (mesh, 2, name, blocks, 30, (4, 12))
+    h, S = _gm_host(case)
+    As, bs, M = ar._knp_system(h, S[name], ar.hp_dtype(), None, None, None, blocks, None)
+    for k in case[5]:
+        sys_, snap = ar.gmres_run(As, bs, M, k, 30, ar.hp_dtype(), snapshots=(k,))
+        for s, st in enumerate(sys_):
+            Z = np.stack([np.asarray(z, dtype=np.float64) for z in st.Z_done], axis=1)
+            assert Z.shape[1] == k
+            AZ = As[s] @ Z
+            y, _, _, sv = np.linalg.lstsq(AZ, np.asarray(bs[s], dtype=np.float64), rcond=None)
+            cond = sv[0] / sv[-1]
+            tol = 10.0 * np.finfo(np.float64).eps * cond ** 2 * np.linalg.norm(Z, 2) * np.linalg.norm(y)
+            diff = np.linalg.norm(np.asarray(snap[k][s], dtype=np.float64) - Z @ y)
+            print("GMRES LSQ %s %s %s k=%d species %d: cond(A Z) %.3g, |x_k - Z y*| %.3g, tolerance %.3g" % (mesh, name, blocks, k, s, cond,
+                                                                                                          diff, tol))
+            assert tol <= 1e-6 * np.linalg.norm(snap[k][s].astype(np.float64)), "the tolerance says nothing on this case"
+            assert diff <= tol, (mesh, name, blocks, k, s, diff / tol)
+
+
+def test_gmres_replica_restarts_from_the_true_residual():
+    """k > m iterations of GMRES(m) are k - m iterations started from x_m, to the bit (the residual b - A x_m is all a cycle hands on)"""
+    case = ar.GM_CASES[1]
+    h, S = _gm_host(case)
+    As, bs, M = ar._knp_system(h, S[case[2]], np.float64, None, None, None, case[3], None)
+    for m, k in ((30, 33), (3, 7), (8, 20)):
+        whole = ar.gmres(As, bs, M, k, m)
+        xm = ar.gmres(As, bs, M, m * ((k - 1) // m), m)
+        again = ar.gmres(As, bs, M, k - m * ((k - 1) // m), m, x0=xm)
+        assert np.array_equal(whole, again), (m, k)
+        assert not np.array_equal(whole, xm)
+
+
+def test_gmres_snapshots_are_the_shorter_solves():
+    """one run to the largest count returns every listed count's iterate: the bits of a run that ends there"""
+    case = ar.GM_CASES[1]
+    h, S = _gm_host(case)
+    As, bs, M = ar._knp_system(h, S[case[2]], np.float64, None, None, None, case[3], None)
+    snap = ar.gmres(As, bs, M, (2, 10, 30, 33), 30)
+    for k in (2, 10, 30, 33):
+        assert np.array_equal(snap[k], ar.gmres(As, bs, M, k, 30)), k
+
+
+@pytest.mark.parametrize("case", ar.GM_CASES, ids=_GM_ID)
+def test_gmres_cases_of_the_device_are_well_conditioned(case):
+    """amg_ref.bound raises above the cap of 1e-9: every case, count and species the device runs has its bound (none is skipped)"""
+    ref = _gm_ref(case)
+    assert sorted(ref) == sorted(case[5])
+    for k, (x, bds, scales) in ref.items():
+        assert len(bds) == case[1]
+        for s in range(case[1]):
+            assert 1e-13 * scales[s] <= bds[s] <= 1e-9 * scales[s]
+            print("GMRES BOUND %s k=%d species %d: %.3g" % (_GM_ID(case), k, s, bds[s] / scales[s]))
+
+
+def test_gmres_cases_reach_every_pass_of_the_inner_products():
+    """what the counts of GM_CASES reach, per block set: columns whose inner products take two, three and four passes of k_gm_dots
+    with a partial last pass, the full cycle of 30 columns and a restart behind it; restarts of short cycles (m = 3, m = 8) that end
+    in an unfinished cycle; two and three species, one hierarchy per species, all three meshes"""
+    for blocks in ("cell", "table"):
+        cases = [c for c in ar.GM_CASES if c[3] == blocks]
+        full = [c for c in cases if c[:2] == ("box_P1", 2) and isinstance(c[2], str) and c[4] == 30]
+        assert full
+        for c in full:
+            last = {ar.gm_batches(ar.gm_columns(k, 30)[-1]) for k in c[5]}
+            assert {(1, True), (2, True), (3, True), (4, True)} <= last, (c, last)
+            assert 30 in c[5] and max(c[5]) > 30 and 0 < max(c[5]) % 30 < 8
+        assert {c[1] for c in cases} >= {2, 3} and any(not isinstance(c[2], str) for c in cases)
+        assert {c[0] for c in cases} >= {"box_P1", "box_P2"}
+    assert any(c[0] == "2D_P1" for c in ar.GM_CASES)
+    short = {(c[4], k) for c in ar.GM_CASES if c[4] < 30 for k in c[5]}
+    assert {m for m, _ in short} == {3, 8} and all(k > m and k % m for m, k in short)
+    assert any(k > 2 * m for m, k in short)
+
+
+@pytest.mark.parametrize("mutation", ar.GM_MUTATIONS)
+def test_gmres_mutations_of_the_replica_are_far_above_the_bound(mutation):
+    """each deliberate error of the replica -- the inner products of columns >= 8 lost; the one partial pass of k_gm_dots lost; the
+    first rotation not applied to the new column; the new basis vector not normalised; the update taken from V instead of Z; back
+    substitution over k - 1 columns; the first two species' y exchanged; the restart's residual taken from x without the cycle's
+    update -- moves x_k by >= 100 bounds for every species on a listed case of either block set: a device with that defect cannot pass"""
+    for blocks in ("cell", "table"):
+        case = next(c for c in ar.GM_CASES if c[3] == blocks and c[5] == ar.GM_KS)
+        h, S = _gm_host(case)
+        ref = _gm_ref(case)
+        worst = {}
+        for k in (17, 33):
+            wrong = ar.knp_xk(h, S[case[2]], k, blocks=blocks, method=("gmres", 30), mut=mutation)
+            x, bds, _ = ref[k]
+            worst[k] = min(np.abs(wrong[s] - x[s]).max() / bds[s] for s in range(case[1]))
+        print("GMRES MUTATION %s %s: %s bounds" % (mutation, _GM_ID(case), ", ".join("k=%d %.3g" % kv for kv in worst.items())))
+        assert max(worst.values()) >= 100.0, (mutation, blocks, worst)
+
+
+@pytest.mark.parametrize("case", ar.GM_FREE_CASES, ids=lambda c: "-".join(str(v) for v in c))
+def test_gmres_free_running_cases_decide_by_a_margin(case):
+    """the converged solves the device is compared with: every decision (estimate against T2, true residual against the tolerance) is
+    >= 1e-3 of its threshold away from flipping in float64, with reversed sums and in extended precision, and the three runs count
+    the same iterations and cycles (asserted by gm_free_reference) -- rounding on the device cannot change the path"""
+    name, rtol, m = case
+    h, S = _gm_host(("box_P1", 2, name, "table"))
+    runs, bds, scales, margin = ar.gm_free_reference(h, S[name], rtol, m)
+    print("GMRES FREE %s rtol %g m=%d: cycles %s, margin %.3g, bounds %s" % (name, rtol, m, [r["cycles"] for r in runs], margin,
+                                                                             ["%.3g" % (b / s) for b, s in zip(bds, scales)]))
+    assert margin >= 1e-3, margin
+    assert all(sum(r["cycles"]) == r["niter"] and max(r["cycles"]) <= m for r in runs)
+    _GM_REF[("free",) + case] = [r["cycles"] for r in runs]
+
+
+def test_gmres_free_running_cases_cover_the_lockstep():
+    """among the converged cases: one where the species end a shared cycle at different columns before column m (each by its own
+    estimate; the earlier one idles), one where one species converges cycles before the other, and one with both"""
+    cyc = {}
+    for case in ar.GM_FREE_CASES:
+        key = ("free",) + case
+        if key not in _GM_REF:
+            h, S = _gm_host(("box_P1", 2, case[0], "table"))
+            _GM_REF[key] = [r["cycles"] for r in ar.gm_free_reference(h, S[case[0]], case[1], case[2])[0]]
+        cyc[case] = _GM_REF[key]
+    m_of = lambda case: case[2]
+    shared_differ = [c for c, (a, b) in cyc.items() if any(x != y and max(x, y) < m_of(c) for x, y in zip(a, b))]
+    sooner = [c for c, (a, b) in cyc.items() if abs(len(a) - len(b)) >= 2]
+    assert shared_differ and sooner, cyc
+    assert any(len(a) != len(b) and min(len(a), len(b)) >= 1 and (a[-1] < m_of(c) or b[-1] < m_of(c)) and max(len(a), len(b)) >= 2
+               for c, (a, b) in cyc.items()), cyc

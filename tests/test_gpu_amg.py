@@ -17,9 +17,17 @@ materials, against the replica on the oracle's blocks assembled at phi = 0; the 
 side of the limit, with the largest cell Peclet number at the edges of k_cell_peclet's waves and workgroups, through a fall-back and
 return on a potential that changes on the device (one solve late, with the rebuilt per-cell array and the re-estimated spectral bound),
 and after set_params.  Against the replica on the OTHER block set the table cases miss by 7.4e8 ... 6.5e11 bounds (tried once on the
-MI355X; tests/test_amg_ref_host.py asserts >= 1e6 between the two replicas).  GMRES on the table path is covered by the stopping tests
-of tests/test_gpu_krylov.py alone (converged solves frozen at the EMI solution: Peclet number 0.012 on box_P1, 0.018 on axon_P1), not
-vector by vector: there is no GMRES replica.
+MI355X; tests/test_amg_ref_host.py asserts >= 1e6 between the two replicas).
+
+Restarted GMRES (knp_set_knp_krylov; gmres_impl, gm_scalar_op) is compared in the same way, with amg_ref.gmres: x_k of GMRES(m) for the
+counts of amg_ref.GM_CASES -- with m = 30, k = 9 / 10, 17 and 25 end in the second, third and fourth pass of k_gm_dots with a partial
+last pass, 30 is the full cycle, 33 the first restart; m = 3 and m = 8 restart in unfinished cycles -- on both block sets, with two and
+three species, a shared hierarchy and one per species, on the three meshes; and solves run to convergence against amg_ref.gmres_free
+(cycle ends on KS_GM_T2 at different columns, a species that idles or has converged cycles before the other, the joint restart): the
+iteration counts are the replica's, the iterates within the bound, res[:, 1] is the host's norm of the returned iterate's residual.
+A single Gram-Schmidt pass is more sensitive to the summation order than the short recurrences, so the GMRES bound takes the larger
+error of two float64 runs of the replica (inner products summed from either end) against the extended-precision one.  Each of eight
+deliberate errors of the replica (amg_ref.GM_MUTATIONS) is >= 9e7 bounds away on these cases (tests/test_amg_ref_host.py).
 
 Bound ("V-cycle parity"): max(32 ||x64 - x_hp||_inf, 1e-13 ||x_hp||_inf) with x64 / x_hp the replica in float64 / extended
 precision -- never taken from the device's numbers.  Measured on the MI355X, as multiples of ||x_k||_inf, worst case of each group:
@@ -47,6 +55,13 @@ precision -- never taken from the device's numbers.  Measured on the MI355X, as 
   KNP  switch, largest Peclet number in 6 + 1 cell positions     1.1e-12         5.8e-14                0.27
   KNP  switch, fall-back and return on the device, 8 solves      3.7e-13         2.2e-14                0.12
   KNP  switch, table after set_params (dt / 2, four materials)   3.7e-13         2.2e-14                0.11
+  GMRES(30)  3D P1 box, 2 species, per-cell blocks, 8 counts     8.8e-12         7.4e-13                0.20
+  GMRES(30)  table, 3D P1 box, 2 species, 2 hierarchies, 8 counts 1.6e-11        1.6e-12                0.11
+  GMRES(3), GMRES(8)  table, 3D P1 box, 2 species               5.4e-12         5.0e-13                0.11
+  GMRES(30)  3D P1 box, 3 species shared (cell / table)          9.3e-13         2.8e-14                0.18
+  GMRES(30)  3D P1 box, one hierarchy per species (cell / table) 2.5e-11         8.1e-13                0.11
+  GMRES(30)  3D P2 box (cell / table), 2D P1 (cell)              6.2e-11         2.8e-12                0.07
+  GMRES(30), GMRES(8)  converged solves, table, 6 cases          1.3e-11         5.4e-13                0.10
   (both DG smoothers, the random right-hand side and the unfused paths are inside their groups)
 
 Two production cases are ill-conditioned by the rule above and are not run: the single-level hierarchy of the 2D mesh (bounds 0.85e-9 ...
@@ -474,3 +489,98 @@ def test_knp_table_is_rebuilt_after_new_coefficients(hip_lib, what):
         set_params_of(c.dev, h.pb)
         c.dev.update_dnphi()
         _match(c, h, levels, 1, c.knp(1, c.b_knp), "new %s" % what, "table")
+
+
+# ---- restarted GMRES, iterate by iterate (krylov.hip: gmres_impl; krylov_scalar.hpp: gm_scalar_op) ---------------------------------
+@contextlib.contextmanager
+def _gmres_on(c, names, m):
+    """the hierarchies `names` in the KNP slots and GMRES(m) as the KNP method; afterwards BiCGStab and the context's state again
+    (contexts are shared by the tests of this module)"""
+    shared = isinstance(names, str)
+    levels = c.levels(names, True) if shared else [c.levels(n, True) for n in names]
+    dev, ns = c.dev, c.ns
+    for s in range(ns):
+        dev.amg_clear(1 + s)
+    if shared:
+        dev.amg_upload(1, c.host.dg2cg, levels, ncol=ns)
+    else:
+        for s in range(ns):
+            dev.amg_upload(1 + s, c.host.dg2cg, levels[s])
+    dev.set_knp_krylov("gmres", m)
+    try:
+        yield levels
+    finally:
+        dev.set_knp_krylov("bicgstab")
+        for s in range(ns):
+            dev.amg_clear(1 + s)
+        dev.upload(c.A.F_B_KNP, c.b_knp)
+        dev.upload(c.A.F_C, c.host.pb.c)
+
+
+def _assert_block_set(c, blocks):
+    if blocks == "cell":
+        assert c.host.peclet() > 0.5
+    else:
+        assert c.host.peclet() <= 0.4
+
+
+@pytest.mark.parametrize("case", ar.GM_CASES, ids=lambda c: "-".join(str(v) for v in c[:5]))
+def test_gmres_iterates(hip_lib, case):
+    """x_k of GMRES(m) for every count of the case (amg_ref.GM_CASES: what the counts reach is written and asserted there) against
+    amg_ref.gmres, within the bound of the three replica runs; each solve twice with the same bits; and with another right-hand side
+    for species 1 the other species keep their bits (the spectral bound held fixed, as in _check_knp)."""
+    mesh, ns, names, blocks, m, ks = case
+    c = _ctx(*ar.gm_host_args(case))
+    assert c.ns == ns
+    _assert_block_set(c, blocks)
+    b2 = c.b_knp.copy()
+    b2[1] *= 1.0 + 1e-3 * np.random.default_rng(17).uniform(-1.0, 1.0, size=b2[1].shape)
+    with _gmres_on(c, names, m) as levels:
+        got = {k: (c.knp(k, c.b_knp), c.knp(k, c.b_knp), c.knp(k, b2, keep_bound=True)) for k in ks}
+    ref = ar.gm_reference(c.host, levels, blocks, m, ks, bs=c.b_knp)
+    bad = []
+    keep = [s for s in range(ns) if s != 1]
+    for k, (x, again, other) in got.items():
+        assert np.array_equal(x, again), (case, k, "a second identical solve gave other bits")
+        assert np.array_equal(other[keep], x[keep]) and not np.array_equal(other[1], x[1]), (case, k, "species are not independent")
+        x64, bds, scales = ref[k]
+        for s in range(ns):
+            err = np.abs(x[s] - x64[s]).max()
+            _report("gmres(%d) %s%s ns=%d %s species %d" % (m, "" if blocks == "cell" else "table ", mesh, ns, names, s), k, bds[s], err,
+                    scales[s])
+            if not err <= bds[s]:
+                bad.append((k, s, err / bds[s]))
+    assert not bad, (case, bad)
+
+
+@pytest.mark.parametrize("case", ar.GM_FREE_CASES, ids=lambda c: "-".join(str(v) for v in c))
+def test_gmres_converged_solves_follow_the_replica(hip_lib, case):
+    """the solve run to convergence (min_it = 0, a look after every iteration) on the cases whose decisions tests/test_amg_ref_host.py
+    shows >= 1e-3 away from their thresholds: per species the iteration count of amg_ref.gmres_free (cycle ends on KS_GM_T2, idling
+    until every species' cycle is done, the joint restart, the test on the true residual), the iterate within the bound, and the
+    reported residual norm res[:, 1] within 1e-6 of the host's norm of b - A x for the returned x."""
+    name, rtol, m = case
+    c = _table_ctx()
+    _assert_block_set(c, "table")
+    A, dev = c.A, c.dev
+    mats = c.host.knp()[0]
+    with _gmres_on(c, name, m) as levels:
+        dev.upload(A.F_B_KNP, c.b_knp)
+        dev.upload(A.F_C, np.zeros(c.ns * c.host.pb.ndof))
+        niter, res = dev.knp_solve(rtol, maxit=400, min_it=0, check_every=1)
+        x = dev.download(A.F_C).reshape(c.ns, -1)
+    runs, bds, scales, margin = ar.gm_free_reference(c.host, levels, rtol, m, bs=c.b_knp)
+    assert margin >= 1e-3, margin
+    bad = []
+    for s in range(c.ns):
+        err = np.abs(x[s] - runs[s]["x"]).max()
+        true = c.host.ref.norm_d8(c.b_knp[s] - mats[s] @ x[s])
+        print("AMGPAR gmres(%d) free %s rtol %g species %d: niter %d (replica %d, cycles %s) bound %.2e err %.2e res %.6e host %.6e"
+              % (m, name, rtol, s, niter[s], runs[s]["niter"], runs[s]["cycles"], bds[s] / scales[s], err / scales[s], res[s, 1], true))
+        if niter[s] != runs[s]["niter"]:
+            bad.append((s, "niter", niter[s], runs[s]["niter"]))
+        elif not err <= bds[s]:
+            bad.append((s, "iterate", err / bds[s]))
+        if not abs(res[s, 1] / true - 1.0) <= 1e-6:
+            bad.append((s, "res", res[s, 1], true))
+    assert not bad, (case, bad)

@@ -41,6 +41,7 @@ def _single_rank(n_axons, steps, method, degree=1):
     vol = np.abs(np.linalg.det(x[:, 1:] - x[:, :1])) / 6.0
     out = (S.c.array().reshape(S.N_ions, nc, S.nd).copy(), S.phi.array().reshape(nc, S.nd).copy(), vol, list(S.emi_niter),
            [max(n) for n in S.knp_niter], np.asarray(S.emi_targets))
+    _single_rank.krylov = getattr(S, "_knp_krylov", "bicgstab")         # the KNP method the device was set to
     S.dev.close()
     return out
 
@@ -48,6 +49,17 @@ def _single_rank(n_axons, steps, method, degree=1):
 @pytest.mark.parametrize("world,method,n_axons,dist0", [(2, "slab", 4, 1), (3, "slab", 4, 1), (3, "rcb", 1, 1), (3, "emix", 0, 1),
                                                         (3, "thin", 4, 1), (2, "p2", 4, 1), (2, "slab", 4, 0)])
 def test_partitioned_solver_with_several_ranks_on_one_gpu(hip_lib, tmp_path, monkeypatch, world, method, n_axons, dist0):
+    _partitioned_against_single_rank(tmp_path, monkeypatch, world, method, n_axons, dist0)
+
+
+def test_partitioned_gmres_with_two_ranks_on_one_gpu(hip_lib, tmp_path, monkeypatch):
+    """the KNP system solved with restarted GMRES (KNP_KNP_KRYLOV=gmres in the workers and in the single-rank run): the all-reduced
+    rows of eight inner products (OP_GM_H), the norms and the joint restarts of a partitioned run"""
+    monkeypatch.setenv("KNP_KNP_KRYLOV", "gmres")
+    _partitioned_against_single_rank(tmp_path, monkeypatch, 2, "slab", 4, 1, krylov="gmres")
+
+
+def _partitioned_against_single_rank(tmp_path, monkeypatch, world, method, n_axons, dist0, krylov="bicgstab"):
     # dist0 = 1: the finest conforming level ROW-DISTRIBUTED (sub-assembled matrices, point-to-point exchange of the shared dofs, one
     # all-reduce of the level-1 residual; csrc/amg_vcycle.hip dist0) -- the default of a partitioned run; 0: replicated behind an all-reduce of
     # the level-0 residual (rounds 1-2).  The small meshes get a coarse-size limit that leaves at least one level below the finest.
@@ -86,6 +98,7 @@ def test_partitioned_solver_with_several_ranks_on_one_gpu(hip_lib, tmp_path, mon
         seen[d["cells"]] += 1
         assert len(d["emi_its"]) == steps and d["emi_its"].max() < 1000 and d["knp_its"].max() < 1000
         assert int(d["dist0"]) == (2 if dist0 else 0), d["dist0"]              # EMI + the shared KNP hierarchy, both row-distributed
+        assert str(d["krylov"]) == krylov == _single_rank.krylov, (str(d["krylov"]), _single_rank.krylov)
         # the partitioned preconditioner is the single-rank one up to rounding: same iteration counts
         assert np.abs(d["emi_its"] - np.asarray(emi_ref)).max() <= 1 and np.abs(d["knp_its"] - np.asarray(knp_ref)).max() <= 1, (
             d["emi_its"], emi_ref, d["knp_its"], knp_ref)
