@@ -79,7 +79,8 @@ struct AmgHierarchy {
     std::vector<AmgLevel> levels;
     float* pinv = nullptr;          // dense pseudo-inverse of the coarsest level (fp32 storage)
     // Partitioned runs: level 0 holds THIS RANK'S rows only (the conforming dofs of its owned cells + of the membrane facets assigned to it,
-    // local numbering), its matrix sub-assembled from those cells / facets: products are per-rank partial sums, made consistent at the
+    // local numbering), its matrix this rank's share of the global one (the shares add up to it, also as fp32 values: every entry is on
+    // one rank -- amg.py: Dist0Space.split_matrix): products are per-rank partial sums, made consistent at the
     // shared dofs by interface_accumulate (comm.hip); levels >= 1 stay replicated behind one all-reduce of the level-1 residual
     bool dist0 = false;
     double* t0 = nullptr;           // [ncol][n_0] work vector of the distributed level

@@ -151,7 +151,7 @@ int knp_amg_finish(knp_ctx* c, int which, int64_t n, const double* pinv) { retur
 int knp_amg_finish_f32(knp_ctx* c, int which, int64_t n, const float* pinv) { return amg_finish_impl(c, which, n, nullptr, pinv); }
 
 // Marks hierarchy `which` as carrying a ROW-DISTRIBUTED level 0 (between knp_amg_begin and the first knp_amg_level): ncg, dg2cg and the
-// level-0 matrices are this rank's rows in local numbering, A sub-assembled from its own cells / facets (knp_amg_interface first).
+// level-0 matrices are this rank's rows in local numbering, A this rank's share of the global matrix (knp_amg_interface first).
 int knp_amg_dist0(knp_ctx* c, int which) {
     if (!c) return -1;
     AmgHierarchy* H = amg_slot(c, which);

@@ -376,7 +376,7 @@ int amg_vcycle_levels(knp_ctx* c, AmgHierarchy& H, int l0, hipStream_t on_stream
 // ---- row-distributed level 0 (partitioned runs) ---------------------------------------------------------------------------------------
 // Vectors on level 0 come in two kinds (the usual bookkeeping of non-overlapping domain decomposition): ACCUMULATED -- every rank that
 // has a shared dof holds its full value (x, the smoother's d, the accumulated residual) -- and DISTRIBUTED -- every rank holds the
-// part its own cells / facets contributed (the restricted DG residual b, and every product with the sub-assembled matrix).  A product
+// part its own cells / facets contributed (the restricted DG residual b, and every product with the rank's share of the matrix).  A product
 // needs no communication; turning its result into an accumulated vector is one interface exchange (interface_accumulate); the
 // restriction to the replicated level 1 is a per-rank partial sum behind one all-reduce of n_1 values (29 k at r=2, 6.5x fewer than the
 // level-0 vector the replicated design all-reduced).  Arithmetic per dof is that of smooth() / amg_vcycle_eager on the global level.

@@ -290,8 +290,10 @@ class Dist0Space:
 
     * rank r's ELEMENTS are its owned cells and the membrane facets whose first cell it owns; its level-0 rows `verts` are the conforming
       dofs those elements touch (ascending global number = local number);
-    * its level-0 matrix is assembled from its elements only, so sum_r S_r^T A_r S_r = A (S_r: selection of the rank's rows) and a product
-      with an accumulated vector is a per-rank partial sum;
+    * its level-0 matrix holds a share of the global one, sum_r S_r^T A_r S_r = A (S_r: selection of the rank's rows), so a product
+      with an accumulated vector is a per-rank partial sum: `local_matrix` assembles it from the rank's elements (what a rank could do
+      without the global matrix), `split_matrix` cuts it out of the global matrix entry by entry (what `localize` uploads: the
+      hierarchy is built from the global matrix anyway, and this split survives the device's fp32 rounding);
     * dofs touched by elements of several ranks are SHARED: `interface_tables` lists them per peer in ascending global order (both sides
       agree without communication: every rank computes all of this from the global mesh).
     """
@@ -344,14 +346,35 @@ class Dist0Space:
         A.sort_indices()
         return A
 
-    def localize(self, levels, A_local):
-        """The hierarchy with level 0 replaced by the rank's rows: A sub-assembled, inverse diagonal / prolongator rows of the GLOBAL level
-        (so the smoother and the Galerkin coarse operators are exactly those of the replicated hierarchy).  None if there is no coarser level."""
+    def split_matrix(self, A):
+        """The rank's share [n, n] of the GLOBAL level-0 matrix A: every entry goes, whole, to the lowest rank that holds both its row
+        and its column (the rank of an element that produced it holds both, so there is one).  As with `local_matrix`,
+        sum_r S_r^T A_r S_r = A -- but entry by entry, so the sum stays A when the device rounds every rank's values to fp32
+        (amg_upload.hip: up_csr).  The sub-assembled parts do not have that property: a coupling between two shared dofs is the
+        sum of several ranks' element contributions, and fl32(a_1) + fl32(a_2) is not fl32(a_1 + a_2).  The partitioned V-cycle
+        then ran on a level-0 operator 2.5e-8 away from the replicated one (P1 box, four ranks), and the Krylov iterates moved by
+        1e-7 -- harmless for convergence, but three orders above the rounding error the iterates are compared at."""
+        A = A.tocsr()
+        sub = A[self.verts][:, self.verts].tocoo()
+        gi, gj = self.verts[sub.row], self.verts[sub.col]
+        mine = np.ones(len(gi), dtype=bool)
+        for q in range(self.rank):                                 # a lower rank that holds both dofs takes the entry
+            has = np.zeros(self.space.n, dtype=bool)
+            has[self.rank_verts[q]] = True
+            mine &= ~(has[gi] & has[gj])
+        Al = sp.coo_matrix((sub.data[mine], (sub.row[mine], sub.col[mine])), shape=(self.n, self.n)).tocsr()
+        Al.sort_indices()
+        return Al
+
+    def localize(self, levels, A_local=None):
+        """The hierarchy with level 0 replaced by the rank's rows: the rank's share of the global A (`split_matrix`; or A_local, a
+        sub-assembled matrix of `local_matrix`), inverse diagonal / prolongator rows of the GLOBAL level (so the smoother and the
+        Galerkin coarse operators are exactly those of the replicated hierarchy).  None if there is no coarser level."""
         if len(levels) < 2:
             return None
         g = levels[0]
         lv = Level()
-        lv.A = A_local
+        lv.A = self.split_matrix(g.A) if A_local is None else A_local
         lv.dinv = np.ascontiguousarray(g.dinv[self.verts])
         lv.rho, lv.cheb_degree, lv.cheb_lower = g.rho, g.cheb_degree, g.cheb_lower
         lv.P = g.P.tocsr()[self.verts].tocsr()

@@ -46,15 +46,26 @@ class Partition:
     """method "slab": contiguous chunks of the cells sorted by centroid coordinate `axis` (idealized BoxMesh geometries: <= 2
     peers per rank); "rcb": recursive coordinate bisection (unstructured meshes, e.g. the EMIx reconstruction)."""
 
-    def __init__(self, mesh, world, axis=0, method="slab", fractions=None):
+    def __init__(self, mesh, world=None, axis=0, method="slab", fractions=None, owner=None):
         # fractions (slab only): world + 1 increasing numbers from 0 to 1, the share of the sorted cells below every cut (default:
         # equal parts); lets a test build a rank so thin that ALL its cells touch a cut
+        # owner: the rank of every cell, given explicitly (ranks 0 ... world - 1, each with at least one cell; `method` is then not
+        # used); lets a test build cuts that meet, so that a conforming dof has three or more owners
         self.mesh = mesh
-        self.world = int(world)
         nc = mesh.num_cells()
-        if method == "rcb":
+        if owner is not None:
+            owner = np.ascontiguousarray(owner, dtype=np.int32)
+            ranks = np.unique(owner)
+            if owner.shape != (nc,) or not np.array_equal(ranks, np.arange(len(ranks))):
+                raise ValueError("owner: one rank per cell, every rank from 0 to the largest one with at least one cell")
+            if world is not None and int(world) != len(ranks):
+                raise ValueError("owner lists %d ranks, world is %d" % (len(ranks), int(world)))
+            self.world = len(ranks)
+        elif method == "rcb":
+            self.world = int(world)
             owner = rcb_owner(mesh.cell_midpoints(), self.world)
         elif method == "slab":
+            self.world = int(world)
             cm = mesh.cell_midpoints()[:, axis]
             order = np.argsort(cm, kind="stable")
             owner = np.empty(nc, dtype=np.int32)

@@ -590,7 +590,7 @@ class Solver:
             dg2cg = self._local_dg2cg()
             d0 = self._dist0()
             if d0 is not None:                      # partitioned run: this rank's rows of the finest conforming level
-                local = d0.localize(levels, d0.local_matrix(kappa, membrane_C=_f(self.C_phi)))
+                local = d0.localize(levels)
                 if local is not None:
                     dev.amg_upload(0, d0.local_dg2cg(self.local_mesh.cells_global), local, dist0=True)
                     self.amg_dist0 = getattr(self, "amg_dist0", 0) + 1          # hierarchies uploaded in the row-distributed form
@@ -742,9 +742,7 @@ class Solver:
         for members, levels in groups:
             local = None
             if d0 is not None:                      # partitioned run: this rank's rows of the finest conforming level
-                gsub = self._amg_global()[1]
-                D = np.mean([self._by_tag(self.ion_list[k]['D_sub'], gsub) for k in members], axis=0)
-                local = d0.localize(levels, d0.local_matrix(D, mass_coef=np.full(len(D), 1.0 / _f(self.dt))))
+                local = d0.localize(levels)
             if local is not None:
                 self.dev.amg_upload(1 + members[0], d0.local_dg2cg(self.local_mesh.cells_global), local, ncol=len(members), dist0=True)
                 self.amg_dist0 = getattr(self, "amg_dist0", 0) + 1

@@ -10,6 +10,8 @@
     rules with the distance of every decision from its threshold; GM_CASES / GM_FREE_CASES: what the device is compared on.
   * `launches`: which (kernel, G, NC) instantiations a hierarchy reaches (amg_vcycle.hip: by_density).
   * `synthetic`: seeded hand-built hierarchies (any density, any level size) for tests/test_amg_ref_host.py and a comparison on the device.
+  * `Dist0` / `vcycle_dist0`: level 0 in the row-distributed form of a partitioned run (amg_vcycle_dist0, interface_accumulate) -- `store`,
+    `emi_xk` and `knp_xk` take it as `dist=`; DIST_MUTATIONS: its deliberate errors; PART_GROUPS: what the partitioned device is compared on.
 A `mut = (name, level)` argument applies one deliberate error (MUTATIONS; drop_tail: (name, (level, matrix))) -- the CPU tests show
 that each one is far above the comparison bound (`bound`).
 The "fsum" fallback is NOT a wider arithmetic: only the row sums of the matrix products are exactly rounded, the vector updates, inner
@@ -79,8 +81,10 @@ def _drop_tail(M, ncol):
     return M, len(hit)
 
 
-def store(levels, dtype=np.float64, mut=None, ncol=1):
-    """device storage of `levels` (objects with A, dinv, rho, cheb_degree, cheb_lower, P, R; the last one with pinv) in `dtype`"""
+def store(levels, dtype=np.float64, mut=None, ncol=1, dist=None):
+    """device storage of `levels` (objects with A, dinv, rho, cheb_degree, cheb_lower, P, R; the last one with pinv) in `dtype`.
+    dist = a `Dist0`: level 0 also in the row-distributed form of a partitioned run, every rank's rows as the device stores them
+    (`vcycle_dist0`); or (`Dist0`, level-0 matrices of the ranks) for other matrices than Dist0Space.localize's split of the global one"""
     fsum = dtype == "fsum"
     wd = np.float64 if fsum else dtype
     name, ml = mut if mut else (None, -1)
@@ -107,6 +111,19 @@ def store(levels, dtype=np.float64, mut=None, ncol=1):
     assert name != "drop_tail" or dropped, "drop_tail: no row of length 1 modulo U * G"
     pinv = np.asarray(levels[-1].pinv).astype(np.float32).astype(np.float64)
     out[-1].pinv = _FsumCsr(pinv) if fsum else pinv.astype(wd)
+    if dist is not None:
+        d0, A_local = dist if isinstance(dist, tuple) else (dist, [None] * dist.world)
+        assert len(levels) >= 2, "a distributed level 0 needs a coarser level"
+        out[0].dist0, out[0].ranks = d0, []
+        for d, Ar in zip(d0.D, A_local):
+            lv, L = d.localize(levels, Ar)[0], _Level()
+            L.n, L.dinv = lv.A.shape[0], np.asarray(lv.dinv, dtype=np.float64).astype(wd)
+            for key in ("A", "P", "R"):
+                M = sp.csr_matrix(getattr(lv, key), dtype=np.float64)
+                M.sort_indices()
+                M = sp.csr_matrix((M.data.astype(np.float32).astype(np.float64), M.indices, M.indptr), shape=M.shape)
+                setattr(L, key, _FsumCsr(M) if fsum else M.astype(wd))
+            out[0].ranks.append(L)
     return out
 
 
@@ -161,6 +178,155 @@ def _vcycle_levels(H, B, l, mut):
     return X
 
 
+# ---- the row-distributed level 0 of a partitioned run (csrc/amg_vcycle.hip: amg_vcycle_dist0; csrc/comm.hip: interface_accumulate) ----
+# deliberate errors of the distributed form (mut = (name, 0)): the third and later owners of a shared dof left out of its sum; A d of
+# the extra Chebyshev steps not accumulated; the zero-guess smoother on the un-accumulated b; the last rank's part missing from the
+# level-1 right-hand side; a message read as [column][position] instead of [position][column]; a peer's message read at the offset
+# of that peer's message to another rank
+DIST_MUTATIONS = ("two_owners", "no_step_accumulation", "zero_guess_unaccumulated", "rank_missing_level1", "message_interleave",
+                  "peer_offset")
+
+
+class Dist0:
+    """The finest conforming level of `host` in the row-distributed form of the cell partition `owner` [nc]: per rank the rows
+    (knpemidg.amg.Dist0Space), the shared-dof tables the device gets (interface_tables), the owned cells and the DG <-> conforming
+    maps of those cells; `emi_matrices`: the ranks' EMI level-0 matrices assembled from their own elements
+    (Dist0Space.local_matrix), which the device does NOT run on (their fp32 roundings do not add up to the rounded global matrix)."""
+
+    def __init__(self, host, owner):
+        from knpemidg import amg
+        self.host, self.owner = host, np.asarray(owner)
+        self.world = int(self.owner.max()) + 1
+        mesh, surf = host.mt[0], np.asarray(host.mt[2].array())
+        space = host.cs2 or host.cs
+        mem = np.nonzero((mesh.facet_cells[:, 1] >= 0) & np.isin(surf, [1]))[0]
+        self.D = [amg.Dist0Space(space, self.owner, mem, r, self.world) for r in range(self.world)]
+        self.tabs = [d.interface_tables() for d in self.D]
+        self.cells = [np.nonzero(self.owner == r)[0] for r in range(self.world)]
+        nd = host.nd
+        # DG dofs of the owned cells (positions in a global DG vector) and their conforming dofs in the rank's numbering
+        self.dg = [(c[:, None] * nd + np.arange(nd)[None, :]).ravel() for c in self.cells]
+        self.cg = [d.local_dg2cg(c).ravel() for d, c in zip(self.D, self.cells)]
+        # per rank: the concatenated send list, and per peer (offset, length) of the message to it
+        self.send_idx = [np.concatenate(t[1]) if t[0] else np.zeros(0, dtype=np.int64) for t in self.tabs]
+        self.send_off = [np.concatenate([[0], np.cumsum([len(l) for l in t[1]])]).astype(np.int64) for t in self.tabs]
+        self._emi = None
+
+    def owners(self):
+        """number of ranks that hold every conforming dof"""
+        cnt = np.zeros(self.D[0].space.n, dtype=np.int64)
+        for d in self.D:
+            cnt[d.verts] += 1
+        return cnt
+
+    def emi_matrices(self):
+        """the ranks' EMI level-0 matrices assembled from their own elements"""
+        if self._emi is None:
+            pb = self.host.pb
+            self._emi = [d.local_matrix(pb.kappa(), membrane_C=float(pb.C_phi)) for d in self.D]
+        return self._emi
+
+    def transfers(self, dtype):
+        """per rank (P_dg of the owned cells [owned DG dofs, rows], its transpose) in the working precision"""
+        out = []
+        for d, dg, cg in zip(self.D, self.dg, self.cg):
+            Pd = sp.csr_matrix((np.ones(len(cg)), (np.arange(len(cg)), cg)), shape=(len(cg), d.n))
+            out.append((_FsumCsr(Pd), _FsumCsr(Pd.T)) if dtype == "fsum" else (Pd.astype(dtype), Pd.T.tocsr().astype(dtype)))
+        return out
+
+
+def _accumulate(d0, V, mut=None):
+    """interface_accumulate on V[column][rank]: every rank packs its values at the dofs it shares with each peer ([position][column]),
+    reads the peers' messages, and replaces every shared dof by the sum over all its owners in ascending rank order"""
+    ncol, name = len(V), (mut[0] if mut else None)
+    send = [np.stack([V[j][r][idx] for j in range(ncol)], axis=1).ravel() for r, idx in enumerate(d0.send_idx)]
+    out = [[None] * d0.world for _ in range(ncol)]
+    for r, (peers, lists, uvtx, aptr, asrc) in enumerate(d0.tabs):
+        if not peers:
+            for j in range(ncol):
+                out[j][r] = V[j][r]
+            continue
+        recv = []
+        for q, l in zip(peers, lists):
+            k = d0.tabs[q][0].index(r)
+            if name == "peer_offset":                                   # the offset of q's message to its next peer
+                k = (k + 1) % len(d0.tabs[q][0])
+            off = min(int(d0.send_off[q][k]), len(d0.send_idx[q]) - len(l))
+            recv.append(send[q][off * ncol:(off + len(l)) * ncol])
+        recv = np.concatenate(recv)
+        total = len(recv) // ncol
+        aptr, asrc, uvtx = np.asarray(aptr, dtype=np.int64), np.asarray(asrc, dtype=np.int64), np.asarray(uvtx, dtype=np.int64)
+        cnt = np.diff(aptr)
+        if name == "two_owners":
+            cnt = np.minimum(cnt, 2)
+        for j in range(ncol):
+            v = V[j][r]
+            w = v.copy()
+            s = np.zeros(len(uvtx), dtype=v.dtype)
+            for t in range(int(cnt.max())):                             # the terms of every sum in the order of k_if_add
+                on = np.nonzero(cnt > t)[0]
+                src = asrc[aptr[on] + t]
+                at = src + j * total if name == "message_interleave" else src * ncol + j
+                s[on] = s[on] + np.where(src < 0, v[uvtx[on]], recv[np.where(src < 0, 0, at)])
+            w[uvtx] = s
+            out[j][r] = w
+    return out
+
+
+def _smooth_dist0(L, B, X, mut):
+    """dist0_smooth: `smooth` on the ranks' rows -- B[column][rank] partial sums, X accumulated (None: zero guess); every product with
+    a sub-assembled matrix is accumulated before it is used"""
+    name = mut[0] if mut else None
+    lmax, lmin = L.rho, L.cheb_lower * L.rho
+    theta, delta = (lmax + lmin) / 2, (lmax - lmin) / 2
+    sigma = theta / delta
+    rho = 1 / sigma
+    ranks, nr = L.ranks, len(L.ranks)
+    each = lambda f: [[f(j, r) for r in range(nr)] for j in range(len(B))]
+    if X is None:
+        R = each(lambda j, r: B[j][r].copy())
+        if name != "zero_guess_unaccumulated":
+            R = _accumulate(L.dist0, R, mut)
+    else:
+        R = _accumulate(L.dist0, each(lambda j, r: B[j][r] - ranks[r].A @ X[j][r]), mut)
+    D = each(lambda j, r: ranks[r].dinv * R[j][r] * (1 / theta))
+    X = each(lambda j, r: D[j][r].copy()) if X is None else each(lambda j, r: X[j][r] + D[j][r])
+    for _ in range(1, L.cheb_degree):
+        rho_new = 1 / (2 * sigma - rho)
+        T = each(lambda j, r: ranks[r].A @ D[j][r])
+        if name != "no_step_accumulation":
+            T = _accumulate(L.dist0, T, mut)
+        R = each(lambda j, r: R[j][r] - T[j][r])
+        D = each(lambda j, r: (rho_new * rho) * D[j][r] + (2 * rho_new / delta) * ranks[r].dinv * R[j][r])
+        X = each(lambda j, r: X[j][r] + D[j][r])
+        rho = rho_new
+    return X
+
+
+def vcycle_dist0(H, B, mut=None):
+    """amg_vcycle_dist0 (and restrict_tail for a transfer-only level 0): B[column][rank] the ranks' partial sums of the level-0
+    right-hand side; returns X[column][rank], accumulated.  The level-1 right-hand side is the sum of the ranks' parts in rank order
+    (the all-reduce), the levels below are the replicated ones (`_vcycle_levels`)."""
+    L = H[0]
+    name = mut[0] if mut else None
+    ranks, nr = L.ranks, len(L.ranks)
+    assert name is None or name in DIST_MUTATIONS
+    part_of = range(nr - 1) if name == "rank_missing_level1" else range(nr)
+
+    def allreduce(parts):
+        s = parts[part_of[0]].copy()
+        for r in part_of[1:]:
+            s = s + parts[r]
+        return s
+    if L.cheb_degree == 0:
+        Xc = _vcycle_levels(H, [allreduce([ranks[r].R @ b[r] for r in range(nr)]) for b in B], 1, None)
+        return [[ranks[r].P @ xc for r in range(nr)] for xc in Xc]
+    X = _smooth_dist0(L, B, None, mut)
+    Xc = _vcycle_levels(H, [allreduce([ranks[r].R @ (b[r] - ranks[r].A @ x[r]) for r in range(nr)]) for b, x in zip(B, X)], 1, None)
+    X = [[x[r] + ranks[r].P @ xc for r in range(nr)] for x, xc in zip(X, Xc)]
+    return _smooth_dist0(L, B, X, mut)
+
+
 def vcycle(H, B, mut=None):
     """x = V(b) for every row of B [ncol, n_0] (or one vector [n_0]); H from `store`"""
     B = np.asarray(B)
@@ -211,6 +377,24 @@ class _TwoLevel:
         d = np.asarray(dg2cg).ravel()
         Pd = sp.csr_matrix((np.ones(len(d)), (np.arange(len(d)), d)), shape=(len(d), ncg))
         self.Pd, self.Pdt = (Pd.astype(self.wd), Pd.T.tocsr().astype(self.wd)) if dtype != "fsum" else (_FsumCsr(Pd), _FsumCsr(Pd.T))
+        self._dtype, self._tr = dtype, None
+
+    def coarse(self, H, C, mut):
+        """P_dg V(P_dg^T c) for the columns C [ncol, ndof] through the hierarchy H; with a row-distributed level 0 every rank restricts
+        the DG dofs of its owned cells (partial sums), and prolongs its accumulated rows to them"""
+        if not hasattr(H[0], "ranks"):
+            return [self.Pd @ e for e in vcycle(H, np.stack([self.Pdt @ c for c in C]), mut)]
+        d0 = H[0].dist0
+        if self._tr is None:
+            self._tr = d0.transfers(self._dtype)
+        X = vcycle_dist0(H, [[Pt @ c[dg] for (_, Pt), dg in zip(self._tr, d0.dg)] for c in C], mut)
+        out = []
+        for x in X:
+            z = np.zeros(len(C[0]), dtype=self.wd)
+            for (P, _), dg, xr in zip(self._tr, d0.dg, x):
+                z[dg] = P @ xr
+            out.append(z)
+        return out
 
 
 class EmiPrecond(_TwoLevel):
@@ -225,7 +409,7 @@ class EmiPrecond(_TwoLevel):
         if self.lmax > 0.0:
             cr, ctt, _ = _cheb2_coefficients(self.lmax, self.wd)
             z = _blocks(self.binv[0], cr * r - ctt * (self.A[0] @ z))
-        return z + self.Pd @ vcycle(self.H, self.Pdt @ r, self.mut)
+        return z + self.coarse(self.H, [r], self.mut)[0]
 
 
 class KnpPrecond(_TwoLevel):
@@ -244,9 +428,9 @@ class KnpPrecond(_TwoLevel):
         for s, (A, Bi, r) in enumerate(zip(self.A, self.binv, R)):
             t = A @ _blocks(Bi, r if block_scale is None else block_scale[s] * r)
             Z.append(_blocks(Bi, cr * r - ctt * t))
-            C.append(self.Pdt @ (r - (1 / theta) * t))
-        E = vcycle(self.Hs, np.stack(C), self.mut) if self.shared else [vcycle(H, c, self.mut) for H, c in zip(self.Hs, C)]
-        return [z + self.Pd @ e for z, e in zip(Z, E)]
+            C.append(r - (1 / theta) * t)
+        E = self.coarse(self.Hs, C, self.mut) if self.shared else [self.coarse(H, [c], self.mut)[0] for H, c in zip(self.Hs, C)]
+        return [z + e for z, e in zip(Z, E)]
 
 
 def bicgstab(As, bs, precond, iters, dtype=np.float64):
@@ -671,12 +855,48 @@ class Host:
         h.ref.pb = h.pb
         return h
 
-    def emi_levels(self):
-        """the production hierarchy (Case.upload_amg of test_gpu_krylov.py)"""
+    def emi_levels(self, level0_degree=None):
+        """the production hierarchy (Case.upload_amg of test_gpu_krylov.py); level0_degree: Chebyshev degree of a P1 mesh's finest
+        conforming level (KNP_AMG_DEGREE0_EMI for this build; None: as the environment has it)"""
+        import os
         from knpemidg import amg
         tags = self.mt[2].array()
         mem = sorted({int(t) for t in np.unique(tags[self.pb.mem])})
-        return amg.build_emi_levels(self.cs, self.cs2, tags, mem, self.pb.kappa(), self.pb.C_phi)
+        keep = os.environ.get("KNP_AMG_DEGREE0_EMI")
+        if level0_degree is not None:
+            os.environ["KNP_AMG_DEGREE0_EMI"] = str(int(level0_degree))
+        try:
+            return amg.build_emi_levels(self.cs, self.cs2, tags, mem, self.pb.kappa(), self.pb.C_phi)
+        finally:
+            if level0_degree is not None:
+                os.environ.pop("KNP_AMG_DEGREE0_EMI")
+                if keep is not None:
+                    os.environ["KNP_AMG_DEGREE0_EMI"] = keep
+
+    def local_problem(self, loc):
+        """the oracle's problem of one rank (knpemidg.partition.LocalMesh: owned cells, then ghosts) with coefficients and state
+        sliced from the global arrays -- what a partitioned run holds behind a halo exchange"""
+        import knpemi_oracle as ko
+        pbg, cg = self.pb, loc.cells_global
+        sub_l, surf_l = loc.localize(self.mt[1], self.mt[2], pbg.membrane_tags)
+        ions = [dict(ion, D=np.asarray(ion["D"])[cg].copy()) for ion in pbg.ions]
+        pbl = ko.Problem(loc.mesh, sub_l.array().astype(np.int64), surf_l.array(), pbg.p, ions, ko.idealized_params(),
+                         membrane_tags=pbg.membrane_tags)
+        assert (pbl.dt, pbl.C_phi, pbl.tau, pbl.splitting) == (pbg.dt, pbg.C_phi, pbg.tau, pbg.splitting)
+        pbl.c, pbl.c_prev_n, pbl.c_elim, pbl.phi = pbg.c[:, cg].copy(), pbg.c_prev_n[:, cg].copy(), pbg.c_elim[cg].copy(), pbg.phi[cg].copy()
+        pbl.phi_M = pbg.phi_M[loc.facets_global].copy()
+        for name in pbg.I_ch:
+            pbl.I_ch[name] = pbg.I_ch[name][loc.facets_global].copy()
+        return pbl
+
+    def knp_groups(self, level0_degree=1):
+        """[(members, levels)]: the production hierarchies of the solved species (amg.build_knp_groups, as knpemidg/solver.py calls
+        it; every ion of the host has one diffusion coefficient on all cells)"""
+        from knpemidg import amg
+        tags = np.asarray(self.mt[1].array())
+        D_subs = [{int(t): float(ion["D"][0]) for t in np.unique(tags)} for ion in self.pb.ions[:self.pb.N_ions]]
+        assert not self.materials and all(np.all(ion["D"] == ion["D"][0]) for ion in self.pb.ions)
+        return amg.build_knp_groups(self.cs, self.cs2, tags, D_subs, self.pb.dt, level0_degree)
 
     def scale(self, knp=False):
         """entry size of a synthetic hierarchy whose V-cycle answers in the size of the cell blocks' part of the preconditioner"""
@@ -738,14 +958,16 @@ class Host:
         return float(self.cell_peclet().max())
 
 
-def emi_xk(host, levels, cheb, k, dtype=np.float64, b=None, mut=None):
-    """x_k of the device's EMI PCG from x_0 = 0 with the two-level preconditioner over `levels`; cheb: the Chebyshev DG smoother"""
+def emi_xk(host, levels, cheb, k, dtype=np.float64, b=None, mut=None, dist=None):
+    """x_k of the device's EMI PCG from x_0 = 0 with the two-level preconditioner over `levels`; cheb: the Chebyshev DG smoother;
+    dist: a `Dist0` -- level 0 of the V-cycle in the row-distributed form of that partition (or the pair `store` takes)"""
     import types
     import krylov_ref as kr
     ref = host.ref
     b = ref.b_emi if b is None else np.asarray(b, dtype=np.float64).ravel()
     lmax = bj_lambda_max([ref.A_emi], [ref.binv_emi], [b]) if cheb else 0.0
-    M = EmiPrecond(ref.A_emi, ref.binv_emi, host.dg2cg, store(levels, dtype, mut), lmax, dtype, mut)
+    H = store(levels, dtype, mut, dist=dist)
+    M = EmiPrecond(ref.A_emi, ref.binv_emi, host.dg2cg, H, lmax, dtype, mut)
     return kr.pcg(types.SimpleNamespace(A_emi=ref.A_emi, b_emi=b, binv_emi=ref.binv_emi), 0.0, 0.0, precond=M, iters=k, dtype=dtype)[0]
 
 
@@ -754,7 +976,7 @@ def knp_lmax(host, blocks, bs):
     return bj_lambda_max(host.knp()[0], host.blocks(blocks), [np.asarray(b, dtype=np.float64).ravel() for b in bs])
 
 
-def _knp_system(host, levels, dtype, bs, lmax_bs, mut, blocks, lmax):
+def _knp_system(host, levels, dtype, bs, lmax_bs, mut, blocks, lmax, dist=None):
     """(A_s, b_s, the two-level preconditioner) of a KNP solve on `host`'s matrices: the arguments of knp_xk"""
     As, _, b0 = host.knp()
     binvs = host.blocks(blocks)
@@ -764,20 +986,21 @@ def _knp_system(host, levels, dtype, bs, lmax_bs, mut, blocks, lmax):
         lmax = bj_lambda_max(As, binvs, bs if lmax_bs is None else lmax_bs)
     shared = hasattr(levels[0], "A")
     amg_mut = mut if isinstance(mut, tuple) else None       # (a name alone: one of GM_MUTATIONS)
-    Hs = store(levels, dtype, amg_mut, ncol=ns) if shared else [store(lv, dtype, amg_mut) for lv in levels]
+    Hs = store(levels, dtype, amg_mut, ncol=ns, dist=dist) if shared else [store(lv, dtype, amg_mut, dist=dist) for lv in levels]
     return As, bs, KnpPrecond(As, binvs, host.dg2cg, Hs, lmax, dtype, amg_mut)
 
 
 def knp_xk(host, levels, k, dtype=np.float64, bs=None, lmax_bs=None, mut=None, blocks="cell", lmax=None, method="bicgstab",
-           reverse=False):
+           reverse=False, dist=None):
     """x_k [nsys, ndof] of the device's KNP solve from x_0 = 0.  levels: one hierarchy shared by the species (its columns), or a
     list with one hierarchy per species.  lmax_bs: the right-hand sides the spectral bound was estimated from (default: bs).
     blocks: the cell blocks of the preconditioner and of the spectral bound -- "cell" (per-cell inverses with the drift), "table" (the
     drift-free class table of solve.hip) or an explicit list (lagged inverses of another potential: `Host.variant(...).blocks`).
     lmax: the spectral bound itself, where the device keeps one estimated on other matrices (`knp_lmax`).
     method: "bicgstab", or ("gmres", m) for GMRES restarted after m columns -- k may then be a sequence of counts (`gmres`), mut one
-    of GM_MUTATIONS, and reverse sums the inner products from the other end."""
-    As, bs, M = _knp_system(host, levels, dtype, bs, lmax_bs, mut, blocks, lmax)
+    of GM_MUTATIONS, and reverse sums the inner products from the other end.
+    dist: a `Dist0` -- level 0 of the V-cycle in the row-distributed form of that partition."""
+    As, bs, M = _knp_system(host, levels, dtype, bs, lmax_bs, mut, blocks, lmax, dist)
     if method == "bicgstab":
         return bicgstab(As, bs, M, k, dtype)
     assert method[0] == "gmres"
@@ -907,6 +1130,96 @@ def switch_sequence(lo, bs):
         step("7 high again, Peclet not seen yet", hi2, hi2, T, lm_lo, switched_at_once=(C, None), new_bound=(T, None)),
         step("8 high again", None, hi2, C, None, stale_array=(hi.blocks(C), None), bound_kept=(C, lm_lo)),
     ]
+
+
+# ---- the partitioned comparison (tests/test_gpu_amg_partition.py, tests/amg_partition_worker.py) -------------------------------------------
+# Production hierarchies with KNP_AMG_MAXCOARSE = 60 (both boxes then have a level below the finest one: [267, 52] on the P1 box,
+# [679, 124, 26] on the P2 box).  A case: ("emi", level-0 degree, Chebyshev DG smoother, counts) or ("knp", solved species, block set,
+# level-0 degree, None (BiCGStab) or the restart length of GMRES, counts); level-0 degree None: the P2 box (its top level has degree
+# 2).  PART_GROUPS: (group, mesh, row-distributed level 0, {partition: cases}); one launch of the ranks serves a group's partition.
+PART_MAXCOARSE = "60"
+PART_GM_KS = (1, 2, 9, 10, 17, 20)                                     # with m = 8: the first and second restart behind 9 / 10 and 17,
+                                                                        # 20 as in GM_CASES: a partial pass of k_gm_dots in every one
+_EMI1 = (("emi", 1, False, (1, 2, 3)), ("emi", 1, True, (1, 2, 3)))
+_KNP2 = (("knp", 2, "cell", 1, None, (1, 2)), ("knp", 2, "table", 1, None, (1, 2)))
+# (x_2 and x_3 of the P2 box with the Chebyshev DG smoother are ill-conditioned: bounds 1.15e-9 and 1.53e-9 of the result)
+_P2 = (("emi", None, False, (1, 2, 3)), ("emi", None, True, (1,)), ("knp", 2, "cell", None, None, (1, 2)))
+PART_GROUPS = (
+    ("P1-emi", "box_P1", True, {"slab2": _EMI1, "thin3": _EMI1,
+                                "quad4": _EMI1 + tuple(("emi", d, cheb, (1, 2, 3)) for d in (0, 2) for cheb in (False, True))}),
+    ("P1-knp2", "box_P1", True, {"slab2": _KNP2,
+                                 "quad4": _KNP2 + (("knp", 2, "cell", 0, None, (1, 2)), ("knp", 2, "table", 1, 8, PART_GM_KS))}),
+    ("P1-knp34", "box_P1", True, {"quad4": (("knp", 3, "cell", 1, None, (1, 2)), ("knp", 4, "table", 1, None, (1, 2)))}),
+    ("P2", "box_P2", True, {"slab2": _P2, "quad4": _P2}),
+    ("P1-replicated", "box_P1", False, {"slab2": _EMI1 + _KNP2[:1]}),
+)
+PART_LAUNCHES = tuple((g, p) for g, _, _, parts in PART_GROUPS for p in parts)
+
+
+def part_group(name):
+    return next(g for g in PART_GROUPS if g[0] == name)
+
+
+def part_partition(mesh, name):
+    """the partitions of the comparison: two x-slabs; three x-slabs whose middle one has no interior cell; the four quadrants of the
+    y-z plane about the box centre (conforming dofs on the centre line have four owners, ranks 0 and 3 share dofs and no facet)"""
+    from knpemidg.partition import Partition
+    if name == "slab2":
+        return Partition(mesh, 2, method="slab")
+    if name == "thin3":
+        return Partition(mesh, 3, method="slab", fractions=[0.0, 0.49, 0.51, 1.0])
+    assert name == "quad4"
+    mid = mesh.cell_midpoints()
+    centre = 0.5 * (mesh.coords.min(axis=0) + mesh.coords.max(axis=0))
+    return Partition(mesh, owner=(mid[:, 1] > centre[1]).astype(np.int32) + 2 * (mid[:, 2] > centre[2]).astype(np.int32))
+
+
+def part_host_key(mesh, case):
+    """the arguments of `Host` for a case (EMI cases run on the host of the two-species cases at the synthetic potential)"""
+    if case[0] == "emi":
+        return mesh, None, 1.0, False
+    return mesh, IONS[case[1]], (1.0 if case[2] == "cell" else TABLE_PHI_SCALE), False
+
+
+def part_case_id(case):
+    if case[0] == "emi":
+        return "emi deg0=%s cheb=%d" % (case[1], case[2])
+    return "knp ns=%d %s deg0=%s %s" % (case[1], case[2], case[3], "bicgstab" if case[4] is None else "gmres(%d)" % case[4])
+
+
+def part_levels(host, case):
+    """the production hierarchy of a case (KNP: the one all species share), built under KNP_AMG_MAXCOARSE = PART_MAXCOARSE"""
+    import os
+    assert os.environ.get("KNP_AMG_MAXCOARSE") == PART_MAXCOARSE
+    if case[0] == "emi":
+        levels = host.emi_levels(case[1])
+    else:
+        groups = host.knp_groups(1 if case[3] is None else case[3])
+        assert len(groups) == 1 and list(groups[0][0]) == list(range(case[1])), "the species do not share one hierarchy"
+        levels = groups[0][1]
+    assert len(levels) >= 2 and (case[0] == "emi" and case[1] is None or levels[0].cheb_degree == (case[1] if case[0] == "emi" else
+                                                                                                 2 if case[3] is None else case[3]))
+    return levels
+
+
+def part_xk(host, levels, case, dtype=np.float64, dist=None, mut=None, reverse=False, bs=None, ks=None):
+    """{k: x_k [columns, ndof]} of a case from the oracle's right-hand sides (bs: others) -- the global replica, or with `dist` (a
+    `Dist0`) level 0 in the row-distributed form"""
+    ks = case[-1] if ks is None else ks
+    if case[0] == "emi":
+        return {k: emi_xk(host, levels, case[2], k, dtype, b=None if bs is None else bs[0], mut=mut, dist=dist)[None] for k in ks}
+    if case[4] is None:
+        return {k: knp_xk(host, levels, k, dtype, bs=bs, blocks=case[2], mut=mut, dist=dist) for k in ks}
+    return knp_xk(host, levels, tuple(ks), dtype, bs=bs, blocks=case[2], mut=mut, dist=dist, method=("gmres", case[4]), reverse=reverse)
+
+
+def part_reference(host, levels, case, bs=None):
+    """{k: (x64 [columns, ndof], bounds [columns], scales [columns])} of the GLOBAL replica: `bound` of the float64 run against the
+    extended-precision one; GMRES: also of the float64 run with reversed sums (`gm_reference`)"""
+    x64, xhp = part_xk(host, levels, case, bs=bs), part_xk(host, levels, case, hp_dtype(), bs=bs)
+    more = [part_xk(host, levels, case, reverse=True, bs=bs)] if case[0] == "knp" and case[4] is not None else []
+    return {k: (x64[k], [bound(x64[k][s], xhp[k][s], *[m[k][s] for m in more]) for s in range(len(x64[k]))],
+                [float(np.abs(xhp[k][s]).max()) for s in range(len(x64[k]))]) for k in x64}
 
 
 def hp_dtype():

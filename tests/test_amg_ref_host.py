@@ -512,3 +512,145 @@ def test_gmres_free_running_cases_cover_the_lockstep():
     assert shared_differ and sooner, cyc
     assert any(len(a) != len(b) and min(len(a), len(b)) >= 1 and (a[-1] < m_of(c) or b[-1] < m_of(c)) and max(len(a), len(b)) >= 2
                for c, (a, b) in cyc.items()), cyc
+
+
+# ---- the row-distributed level 0 of a partitioned run (amg_ref.vcycle_dist0; tests/test_gpu_amg_partition.py) ---------------------------
+_PART_HOSTS, _PART_REF, _PART_DIST = {}, {}, {}
+
+
+@pytest.fixture
+def part_env(monkeypatch):
+    monkeypatch.setenv("KNP_AMG_MAXCOARSE", ar.PART_MAXCOARSE)
+    for key in ("KNP_AMG_DEGREE0_EMI", "KNP_AMG_DEGREE0_KNP", "KNP_AMG_DEGREE0"):
+        monkeypatch.delenv(key, raising=False)
+
+
+def _part_ref(mesh, case):
+    """(host, production hierarchy, amg_ref.part_reference) of a case, computed once"""
+    key = ar.part_host_key(mesh, case)
+    if (key, case) not in _PART_REF:
+        if key not in _PART_HOSTS:
+            _PART_HOSTS[key] = ar.Host(*key)
+        h = _PART_HOSTS[key]
+        levels = ar.part_levels(h, case)
+        _PART_REF[(key, case)] = (h, levels, ar.part_reference(h, levels, case))
+    return _PART_REF[(key, case)]
+
+
+def _part_dist(host, pname):
+    key = (id(host), pname)
+    if key not in _PART_DIST:
+        _PART_DIST[key] = ar.Dist0(host, ar.part_partition(host.mt[0], pname).owner)
+    return _PART_DIST[key]
+
+
+@pytest.mark.parametrize("group,pname", ar.PART_LAUNCHES, ids=lambda v: str(v))
+def test_partitioned_cases_have_their_bounds_and_the_distributed_replica_is_the_global_one(part_env, group, pname):
+    """every case the partitioned device runs (amg_ref.PART_GROUPS) has its bound -- amg_ref.bound raises above 1e-9 of the result --,
+    and with level 0 in the row-distributed form of the case's partition (every rank's share of the global matrix rounded to fp32 on
+    its own, right-hand sides as the ranks' partial sums, shared dofs summed over their owners in rank order, the level-1 right-hand
+    side summed over the ranks) the replica's x_k stays within that bound of the global replica's: the global replica is the
+    reference of the partitioned device.  (Measured: at most 0.64 bounds, EMI on the P1 box with the Chebyshev DG smoother, k = 3.)"""
+    _, mesh, dist0, parts = ar.part_group(group)
+    for case in parts[pname]:
+        h, levels, ref = _part_ref(mesh, case)
+        assert sorted(ref) == sorted(case[-1])
+        assert [lv.A.shape[0] for lv in levels] == ([267, 52] if mesh == "box_P1" else [679, 124, 26])
+        xd = ar.part_xk(h, levels, case, dist=_part_dist(h, pname)) if dist0 else None
+        for k, (x64, bds, scales) in ref.items():
+            for s in range(len(bds)):
+                assert 1e-13 * scales[s] <= bds[s] <= 1e-9 * scales[s]
+                moved = np.abs(xd[k][s] - x64[s]).max() / bds[s] if dist0 else 0.0
+                print("PART BOUND %s %s %s k=%d column %d: %.3g, distributed replica %.3g bounds away" % (group, pname, ar.part_case_id(case),
+                                                                                                        k, s, bds[s] / scales[s], moved))
+                assert moved <= 1.0, (group, pname, case, k, s, moved)
+
+
+def test_quadrant_partition_reaches_the_sums_of_three_and_four_owners(part_env):
+    """what the partitions of the comparison reach: on the quadrants, conforming dofs with four owners on the P1 box and with two,
+    three and four on the P2 box, interface peers that are no halo peers; on the slabs at most two owners; and a transfer-only level 0
+    exchanges nothing (its mutations of the exchange cannot show: the degree-0 cases check the all-reduced level-1 right-hand side)"""
+    for mesh, want in (("box_P1", {1, 2, 4}), ("box_P2", {1, 2, 3, 4})):
+        h = _part_ref(mesh, ("emi", 1 if mesh == "box_P1" else None, False, (1, 2, 3)))[0]
+        d0 = _part_dist(h, "quad4")
+        assert set(np.unique(d0.owners())) == want
+        part = ar.part_partition(h.mt[0], "quad4")
+        assert all(len(t[0]) == 3 for t in d0.tabs) and any(len(part.local(r).peers) == 2 for r in range(4))
+        assert max(np.diff(t[3]).max() for t in d0.tabs) == 4               # k_if_add: up to four terms
+        assert set(np.unique(_part_dist(h, "slab2").owners())) == {1, 2}
+
+
+# distance of x_k from the correct distributed replica, in bounds, smallest over the columns and the counts of the case, measured on
+# the quadrant partition (EMI: k = 1, 2, 3; KNP: k = 1, 2); 0: the error cannot show on that case
+_DIST_MEASURED = {
+    #                          EMI P1 deg 1  EMI P1 deg 2  EMI P2     KNP P1 3 species  KNP P1 4 species  KNP P2 2 species
+    "two_owners":               (8.2e9,       2.5e9,        1.1e9,     4.5e10,           3.0e10,           3.5e10),
+    "no_step_accumulation":     (0.0,         6.0e8,        2.0e9,     0.0,              0.0,              1.3e11),
+    "zero_guess_unaccumulated": (2.0e9,       7.8e7,        6.5e8,     4.3e10,           5.6e10,           1.1e11),
+    "rank_missing_level1":      (4.2e8,       1.5e8,        2.1e9,     8.5e10,           5.3e11,           7.3e10),
+    "message_interleave":       (0.0,         0.0,          0.0,       7.9e10,           2.0e12,           1.7e11),
+    "peer_offset":              (8.2e9,       2.5e9,        1.2e9,     1.5e11,           8.2e11,           1.6e11),
+}
+_DIST_CASES = (("box_P1", ("emi", 1, False, (1, 2, 3))), ("box_P1", ("emi", 2, False, (1, 2, 3))), ("box_P2", ("emi", None, False, (1, 2, 3))),
+               ("box_P1", ("knp", 3, "cell", 1, None, (1, 2))), ("box_P1", ("knp", 4, "table", 1, None, (1, 2))),
+               ("box_P2", ("knp", 2, "cell", None, None, (1, 2))))
+
+
+@pytest.mark.parametrize("mutation", ar.DIST_MUTATIONS)
+def test_mutations_of_the_distributed_replica_are_far_above_the_bound(part_env, mutation):
+    """Deliberate errors of the row-distributed form, on the quadrant partition (dofs with three and four owners, three interface
+    peers): the third and later owners of a shared dof left out of its sum; A d of the extra Chebyshev step not accumulated; the
+    zero-guess smoother on the un-accumulated b; the last rank's part missing from the level-1 right-hand side; the columns of a
+    message read in the wrong interleave; a peer's message read at the offset of its message to another rank.  Distance of x_k from
+    the correct distributed replica in bounds of the case, smallest over columns and counts (_DIST_MEASURED, measured on the CPU):
+
+      error                      EMI P1 deg 1  EMI P1 deg 2  EMI P2   KNP P1, 3 sp.  KNP P1, 4 sp.  KNP P2, 2 sp.
+      two_owners                 8.2e9         2.5e9         1.1e9    4.5e10         3.0e10         3.5e10
+      no_step_accumulation       0             6.0e8         2.0e9    0              0              1.3e11
+      zero_guess_unaccumulated   2.0e9         7.8e7         6.5e8    4.3e10         5.6e10         1.1e11
+      rank_missing_level1        4.2e8         1.5e8         2.1e9    8.5e10         5.3e11         7.3e10
+      message_interleave         0             0             0        7.9e10         2.0e12         1.7e11
+      peer_offset                8.2e9         2.5e9         1.2e9    1.5e11         8.2e11         1.6e11
+
+    Asserted: a tenth of each.  The zeros are by construction: a level 0 of degree 1 has no extra Chebyshev step (the P1 cases of
+    degree 2 and the P2 box, whose top level has degree 2, run it), and with one column a message has one interleave.  Every error is
+    >= 1e7 bounds away on a case the device runs, with three and with four columns for the column error."""
+    shown = 0
+    for (mesh, case), measured in zip(_DIST_CASES, _DIST_MEASURED[mutation]):
+        h, levels, ref = _part_ref(mesh, case)
+        d0 = _part_dist(h, "quad4")
+        x, y = ar.part_xk(h, levels, case, dist=d0), ar.part_xk(h, levels, case, dist=d0, mut=(mutation, 0))
+        moved = min(np.abs(y[k][s] - x[k][s]).max() / ref[k][1][s] for k in ref for s in range(len(ref[k][1])))
+        print("DIST MUTATION %s %s %s: %.3g bounds" % (mutation, mesh, ar.part_case_id(case), moved))
+        if measured == 0.0:
+            assert moved == 0.0, (mutation, mesh, case, moved)
+        else:
+            assert moved >= 0.1 * measured, (mutation, mesh, case, moved, measured)
+            shown += moved >= 1e7
+    assert shown >= 3, (mutation, shown)
+
+
+def test_sub_assembled_level0_matrices_do_not_survive_the_fp32_rounding(part_env):
+    """why Dist0Space.localize splits the GLOBAL matrix entry by entry: the ranks' matrices assembled from their own elements
+    (Dist0Space.local_matrix) add up to the global one in float64, but the device rounds every rank's values to fp32 on their own, and
+    a coupling between two shared dofs is then fl32(a_1) + fl32(a_2), not fl32(a_1 + a_2).  With them the distributed replica's x_k
+    (EMI, P1 box, quadrants) is 2680 / 651 / 700 bounds (k = 1, 2, 3) from the global replica -- asserted: a tenth; with the split
+    it is within the bound (the test above).  Tried once on the MI355X with the sub-assembled matrices: the device missed the bound of
+    the global replica by 2677 / 652 / 700 bounds (plain DG smoother) and 2.0e4 / 1970 / 2831 (Chebyshev) -- the numbers of this replica."""
+    case = ("emi", 1, False, (1, 2, 3))
+    h, levels, ref = _part_ref("box_P1", case)
+    d0 = _part_dist(h, "quad4")
+    n = levels[0].A.shape[0]
+    S = [sp.csr_matrix((np.ones(d.n), (np.arange(d.n), d.verts)), shape=(d.n, n)) for d in d0.D]
+    r32 = lambda M: sp.csr_matrix((M.data.astype(np.float32).astype(np.float64), M.indices, M.indptr), shape=M.shape)
+    A32 = r32(sp.csr_matrix(levels[0].A))
+    split = sum(s.T @ r32(d.split_matrix(levels[0].A)) @ s for s, d in zip(S, d0.D))
+    assert abs(split - A32).max() == 0.0                                # exact: every entry lives on one rank
+    sub = sum(s.T @ r32(a) @ s for s, a in zip(S, d0.emi_matrices()))
+    assert abs(sum(s.T @ a @ s for s, a in zip(S, d0.emi_matrices())) - levels[0].A).max() <= 1e-12 * abs(levels[0].A).max()
+    assert 1e-9 * abs(A32).max() <= abs(sub - A32).max() <= 1e-7 * abs(A32).max()
+    x = ar.part_xk(h, levels, case, dist=(d0, d0.emi_matrices()))
+    for k, measured in zip((1, 2, 3), (2680.0, 651.0, 700.0)):
+        moved = np.abs(x[k][0] - ref[k][0][0]).max() / ref[k][1][0]
+        print("SUB-ASSEMBLED k=%d: %.3g bounds" % (k, moved))
+        assert moved >= 0.1 * measured, (k, moved)

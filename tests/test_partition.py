@@ -165,6 +165,10 @@ def test_row_distributed_level0_algebra(degree, world, method, monkeypatch):
     # (1) sub-assembled matrices add up to the global operator; every dof has an owner
     S = sum((sp_sel(d, space.n).T @ a @ sp_sel(d, space.n)) for d, a in zip(D, Al))
     assert abs(S - A).max() <= 1e-12 * abs(A).max()
+    # (1b) the entry-wise split of the global matrix that localize uploads: every entry on exactly one rank, so the sum is exact
+    split = [d.localize(levels)[0].A for d in D]
+    assert abs(sum((sp_sel(d, space.n).T @ a @ sp_sel(d, space.n)) for d, a in zip(D, split)) - A).max() == 0.0
+    assert sum(a.nnz for a in split) == A.nnz
     assert np.array_equal(np.unique(np.concatenate([d.verts for d in D])), np.arange(space.n))
     tabs = [d.interface_tables() for d in D]
     # (2) peers list the same shared dofs in the same order
@@ -366,3 +370,80 @@ def test_row_distributed_level0_gloo(world, method, degree):
     for rank, e in res:
         assert not isinstance(e, str), e
         assert e < 1e-10, (rank, e)
+
+
+def _quadrants(mesh):
+    mid = mesh.cell_midpoints()
+    centre = 0.5 * (mesh.coords.min(axis=0) + mesh.coords.max(axis=0))
+    return (mid[:, 1] > centre[1]).astype(np.int32) + 2 * (mid[:, 2] > centre[2]).astype(np.int32)
+
+
+def test_partition_from_an_explicit_owner_array():
+    """Partition(owner=...): the four quadrants of the y-z plane about the box centre, a partition whose cuts MEET -- conforming dofs with
+    three and four owners, and ranks that share dofs but no facet (interface peers that are no halo peers), which no slab or RCB
+    partition of these long boxes produces.  The halo tables of the ranks pair up as for the built-in methods; the shared-dof tables
+    list every owner of a dof in ascending rank order; and Dist0Space.split_matrix gives every entry of the global level-0 matrix to
+    exactly one rank, so the ranks' fp32 roundings add up to the rounded global matrix."""
+    import scipy.sparse as sp
+    from common import small_3d
+    from knpemidg import amg
+    from knpemidg.partition import Partition
+    mesh, sub, surf = small_3d((8, 4, 4))
+    owner = _quadrants(mesh)
+    part = Partition(mesh, owner=owner)
+    assert part.world == 4 and np.array_equal(part.owner, owner) and part.owner.dtype == np.int32
+    assert Partition(mesh, 4, owner=owner).world == 4
+    with pytest.raises(ValueError):
+        Partition(mesh, 3, owner=owner)                                 # world contradicts the array
+    with pytest.raises(ValueError):
+        Partition(mesh, owner=np.where(owner == 3, 4, owner))           # a rank without cells
+    with pytest.raises(ValueError):
+        Partition(mesh, owner=owner[:-1])
+    # _cut as for the built-in methods: the same object from the same owner array
+    slab = Partition(mesh, 3, method="slab")
+    again = Partition(mesh, owner=slab.owner)
+    assert all(np.array_equal(a, b) for a, b in zip(slab._cut, again._cut))
+    locs = [part.local(r) for r in range(4)]
+    assert [l.nc_owned for l in locs] == [192] * 4
+    for r, l in enumerate(locs):
+        assert sorted(l.peers) == sorted({r ^ 1, r ^ 2})                # the diagonal quadrant shares an edge, no facet
+        for q, sl, ro, rc in zip(l.peers, l.send_lists, l.recv_offsets, l.recv_counts):
+            lq = locs[q]
+            i = lq.peers.index(r)
+            assert np.array_equal(l.cells_global[sl], lq.cells_global[lq.recv_offsets[i]:lq.recv_offsets[i] + lq.recv_counts[i]])
+            assert (sl < l.nc_owned).all() and ro >= l.nc_owned
+    cs = amg.ConformingSpace(mesh, surf.array(), [1])
+    mem = np.nonzero((mesh.facet_cells[:, 1] >= 0) & np.isin(surf.array(), [1]))[0]
+    for space, owners_want in ((cs, {1, 2, 4}), (None, {1, 2, 3, 4})):
+        if space is None:                                               # the P2 box of the device tests
+            mesh2, _, surf2 = small_3d((6, 3, 3))
+            space = amg.ConformingSpaceP2(amg.ConformingSpace(mesh2, surf2.array(), [1]))
+            own2 = _quadrants(mesh2)
+            mem2 = np.nonzero((mesh2.facet_cells[:, 1] >= 0) & np.isin(surf2.array(), [1]))[0]
+            D = [amg.Dist0Space(space, Partition(mesh2, owner=own2).owner, mem2, r, 4) for r in range(4)]
+        else:
+            D = [amg.Dist0Space(space, part.owner, mem, r, 4) for r in range(4)]
+        cnt = share_count(D, space.n).astype(int)
+        assert set(np.unique(cnt)) == owners_want
+        if space is cs:
+            assert [d.n for d in D] == [98] * 4
+            assert all((cnt[d.verts] == 2).sum() == 46 and (cnt[d.verts] == 4).sum() == 11 for d in D)
+        tabs = [d.interface_tables() for d in D]
+        for r, (peers, lists, uvtx, aptr, asrc) in enumerate(tabs):
+            assert peers == [q for q in range(4) if q != r]             # three interface peers, two halo peers
+            assert np.array_equal(np.diff(aptr), cnt[D[r].verts[uvtx]])  # one term per owner ...
+            for u in range(len(uvtx)):                                  # ... in ascending rank order, this rank's own value among them
+                src = asrc[aptr[u]:aptr[u + 1]]
+                off = np.concatenate([[0], np.cumsum([len(l) for l in lists])])
+                ranks = [r if k < 0 else peers[int(np.searchsorted(off, k, side="right")) - 1] for k in src]
+                assert ranks == sorted(ranks) and ranks.count(r) == 1
+                assert all(k < 0 or lists[peers.index(q)][k - off[peers.index(q)]] == uvtx[u] for k, q in zip(src, ranks))
+        # the entry-wise split of a global matrix: disjoint, complete, exact under the device's fp32 rounding
+        rng = np.random.default_rng(3)
+        A = space.stiffness(rng.uniform(0.5, 1.5, size=(len(space.dof), space.dof.shape[1])), membrane=(D[0].mem, 2.0e2))
+        r32 = lambda M: sp.csr_matrix((M.data.astype(np.float32).astype(np.float64), M.indices, M.indptr), shape=M.shape)
+        parts = [sp_sel(d, space.n).T @ r32(d.split_matrix(A)) @ sp_sel(d, space.n) for d in D]
+        A32 = r32(sp.csr_matrix(A))
+        assert abs(sum(parts) - A32).max() == 0.0
+        assert sum(p.nnz for p in parts) == A32.nnz
+        assert D[0].localize([amg.Level()], None) is None               # no coarser level: nothing to distribute
