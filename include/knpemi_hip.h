@@ -154,7 +154,8 @@ int knp_emi_rhs(knp_ctx* ctx);             /* B_EMI <- L_emi(C, C_ELIM, PHI_M, I
 int knp_knp_rhs(knp_ctx* ctx);             /* B_KNP <- L_knp(C, C_PREV, C_ELIM, PHI, PHI_M, I_CH) solver.py:731 */
 
 /* ---- solves (KSP.solve) ----------------------------------------------------------------------
- * EMI: PCG, cell-block-Jacobi (+ auxiliary-space AMG when uploaded); initial guess = PHI (ksp_initial_guess_nonzero).
+ * EMI: PCG, cell-block-Jacobi (+ auxiliary-space AMG when uploaded); initial guess: extrapolated from PHI and the solve's history
+ *      (below; the reference starts from PHI itself, ksp_initial_guess_nonzero).
  *      Without a residual target (knp_emi_residual_target(ctx, 0), the state after knp_ctx_create): PETSc's default test on the
  *      preconditioned norm, ||M^-1 r|| <= max(rtol ||M^-1 b||, atol) (solver.py:425-444); res = {||M^-1 r0||, ||M^-1 r||, ||M^-1 b||}.
  *      With a residual target r_abs > 0 (what knpemidg.Solver uses; csrc/krylov.hip: cg_converged) the solve ends when BOTH
@@ -170,8 +171,20 @@ int knp_knp_rhs(knp_ctx* ctx);             /* B_KNP <- L_knp(C, C_PREV, C_ELIM, 
  *      for in the max norm, and their max-norm error was measured at 0.03-0.055 of that ratio on uniform AND on sliver-ridden meshes
  *      (csrc/krylov.hip, profiles/r03_knp_norms_*.txt), i.e. the test asks for an estimated relative max-norm error of about rtol; the
  *      factor 20 (KNP_D8_FACTOR) applies to whatever rtol is passed (callers that mean the residual itself, e.g. a direct-solve
- *      emulation, divide it out); at least min_it iterations (ksp_min_it, solver.py:686); initial guess = C.
+ *      emulation, divide it out); at least min_it iterations (ksp_min_it, solver.py:686); initial guess: extrapolated from C and the
+ *      solve's history (below).
  *      res per system = {||r0 / vol||_8, ||r / vol||_8, ||b / vol||_8} (KNP_KNP_NORM2=1: the cell-volume-weighted 2-norms instead).
+ * Initial guess (csrc/solve.hip: extrapolate_guess).  Each solve keeps a history h1, h2 of the fields it was STARTED from and a count
+ *      nh of valid entries.  With x the content of PHI (C) when the solve is called: nh = 0: the guess is x; nh >= 1: 2 x - h1 (one
+ *      rounding); with KNP_EXTRAPOLATE_ORDER=2 (or _EMI / _KNP for one solve) and nh = 2: 3 (x - h1) + h2.  Then h2 <- h1 (order 2, or
+ *      KNP_FUSE_EXTRAP=0), h1 <- x, nh <- min(nh + 1, 2).  knp_upload of PHI sets nh = 0 for the EMI solve, knp_upload of C for the KNP
+ *      solve; nothing else does (not knp_set_params, not the other uploads; knp_state_load restores the saved count).  So the
+ *      first solve after an upload of U starts from U and makes U the history point h1: the second one starts from 2 x_1 - U, with x_1
+ *      the first solution.  KNP_EXTRAPOLATE=0 starts every solve from the field itself (2: EMI only, 3: KNP only), as does the
+ *      manufactured-solution mode (splitting = 2).  A solve with maxit = 0 leaves the guess in the field and returns -3.
+ *      The lagged cell-block inverses (rebuilt from the current coefficients every KNP_BJ_LAG = 8 solves; a KNP solve on the
+ *      drift-free class table sets their age to 0 instead, so the first solve that falls back to them rebuilds them) and the spectral bound of
+ *      the Chebyshev cell-block smoother are reset by knp_set_params and by knp_upload of C, C_ELIM, PHI or KAPPA.
  * niter: iterations (EMI: 1 int, KNP: n_sys ints).  Returns -3 if not converged within maxit (ksp_error_if_not_converged, solver.py:428).
  * knp_emi_residual_target: r_abs > 0 arms the error-controlled stop above for the following EMI solves; 0 restores PETSc's test.
  *      Every rank of a partitioned run must pass the same number (knp_allreduce_sum). */

@@ -433,15 +433,18 @@ class KnpPrecond(_TwoLevel):
         return [z + e for z, e in zip(Z, E)]
 
 
-def bicgstab(As, bs, precond, iters, dtype=np.float64):
-    """`iters` iterations of bicgstab_impl from x0 = 0 for the species' systems (their scalars are separate, the preconditioner sees all
-    of them); the first iteration in the folded form p = r.  Returns [nsys, n]."""
+def bicgstab(As, bs, precond, iters, dtype=np.float64, x0=None):
+    """`iters` iterations of bicgstab_impl from x0 (default 0) for the species' systems (their scalars are separate, the
+    preconditioner sees all of them); the first iteration in the folded form p = r.  Returns [nsys, n]."""
     wd = np.float64 if dtype == "fsum" else dtype
     A = [_FsumCsr(M) if dtype == "fsum" else sp.csr_matrix(M).astype(wd) for M in As]
     ns = len(A)
     r = [np.asarray(b).astype(wd) for b in bs]                          # x0 = 0
-    rhat = [x.copy() for x in r]
     x = [np.zeros_like(b) for b in r]
+    if x0 is not None:                                                  # k_bi_init: r = b - A x0
+        x = [np.asarray(v).astype(wd).ravel().copy() for v in x0]
+        r = [r[s] - A[s] @ x[s] for s in range(ns)]
+    rhat = [v.copy() for v in r]
     rho = [b @ b for b in r]
     p = v = None
     alpha, omega, beta = [wd(1)] * ns, [wd(1)] * ns, [wd(0)] * ns
@@ -836,10 +839,11 @@ class Host:
         self.ncg = int(self.dg2cg.max()) + 1
         self._knp = self._tab = None
 
-    def variant(self, phi=None, dt=None, D=None):
+    def variant(self, phi=None, dt=None, D=None, c=None):
         """this host with another potential [nc, nd], time step or diffusion coefficients [ions, nc]: the KNP matrices and both block
         sets follow (assembled at first use), the mesh, the state and the EMI side (`ref`) are shared.  For potentials and
-        coefficients that change on a live device."""
+        coefficients that change on a live device.  c = (solved concentrations [N_ions, nc, nd], eliminated one [nc, nd]): kappa, and
+        with it A_emi, b_emi and binv_emi of `ref`, follow (assembled here; the KNP matrices do not depend on c, their loads do)."""
         import copy
         h = copy.copy(self)
         h.pb = copy.copy(self.pb)
@@ -851,6 +855,12 @@ class Host:
         if D is not None:
             h.pb.ions = [dict(ion, D=np.array(d, dtype=np.float64)) for ion, d in zip(self.pb.ions, D)]
             h._tab = None
+        if c is not None:
+            import krylov_ref as kr
+            h.pb.c = np.array(c[0], dtype=np.float64).reshape(self.pb.c.shape)
+            h.pb.c_elim = np.array(c[1], dtype=np.float64).reshape(self.pb.c_elim.shape)
+            h.ref = kr.Ref(h.pb)
+            return h
         h.ref = copy.copy(self.ref)
         h.ref.pb = h.pb
         return h
@@ -958,17 +968,24 @@ class Host:
         return float(self.cell_peclet().max())
 
 
-def emi_xk(host, levels, cheb, k, dtype=np.float64, b=None, mut=None, dist=None):
-    """x_k of the device's EMI PCG from x_0 = 0 with the two-level preconditioner over `levels`; cheb: the Chebyshev DG smoother;
-    dist: a `Dist0` -- level 0 of the V-cycle in the row-distributed form of that partition (or the pair `store` takes)"""
+def emi_xk(host, levels, cheb, k, dtype=np.float64, b=None, mut=None, dist=None, x0=None, binv=None, lmax=None):
+    """x_k of the device's EMI PCG from x_0 (default 0) with the two-level preconditioner over `levels`; cheb: the Chebyshev DG smoother;
+    dist: a `Dist0` -- level 0 of the V-cycle in the row-distributed form of that partition (or the pair `store` takes).
+    binv: other cell blocks than those of the host's matrix (lagged ones); lmax: the spectral bound itself, where the device keeps one
+    (default: estimated on these matrices and blocks from b).  levels = None: the cell blocks alone (a context without a hierarchy)."""
     import types
     import krylov_ref as kr
     ref = host.ref
     b = ref.b_emi if b is None else np.asarray(b, dtype=np.float64).ravel()
-    lmax = bj_lambda_max([ref.A_emi], [ref.binv_emi], [b]) if cheb else 0.0
+    binv = ref.binv_emi if binv is None else np.asarray(binv, dtype=np.float64)
+    sysm = types.SimpleNamespace(A_emi=ref.A_emi, b_emi=b, binv_emi=binv)
+    if levels is None:
+        return kr.pcg(sysm, 0.0, 0.0, x0=x0, iters=k, dtype=dtype)[0]
+    if lmax is None:
+        lmax = bj_lambda_max([ref.A_emi], [binv], [b]) if cheb else 0.0
     H = store(levels, dtype, mut, dist=dist)
-    M = EmiPrecond(ref.A_emi, ref.binv_emi, host.dg2cg, H, lmax, dtype, mut)
-    return kr.pcg(types.SimpleNamespace(A_emi=ref.A_emi, b_emi=b, binv_emi=ref.binv_emi), 0.0, 0.0, precond=M, iters=k, dtype=dtype)[0]
+    M = EmiPrecond(ref.A_emi, binv, host.dg2cg, H, lmax, dtype, mut)
+    return kr.pcg(sysm, 0.0, 0.0, x0=x0, precond=M, iters=k, dtype=dtype)[0]
 
 
 def knp_lmax(host, blocks, bs):
@@ -991,8 +1008,8 @@ def _knp_system(host, levels, dtype, bs, lmax_bs, mut, blocks, lmax, dist=None):
 
 
 def knp_xk(host, levels, k, dtype=np.float64, bs=None, lmax_bs=None, mut=None, blocks="cell", lmax=None, method="bicgstab",
-           reverse=False, dist=None):
-    """x_k [nsys, ndof] of the device's KNP solve from x_0 = 0.  levels: one hierarchy shared by the species (its columns), or a
+           reverse=False, dist=None, x0=None):
+    """x_k [nsys, ndof] of the device's KNP solve from x_0 = 0 (x0 [nsys, ndof]: from there).  levels: one hierarchy shared by the species (its columns), or a
     list with one hierarchy per species.  lmax_bs: the right-hand sides the spectral bound was estimated from (default: bs).
     blocks: the cell blocks of the preconditioner and of the spectral bound -- "cell" (per-cell inverses with the drift), "table" (the
     drift-free class table of solve.hip) or an explicit list (lagged inverses of another potential: `Host.variant(...).blocks`).
@@ -1002,9 +1019,9 @@ def knp_xk(host, levels, k, dtype=np.float64, bs=None, lmax_bs=None, mut=None, b
     dist: a `Dist0` -- level 0 of the V-cycle in the row-distributed form of that partition."""
     As, bs, M = _knp_system(host, levels, dtype, bs, lmax_bs, mut, blocks, lmax, dist)
     if method == "bicgstab":
-        return bicgstab(As, bs, M, k, dtype)
+        return bicgstab(As, bs, M, k, dtype, x0=x0)
     assert method[0] == "gmres"
-    return gmres(As, bs, M, k, method[1], dtype, mut=mut if isinstance(mut, str) else None, reverse=reverse)
+    return gmres(As, bs, M, k, method[1], dtype, mut=mut if isinstance(mut, str) else None, x0=x0, reverse=reverse)
 
 
 def knp_gmres_free(host, levels, rtol, m, dtype=np.float64, bs=None, blocks="table", min_it=0, reverse=False):
