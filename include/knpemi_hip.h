@@ -359,13 +359,28 @@ int knp_rec_add_map_part(knp_ctx* ctx, int64_t n_global, int64_t n, const int32_
  *                    context as it was.  Runs the locate pass (one thread per cell, integer atomicMin per point: deterministic) and the
  *                    weights pass, and waits for them.  Returns the handle >= 0, or a negative status; -7 with a communicator active
  *                    (several ranks), without entering a collective.
+ *  knp_grid_create_derived : knp_grid_create plus n_derived quantities evaluated in the owner cell, with that cell's D (DG gradients are
+ *                    one-sided: on a facet, an edge, a vertex or the membrane the owner decides the side, as it decides the value;
+ *                    tags therefore give ECS-only or ICS-only fluxes).  kind[q]: KNP_GD_EFIELD  -grad phi;  KNP_GD_FLUX_DIFFUSIVE
+ *                    -D_k grad c_k;  KNP_GD_FLUX  J_k = -D_k grad c_k - z_k D_k psi c_k(p) grad phi, psi = F / (R T);  KNP_GD_CURRENT
+ *                    F sum_k z_k J_k over every ion.  ion[q] = 0 .. n_ions - 1 (n_ions - 1: the eliminated ion, C_ELIM); ignored for
+ *                    EFIELD and CURRENT.  Units are those of knp_set_params.  A frame is [n_fields nodal planes][per derived quantity:
+ *                    d component planes, x first][npts]; NaN in every component without an owner.  n_fields may be 0 here.  Also
+ *                    refused before anything is allocated: an unknown kind, an ion outside 0 .. n_ions - 1, nothing selected, more
+ *                    than 2 n_ions + 2 derived quantities, a context whose parameters were never set (knp_set_params).
+ *                    knp_grid_create is this call with n_derived = 0.  A grid with derived quantities runs the nodal kernel for its
+ *                    nodal planes and then one more kernel; knp_grid_timing's sample_ms spans both.
  *  knp_grid_points : owner[npts] (caller's cell ids) and tag[npts] of the points; either may be null
  *  knp_grid_sample : one frame of the fields as they are now: kernel, asynchronous copy into one of two pinned host buffers and an
  *                    event, all on the context's stream; -5 while two frames wait to be fetched
- *  knp_grid_fetch  : waits for the event of the oldest waiting frame only and copies it to out[bytes], bytes = n_fields x npts x 8 (4)
+ *  knp_grid_fetch  : waits for the event of the oldest waiting frame only and copies it to out[bytes], bytes = (n_fields + d n_derived) x npts x 8 (4)
  *  knp_grid_timing : device milliseconds of the locate and weights passes, and of the kernel and the copy of the last fetched frame */
 int knp_grid_create(knp_ctx* ctx, const double* lo, const double* h, const int64_t* shape, double tol, int n_tags, const uint32_t* tags,
                     int n_fields, const int32_t* fields, int f32);
+typedef enum { KNP_GD_EFIELD = 0, KNP_GD_FLUX = 1, KNP_GD_FLUX_DIFFUSIVE = 2, KNP_GD_CURRENT = 3 } knp_grid_derived;
+int knp_grid_create_derived(knp_ctx* ctx, const double* lo, const double* h, const int64_t* shape, double tol, int n_tags,
+                            const uint32_t* tags, int n_fields, const int32_t* fields, int n_derived, const int32_t* kind,
+                            const int32_t* ion, int f32);
 int knp_grid_points(knp_ctx* ctx, int grid, int32_t* owner, int32_t* tag);
 int knp_grid_sample(knp_ctx* ctx, int grid);
 int knp_grid_fetch(knp_ctx* ctx, int grid, void* out, size_t bytes);

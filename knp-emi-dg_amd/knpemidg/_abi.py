@@ -17,6 +17,8 @@ F_PHI, F_C, F_C_PREV, F_C_ELIM, F_PHI_M, F_I_CH, F_E, F_KAPPA, F_DNPHI, F_B_EMI,
     F_FACET_TMP = range(14)
 
 FACET_TMP_SLOTS = 4        # KNP_FACET_TMP_SLOTS (include/knpemi_hip.h)
+# enum knp_grid_derived (include/knpemi_hip.h)
+GD_EFIELD, GD_FLUX, GD_FLUX_DIFFUSIVE, GD_CURRENT = range(4)
 # knp_debug_table_id (include/knpemi_hip.h)
 DT_CELLS, DT_NBR, DT_FLAG, DT_CFACET, DT_MF, DT_HB_SRC, DT_HB_LOC, DT_META = range(8)
 
@@ -134,6 +136,8 @@ SIGNATURES = {
     "knp_rec_map_arm": (C.c_int, [_ctxp, C.c_double]),
     "knp_rec_map_read": (C.c_int, [_ctxp, C.c_int64, _f64p, _f64p, _f64p, _f64p, _i32p]),
     "knp_grid_create": (C.c_int, [_ctxp, _f64p, _f64p, _i64p, C.c_double, C.c_int, _u32p, C.c_int, _i32p, C.c_int]),
+    "knp_grid_create_derived": (C.c_int, [_ctxp, _f64p, _f64p, _i64p, C.c_double, C.c_int, _u32p, C.c_int, _i32p, C.c_int, _i32p, _i32p,
+                                          C.c_int]),
     "knp_grid_points": (C.c_int, [_ctxp, C.c_int, _i32p, _i32p]),
     "knp_grid_sample": (C.c_int, [_ctxp, C.c_int]),
     "knp_grid_fetch": (C.c_int, [_ctxp, C.c_int, C.c_void_p, C.c_size_t]),
@@ -998,9 +1002,11 @@ class Device:
         self._chk(self.lib.knp_rec_destroy(self.ctx), "knp_rec_destroy")
 
     # -- fields on a regular voxel grid (csrc/grid.hip; knpemidg/grid.py holds the host side) ------------------------------
-    def grid_create(self, lo, h, shape, fields, tol=1.0e-12, tags=None, f32=False):
+    def grid_create(self, lo, h, shape, fields, tol=1.0e-12, tags=None, f32=False, derived=None):
         """Locate the points of the grid lo + i h, i < shape (axis order x, y[, z]) and keep their cells and barycentric coordinates
-        on the device; fields = field ids (0 phi, 1 + k solved concentration k, n_ions the eliminated ion).  Returns the handle."""
+        on the device; fields = field ids (0 phi, 1 + k solved concentration k, n_ions the eliminated ion).  derived: (kind, ion)
+        pairs, kind out of GD_EFIELD / GD_FLUX / GD_FLUX_DIFFUSIVE / GD_CURRENT (knp_grid_create_derived; `fields` may be empty then):
+        d component planes each behind the nodal planes of a frame.  Returns the handle."""
         lo = np.ascontiguousarray(lo, dtype=np.float64)
         h = np.ascontiguousarray(h, dtype=np.float64)
         shape = np.ascontiguousarray(shape, dtype=np.int64)
@@ -1008,8 +1014,14 @@ class Device:
             raise KnpError("grid_create: lo, h and shape must hold one entry per mesh dimension")
         tg = np.ascontiguousarray([] if tags is None else list(tags), dtype=np.uint32)
         fl = np.ascontiguousarray(fields, dtype=np.int32)
-        rc = self.lib.knp_grid_create(self.ctx, _p(lo, _f64p), _p(h, _f64p), _p(shape, _i64p), float(tol), len(tg), _p(tg, _u32p), len(fl),
-                                      _p(fl, _i32p), int(bool(f32)))
+        if derived is None:
+            rc = self.lib.knp_grid_create(self.ctx, _p(lo, _f64p), _p(h, _f64p), _p(shape, _i64p), float(tol), len(tg), _p(tg, _u32p), len(fl),
+                                          _p(fl, _i32p), int(bool(f32)))
+        else:
+            kind = np.ascontiguousarray([k for k, _ in derived], dtype=np.int32)
+            ion = np.ascontiguousarray([i for _, i in derived], dtype=np.int32)
+            rc = self.lib.knp_grid_create_derived(self.ctx, _p(lo, _f64p), _p(h, _f64p), _p(shape, _i64p), float(tol), len(tg), _p(tg, _u32p),
+                                                  len(fl), _p(fl, _i32p), len(kind), _p(kind, _i32p), _p(ion, _i32p), int(bool(f32)))
         if rc < 0:
             self._chk(rc, "knp_grid_create")
         return int(rc)

@@ -11,6 +11,11 @@ written to do the same).  It is what runs without a device and what the tests co
 follows `recorder.locate_points`: among the cells whose smallest barycentric coordinate is >= -tol the lowest index in the caller's
 numbering; a point no cell contains has owner -1 and NaN in every field.
 
+Beside the nodal fields a grid carries what a KNP-EMI run is made for: the electric field -grad phi, the ion fluxes
+J_k = -D_k grad c_k - z_k D_k psi c_k grad phi, their diffusive share and the current density F sum_k z_k J_k, evaluated in the
+owner cell with that cell's D (k_grid_sample_derived; `GridSpec.sample_derived` is its host statement and also returns the sum of
+the moduli of the terms of every value, the scale of a rounding bound).
+
 `GridSampler` is what `Solver.record_grid` returns: the device handle, `sample()`, the owner and tag volumes, and the frame file
 `<filename><name>.h5` (+ `<name>.xdmf`) the time loops write.
 """
@@ -18,7 +23,7 @@ import os
 
 import numpy as np
 
-from knpemidg._abi import KnpError
+from knpemidg._abi import GD_CURRENT, GD_EFIELD, GD_FLUX, GD_FLUX_DIFFUSIVE, KnpError
 from knpemidg.recorder import basis_weights
 
 DEFAULT_TOL = 1.0e-12
@@ -26,19 +31,41 @@ MAX_TAGS = 8               # KNP_GRID_MAX_TAGS (csrc/grid.hip)
 _NONE = np.iinfo(np.int64).max
 
 
+_DERIVED_PREFIXES = (("diffusive_flux_", GD_FLUX_DIFFUSIVE), ("flux_", GD_FLUX))
+
+
 def resolve_fields(fields, ion_names):
-    """Field ids of the C ABI for names out of "phi" and the ion names (ion_list order, the eliminated ion last): 0 = phi,
-    1 + k = ion k.  ValueError for an unknown or repeated name."""
+    """What the C ABI samples for names out of "phi" and the ion names (ion_list order, the eliminated ion last) and out of the
+    derived vector quantities "efield", "flux_<ion>", "diffusive_flux_<ion>" and "current", one entry per name in the order given:
+    a nodal field is its field id (0 = phi, 1 + k = ion k), a derived quantity the pair (kind, ion) of knp_grid_create_derived
+    (ion -1 for efield and current).  ValueError for an unknown or repeated name."""
     if isinstance(fields, str):
         fields = (fields,)
-    names = ["phi"] + [str(n) for n in ion_names]
+    ions = [str(n) for n in ion_names]
+    for reserved in ("efield", "current"):
+        if reserved in ions:
+            raise ValueError("record_grid: an ion named %r cannot be told from the derived quantity of that name" % reserved)
+    names = ["phi"] + ions
+    known = names + ["efield", "current", "flux_<ion>", "diffusive_flux_<ion>"]
     out = []
     for f in fields:
-        if f not in names:
-            raise ValueError("record_grid: unknown field %r (known: %s)" % (f, ", ".join(names)))
-        if names.index(f) in out:
+        if f in names:
+            entry = names.index(f)
+        elif f == "efield":
+            entry = (GD_EFIELD, -1)
+        elif f == "current":
+            entry = (GD_CURRENT, -1)
+        else:
+            entry = None
+            for prefix, kind in _DERIVED_PREFIXES:
+                if isinstance(f, str) and f.startswith(prefix) and f[len(prefix):] in ions:
+                    entry = (kind, ions.index(f[len(prefix):]))
+                    break
+            if entry is None:
+                raise ValueError("record_grid: unknown field %r (known: %s)" % (f, ", ".join(known)))
+        if entry in out:
             raise ValueError("record_grid: field %r is listed twice" % (f,))
-        out.append(names.index(f))
+        out.append(entry)
     if not out:
         raise ValueError("record_grid: no field to sample")
     return out
@@ -83,6 +110,20 @@ def _bary(x0, c, det, p):
         total = total + lam[:, j]
     lam[:, 0] = 1.0 - total
     return lam
+
+
+def basis_gradients(bary, glam, degree):
+    """grad w_a [n, nd, d] of the nodal basis (the local dof order of basis_weights) from lambda [n, d+1] and grad lambda
+    [n, d+1, d].  P1: grad lambda_a; P2: vertices (4 lambda_a - 1) grad lambda_a, edges (a, b), a < b,
+    4 (lambda_b grad lambda_a + lambda_a grad lambda_b)."""
+    if degree == 1:
+        return glam.copy()
+    if degree != 2:
+        raise ValueError("degree must be 1 or 2")
+    nv = bary.shape[1]
+    cols = [(4.0 * bary[:, a] - 1.0)[:, None] * glam[:, a] for a in range(nv)]
+    cols += [4.0 * (bary[:, b, None] * glam[:, a] + bary[:, a, None] * glam[:, b]) for a in range(nv) for b in range(a + 1, nv)]
+    return np.stack(cols, axis=1)
 
 
 class GridSpec:
@@ -214,9 +255,73 @@ class GridSpec:
         out[found] = (w[found] * u[owner[found]]).sum(axis=1)
         return out
 
+    def sample_derived(self, mesh, quantities, phi, conc, z, D, psi, F, degree, owner=None, bary=None):
+        """The host statement of k_grid_sample_derived.  quantities: (kind, ion) pairs as resolve_fields gives them; phi [nc, nd] and
+        conc [n_ions][nc, nd] the nodal fields (caller's cell order, the eliminated ion last); z [n_ions], D [n_ions][nc], psi = F / (R T).
+        With grad u = sum_a u_a grad w_a and u(p) = sum_a u_a w_a in the owner cell, grad lambda_j = c_j / det from _cell_geometry:
+          efield -grad phi;  diffusive flux -D_k grad c_k;  flux J_k = -D_k grad c_k - z_k D_k psi c_k(p) grad phi;
+          current F sum_k z_k J_k over every ion.
+        Returns (values, scale), each [len(quantities), npts, d]: values are NaN where owner is -1; scale is, per point and component,
+        the sum of the absolute values of the terms the value is made of (every u_a grad w_a and u_a w_a entering with its
+        modulus; 0 where owner is -1) -- what a rounding bound for the value has to be proportional to."""
+        owner = self.owner if owner is None else owner
+        bary = self.bary if bary is None else bary
+        if owner is None:
+            raise ValueError("grid: locate the points first")
+        d = self.dim
+        z, D = np.asarray(z, dtype=np.float64), np.asarray(D, dtype=np.float64)
+        n_ions = len(z)
+        found = np.nonzero(owner >= 0)[0]
+        cells = owner[found]
+        _, c, det, _, _ = _cell_geometry(np.asarray(mesh.coords, dtype=np.float64)[np.asarray(mesh.cells)[cells]])
+        glam = np.empty((len(found), d + 1, d))
+        glam[:, 1:] = c / det[:, None, None]
+        glam[:, 0] = -glam[:, 1:].sum(axis=1)
+        w = basis_weights(bary[found], degree)
+        dw = basis_gradients(bary[found], glam, degree)
+        aw, adw = np.abs(w), np.abs(dw)
+
+        def value_grad(u):
+            u = np.asarray(u, dtype=np.float64).reshape(-1, w.shape[1])[cells]
+            return ((w * u).sum(axis=1), np.einsum("na,nak->nk", u, dw),
+                    (aw * np.abs(u)).sum(axis=1), np.einsum("na,nak->nk", np.abs(u), adw))
+
+        _, gphi, _, aphi = value_grad(phi)
+        ion_cache = {}
+
+        def ion_terms(k):
+            """(diffusive flux, flux, their scales) of ion k"""
+            if k not in ion_cache:
+                ck, gck, ack, agck = value_grad(conc[k])
+                Dk = D[k][cells][:, None]
+                diff, sdiff = -Dk * gck, Dk * agck
+                drift = z[k] * Dk * psi * ck[:, None]
+                ion_cache[k] = (diff, diff - drift * gphi, sdiff, sdiff + np.abs(z[k]) * Dk * psi * ack[:, None] * aphi)
+            return ion_cache[k]
+
+        values = np.full((len(quantities), self.npts, d), np.nan)
+        scale = np.zeros((len(quantities), self.npts, d))
+        for q, (kind, ion) in enumerate(quantities):
+            if kind == GD_EFIELD:
+                v, s = -gphi, aphi
+            elif kind == GD_FLUX_DIFFUSIVE:
+                v, _, s, _ = ion_terms(ion)
+            elif kind == GD_FLUX:
+                _, v, _, s = ion_terms(ion)
+            elif kind == GD_CURRENT:
+                v, s = np.zeros_like(gphi), np.zeros_like(gphi)
+                for k in range(n_ions):
+                    _, fk, _, sk = ion_terms(k)
+                    v = v + F * z[k] * fk
+                    s = s + F * np.abs(z[k]) * sk
+            else:
+                raise ValueError("grid: unknown derived quantity %r" % (kind,))
+            values[q, found], scale[q, found] = v, s
+        return values, scale
+
 
 # ---------------------------------------------------------------------------------------------------- files
-def _xdmf_text(h5_name, spec, fields, times, precision):
+def _xdmf_text(h5_name, spec, fields, times, precision, vectors=()):
     d = spec.dim
     dims = " ".join(str(n) for n in spec.array_shape)
     topo, geo = ("3DCoRectMesh", "ORIGIN_DXDYDZ") if d == 3 else ("2DCoRectMesh", "ORIGIN_DXDY")
@@ -234,9 +339,11 @@ def _xdmf_text(h5_name, spec, fields, times, precision):
                 '     <DataItem Format="XML" Dimensions="%d">%s</DataItem>' % (d, vec(spacing)),
                 '    </Geometry>']
         for f in fields:
-            out += ['    <Attribute Name="%s" AttributeType="Scalar" Center="Node">' % f,
+            # a Vector attribute has three components, also on a 2D grid (GridFile.add writes a zero third one)
+            kind, fdims = ("Vector", dims + " 3") if f in vectors else ("Scalar", dims)
+            out += ['    <Attribute Name="%s" AttributeType="%s" Center="Node">' % (f, kind),
                     '     <DataItem Format="HDF" NumberType="Float" Precision="%d" Dimensions="%s">%s:/%s/vector_%d</DataItem>'
-                    % (precision, dims, h5_name, f, n),
+                    % (precision, fdims, h5_name, f, n),
                     '    </Attribute>']
         out.append('   </Grid>')
     out += ['  </Grid>', ' </Domain>', '</Xdmf>', '']
@@ -244,7 +351,8 @@ def _xdmf_text(h5_name, spec, fields, times, precision):
 
 
 class GridFile:
-    """`path` (.h5) with /grid/{lo,hi,shape,spacing}, /grid/cell, /grid/tag, /t, /step and /<field>/vector_<n>, streamed through
+    """`path` (.h5) with /grid/{lo,hi,shape,spacing}, /grid/cell, /grid/tag, /t, /step and /<field>/vector_<n> ([nz, ny, nx]; a vector
+    quantity, handed to add() as [..., d], is written as [nz, ny, nx, 3] and declared AttributeType="Vector"), streamed through
     h5lite.H5Writer under a temporary name and renamed by close(), which also writes the XDMF sidecar next to it: a
     3DCoRectMesh / 2DCoRectMesh temporal collection (Dimensions, Origin and DxDyDz in z-y-x order) whose DataItems point into the .h5."""
 
@@ -256,6 +364,7 @@ class GridFile:
         self.tmp = os.path.join(folder, ".%s.tmp%d" % (os.path.basename(self.path), os.getpid()))
         self.spec, self.fields = spec, list(fields)
         self.t, self.step = [], []
+        self.vectors = set()            # the fields whose frames came as [..., d]: Vector attributes of the sidecar
         self.precision = 8
         w = self.w = H5Writer(self.tmp)
         w.write("/grid/lo", spec.lo)
@@ -269,10 +378,18 @@ class GridFile:
 
     def add(self, t, step, frame):
         n = len(self.t)
+        shape = self.spec.array_shape
         for f in self.fields:
             a = np.asarray(frame[f])
             self.precision = a.dtype.itemsize
-            self.w.write("/%s/vector_%d" % (f, n), a.reshape(self.spec.array_shape))
+            if a.ndim == len(shape) + 1:
+                # a vector quantity [..., d] (a view into the component planes of the frame): interleaved here, in the one copy the
+                # writer makes anyway, as [..., 3] with a zero third component in 2D
+                self.vectors.add(f)
+                v = np.zeros(shape + (3,), dtype=a.dtype)
+                v[..., :a.shape[-1]] = a
+                a = v
+            self.w.write("/%s/vector_%d" % (f, n), a.reshape(shape + a.shape[len(shape):]))
         self.t.append(float(t))
         self.step.append(int(step))
 
@@ -293,18 +410,23 @@ class GridFile:
                 os.remove(self.tmp)
         xdmf = os.path.splitext(self.path)[0] + ".xdmf"
         with open(xdmf + ".tmp%d" % os.getpid(), "w") as fh:
-            fh.write(_xdmf_text(os.path.basename(self.path), self.spec, self.fields, self.t, self.precision))
+            fh.write(_xdmf_text(os.path.basename(self.path), self.spec, self.fields, self.t, self.precision, self.vectors))
         os.replace(xdmf + ".tmp%d" % os.getpid(), xdmf)
         return self.path
 
 
 # ---------------------------------------------------------------------------------------------------- device
 class GridSampler:
-    """One grid on the device (`Solver.record_grid`).  sample() returns {field: array shaped shape[::-1]}; `cells` and `tags` are
+    """One grid on the device (`Solver.record_grid`).  sample() returns {field: array shaped shape[::-1]}, a vector quantity (efield,
+    flux_<ion>, diffusive_flux_<ion>, current) shaped shape[::-1] + (d,); field_ids as resolve_fields gives them; `cells` and `tags` are
     the owner (caller's cell ids) and subdomain volumes, -1 where the grid sticks out of the mesh."""
 
     def __init__(self, spec, fields, field_ids, every=1, dtype=np.float64, name="grid"):
         self.spec, self.fields, self.field_ids = spec, list(fields), list(field_ids)
+        # the layout of a frame: the nodal planes in the order given, then d component planes per derived quantity in the order given
+        self.nodal = [(f, e) for f, e in zip(self.fields, self.field_ids) if not isinstance(e, tuple)]
+        self.derived = [(f, e) for f, e in zip(self.fields, self.field_ids) if isinstance(e, tuple)]
+        self.n_planes = len(self.nodal) + spec.dim * len(self.derived)
         self.every = int(every)
         if self.every < 1:
             raise ValueError("record_grid: every must be a positive number of steps")
@@ -322,7 +444,8 @@ class GridSampler:
 
     def attach(self, dev):
         s = self.spec
-        self.handle = dev.grid_create(s.lo, s.h, s.shape, self.field_ids, tol=s.tol, tags=s.tags, f32=self.dtype == np.float32)
+        self.handle = dev.grid_create(s.lo, s.h, s.shape, [e for _, e in self.nodal], tol=s.tol, tags=s.tags, f32=self.dtype == np.float32,
+                                      derived=[e for _, e in self.derived] or None)
         self.dev = dev
         self._points = None
 
@@ -346,8 +469,13 @@ class GridSampler:
         return self._volumes()[1]
 
     def _fetch(self, out=None):
-        a = self.dev.grid_fetch(self.handle, len(self.fields), self.spec.npts, self.dtype, out=out)
-        return {f: a[q].reshape(self.spec.array_shape) for q, f in enumerate(self.fields)}
+        a = self.dev.grid_fetch(self.handle, self.n_planes, self.spec.npts, self.dtype, out=out)
+        shape, d, nn = self.spec.array_shape, self.spec.dim, len(self.nodal)
+        frame = {f: a[q].reshape(shape) for q, (f, _) in enumerate(self.nodal)}
+        for q, (f, _) in enumerate(self.derived):
+            # [..., d], x component first: a view of the quantity's component planes
+            frame[f] = np.moveaxis(a[nn + q * d:nn + (q + 1) * d].reshape((d,) + shape), 0, -1)
+        return frame
 
     def sample(self):
         """The fields as they are now (waits for this frame).  Not between the frames of a running time loop's file."""
@@ -379,7 +507,7 @@ class GridSampler:
     def _write_one(self):
         t, step = self._waiting.pop(0)
         if self._scratch is None:       # the file takes the values at once: one buffer serves every frame of the loop
-            self._scratch = np.empty((len(self.fields), self.spec.npts), dtype=self.dtype)
+            self._scratch = np.empty((self.n_planes, self.spec.npts), dtype=self.dtype)
         self._file.add(t, step, self._fetch(self._scratch))
 
     def after_step(self, steps_done, t):

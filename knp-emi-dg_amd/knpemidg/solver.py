@@ -334,7 +334,12 @@ class Solver:
         shape 1 sits at lo: a slice of a 3D mesh) on the device (csrc/grid.hip) -- the images and coarse volumes the reference's figure
         scripts rebuild from results.h5 with FEniCS (examples/*/make_figures*.py).  Callable once setup_domain has run; the points are
         located as soon as the device context exists.  Returns the `knpemidg.grid.GridSampler`; up to 8 grids per solver.
-          fields   out of "phi" and the ion names (the eliminated ion included)
+          fields   out of "phi" and the ion names (the eliminated ion included), and out of the vector quantities "efield"
+                   (-grad phi), "diffusive_flux_<ion>" (-D_k grad c_k), "flux_<ion>" (J_k = -D_k grad c_k - z_k D_k psi c_k grad phi,
+                   solver.py:31-34) and "current" (F sum_k z_k J_k over every ion), in the units of the parameters; each is
+                   evaluated in the cell that owns the point, with that cell's D: DG gradients are one-sided, on a facet or the
+                   membrane the owner decides the side (`tags` gives ECS-only or ICS-only fluxes).  sample() returns them as
+                   [nz, ny, nx, d]; the file holds [nz, ny, nx, 3] and the sidecar declares them as Vector attributes
           every    the time loops write frame 0 for the state they start from, then one frame every `every` steps, to
                    `<filename><name>.h5` (+ `<name>.xdmf` for ParaView), next to timeseries.h5; a resumed run writes
                    `<name>_from<k>.h5` with /step_offset, as the field output does
