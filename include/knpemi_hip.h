@@ -88,6 +88,33 @@ int knp_set_mms(knp_ctx* ctx, const double* C, const double* extra_emi, const do
  * fsrc[n_sys][nc] of knp_set_params. */
 int knp_set_source(knp_ctx* ctx, const double* src);
 
+/* Ion sources evaluated on the device (knpemidg.Expression): a scalar C++ expression of x and named parameters, wrapped by
+ * knpemidg/expression.py into a translation unit around csrc/source_rtc.hpp and compiled with knp_ode_rtc_compile.  Its kernel
+ * writes, for every ECS cell of the context (tag 0, owned and ghost -- the `dx(0)` of solver.py:599) and local basis function a,
+ * vol * sum_q w_q f(x_q) B[q][a] into the species' row of the buffer of knp_set_source: one lane per cell, fixed summation order,
+ * no atomics (same bits on every run), overwriting (a repeated evaluation changes nothing).
+ *  knp_source_set_rule: the rule the kernels integrate with, once per context before the first registration: bary[nq][dim+1],
+ *                       w[nq] (sums to 1), B[nq][nd] basis values at the points; 1 <= nq <= 4096.  The caller tabulates them, so
+ *                       host and device use the same numbers
+ *  knp_source_register: loads the code object on the context's device as the source of `species` (replacing an earlier one; the
+ *                       modules are unloaded with the context).  The first call builds the list of ECS cells; the buffer is
+ *                       allocated zero-filled if absent.  -1 in manufactured-solution mode (splitting == 2), for a species outside
+ *                       [0, n_sys), for n_params outside 0..32 and without a rule
+ *  knp_source_eval    : enqueues the species' kernel on the context's stream with params[n_params] BY VALUE in the kernel
+ *                       arguments: no copy to the device, no synchronisation (knp_host_round_trips does not move).  An empty cell
+ *                       list launches nothing.  With knp_set_source in the same step, call that first: rows of device sources are
+ *                       then overwritten, rows of host-integrated sources survive
+ *  knp_source_clear   : drops the species' kernel and zeroes its row
+ *  knp_source_cells   : length of the ECS cell list (-1 before the first registration)
+ *  knp_source_download: the whole buffer, out[n_sys][nc*nd] in device cell order, for tests (waits for the stream); 1 and `out`
+ *                       untouched when the context has no buffer */
+int knp_source_set_rule(knp_ctx* ctx, int nq, const double* bary, const double* w, const double* B);
+int knp_source_register(knp_ctx* ctx, int species, const void* code, size_t size, const char* kernel_name, int n_params);
+int knp_source_eval(knp_ctx* ctx, int species, const double* params, int n_params);
+int knp_source_clear(knp_ctx* ctx, int species);
+int64_t knp_source_cells(knp_ctx* ctx);
+int knp_source_download(knp_ctx* ctx, double* out);
+
 /* DG-p path (degree 2): reference-basis tabulation of one integral class.  The operator applies are matrix-free and need
  * no tabulation (csrc/apply_p2.hip); the right-hand sides, facet averages and Nernst projections of step III (the device
  * analogue of assemble(L_emi / L_knp), solver.py:477-479, 730-731, and of pcws_constant_project, utils.py:100-124) are

@@ -180,6 +180,7 @@ void knp_ctx_destroy(knp_ctx* c) {
     for (auto ev : c->aux_events) hipEventDestroy(ev);
     if (c->fork_event) hipEventDestroy(c->fork_event);
     ode_destroy_all(c);
+    source_destroy(c);
     rec_destroy(c);
     grid_destroy_all(c);
     state_destroy(c);
@@ -306,11 +307,16 @@ int knp_set_geometry_classes(knp_ctx* c, int ncls, const uint16_t* cls, const do
 
 // Host-integrated load vector of the ion sources, int f_k v dx(0) (solver.py:599), for sources that are not constants: added to
 // L_knp by the right-hand-side kernels.  src[n_sys][nc*nd] in device cell order, or null to clear.  (The manufactured-solution
-// mode owns the same buffer: knp_set_mms.)
+// mode owns the same buffer: knp_set_mms.)  Species with a device-evaluated source (knp_source_register, source.hip) write their rows
+// of the same buffer after this call, on the same stream: while one is registered, null zeroes the buffer instead of freeing it.
 int knp_set_source(knp_ctx* c, const double* src) {
     if (!c) return -1;
     if (c->p.splitting == 2) { c->err = "knp_set_source: the manufactured-solution mode sets its own data terms"; return -1; }
     const int64_t n = (int64_t)c->p.n_sys * c->m.nc * c->nd;
+    if (!src && c->extra_knp && source_registered(c)) {
+        HIPCHK(c, hipMemsetAsync(c->extra_knp, 0, sizeof(double) * n, c->stream));
+        return 0;
+    }
     if (!src) {
         hipFree(c->extra_knp);
         c->extra_knp = nullptr;

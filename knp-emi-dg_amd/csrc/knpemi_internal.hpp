@@ -120,6 +120,8 @@ struct Fields {
     }
 };
 
+struct SourceState;                // source.hip: the context's device-evaluated ion sources
+
 struct knp_ctx {
     int device = 0;
     int degree = 1;
@@ -150,6 +152,7 @@ struct knp_ctx {
     double* mms_C = nullptr;       // [n_sys][nc]
     double* extra_emi = nullptr;   // [nc*nd]
     double* extra_knp = nullptr;   // [n_sys][nc*nd]
+    SourceState* src = nullptr;    // device-evaluated ion sources writing rows of extra_knp (source.hip; created by the first call that needs it)
     // DG-p (p >= 2) path: tabulated rules + assembled cell blocks [nc][dim+2][nd][nd] (tab_dg.hip)
     TabRule tab[KNP_TAB_COUNT];
     double* tab_mem[KNP_TAB_COUNT] = {nullptr};
@@ -363,6 +366,8 @@ template <typename T> inline void state_push_host(StateBlk& b, const T* v, int64
 void ode_destroy_all(knp_ctx* c);   // ode.hip: frees the context's membrane models and runtime-compiled kernels
 void rec_destroy(knp_ctx* c);       // record.hip: frees the context's time-series recorder, if any
 void grid_destroy_all(knp_ctx* c);  // grid.hip: frees the context's voxel-grid samplers, if any
+void source_destroy(knp_ctx* c);    // source.hip: unloads the context's device-evaluated ion sources, frees their cell list and rule
+bool source_registered(knp_ctx* c); // source.hip: some species has a device-evaluated source (knp_source_register)
 int ode_check_failed(knp_ctx* c);   // ode.hip: reads and clears the ODE failure flag (stream idle); sets c->err
 int status_look(knp_ctx* c);        // krylov.hip: head of the status block -> c->pinned, one copy and one stream wait
 int sync_check_ode(knp_ctx* c);     // ode.hip: waits for the stream and checks the ODE failure flag (0, -2 HIP error, -4 ODE failure)

@@ -41,6 +41,12 @@ SIGNATURES = {
     "knp_set_tabulation": (C.c_int, [_ctxp, C.c_int, C.c_int, C.c_int, _f64p, _f64p, _f64p]),
     "knp_set_mms": (C.c_int, [_ctxp, _f64p, _f64p, _f64p]),
     "knp_set_source": (C.c_int, [_ctxp, _f64p]),
+    "knp_source_set_rule": (C.c_int, [_ctxp, C.c_int, _f64p, _f64p, _f64p]),
+    "knp_source_register": (C.c_int, [_ctxp, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_int]),
+    "knp_source_eval": (C.c_int, [_ctxp, C.c_int, _f64p, C.c_int]),
+    "knp_source_clear": (C.c_int, [_ctxp, C.c_int]),
+    "knp_source_cells": (C.c_int64, [_ctxp]),
+    "knp_source_download": (C.c_int, [_ctxp, _f64p]),
     "knp_field_size": (C.c_int64, [_ctxp, C.c_int]),
     "knp_debug_table_size": (C.c_int64, [_ctxp, C.c_int]),
     "knp_debug_table": (C.c_int, [_ctxp, C.c_int, C.c_void_p, C.c_int64]),
@@ -502,6 +508,8 @@ class Device:
         self._pending = []                 # queued PDE<->ODE column copies: (handle, to_facet, what, col, field, offset)
         self._rtc_ids = {}                 # kernel name of a registered HIP_RHS model -> its device model id (knp_ode_register)
         self._rtc_methods = {}             # device model id -> the methods whose kernels are loaded (knp_ode_register_method)
+        self._source_rule_set = False      # the rule tables of the device-evaluated sources are uploaded (knp_source_set_rule)
+        self._source_kernels = {}          # species -> kernel name of its registered Expression (knp_source_register)
         self._tmp_slot = -1                # rotating scratch slot of facet_trace results
         self._tmp_gen = [0] * FACET_TMP_SLOTS
         if degree != 1:
@@ -560,6 +568,48 @@ class Device:
         if src is not None:
             src = np.ascontiguousarray(np.asarray(src, dtype=np.float64).reshape(self.n_sys, self.nc, self.nd)[:, self.cell_order])
         self._chk(self.lib.knp_set_source(self.ctx, _p(src, _f64p)), "knp_set_source")
+
+    # -- device-evaluated ion sources (knpemidg/expression.py builds, csrc/source.hip loads and launches) ---------------------
+    def source_register(self, species, expr):
+        """Make `expr` (a knpemidg.Expression) the source of `species`: compiled once per process for this context's dimension and
+        basis size, loaded on this context; the rule tables go up with the first registration.  A species whose registered kernel
+        is this one already (same code, parameter names, dimension and basis: values travel with every evaluation) is left alone.
+        A compile error raises KnpError with the hipRTC log."""
+        from knpemidg import expression
+        species = int(species)
+        if self._source_kernels.get(species) == expr.kernel_name(self.dim, self.nd):
+            return
+        kernel, code = expr.compiled(self.dim, self.nd)
+        if not self._source_rule_set:
+            bary, w, B = expression.rule_tables(self.dim, self.degree)
+            assert bary.shape == (len(w), self.dim + 1) and B.shape == (len(w), self.nd)
+            self._chk(self.lib.knp_source_set_rule(self.ctx, len(w), _p(bary, _f64p), _p(w, _f64p), _p(B, _f64p)), "knp_source_set_rule")
+            self._source_rule_set = True
+        self._chk(self.lib.knp_source_register(self.ctx, species, code, len(code), kernel.encode(), len(expr.names)),
+                  "knp_source_register")
+        self._source_kernels[species] = kernel
+
+    def source_eval(self, species, values):
+        """Enqueue the evaluation of the species' registered source with these parameter values (no copy, no wait)."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        self._chk(self.lib.knp_source_eval(self.ctx, int(species), _p(v, _f64p), v.size), "knp_source_eval")
+
+    def source_clear(self, species):
+        self._chk(self.lib.knp_source_clear(self.ctx, int(species)), "knp_source_clear")
+        self._source_kernels.pop(int(species), None)
+
+    def source_cells(self):
+        """Number of ECS cells the registered sources integrate over (-1 before the first registration)."""
+        return int(self.lib.knp_source_cells(self.ctx))
+
+    def source_download(self):
+        """The source load vectors as the right-hand side sees them, [n_sys, nc, nd] in caller cell order; None if the context holds none."""
+        out = np.empty((self.n_sys, self.nc, self.nd), dtype=np.float64)
+        rc = self.lib.knp_source_download(self.ctx, _p(out, _f64p))
+        if rc == 1:
+            return None
+        self._chk(rc, "knp_source_download")
+        return np.ascontiguousarray(out[:, self.cell_rank])
 
     def size(self, field):
         return int(self.lib.knp_field_size(self.ctx, field))
