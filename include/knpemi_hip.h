@@ -576,7 +576,7 @@ int knp_apply_timing_read(knp_ctx* ctx, int which, float* avg_ms, int* count);
  * 9 assembled P2 blocks (KNP_P2_ASSEMBLED=1).  Negative on bad arguments.  No reference counterpart (measurement only). */
 int knp_apply_variant(knp_ctx* ctx, int which);
 
-/* FP64 MFMA probe of the DG-P2 path's dense facet-quadrature contraction (csrc/apply_p2.hip): variant 0 = per-thread FMA chain
+/* FP64 MFMA probe of the DG-P2 path's dense facet-quadrature contraction (csrc/p2_probe.hip): variant 0 = per-thread FMA chain
  * (what the product kernels use), 1 = v_mfma_f64_16x16x4_f64 tiles.  in[ncol][26] = {jump(u)[6], kappa[6], kappa'[6], dn u[3],
  * dn u'[3], area, penalty}, out[ncol][9] = {r[6], T[3]}; returns the average kernel time over `reps` launches.  Diagnostic
  * (no counterpart in the reference): it documents why the product path keeps the vector pipe. */

@@ -14,7 +14,7 @@ enum ApplyFamily : int {
     AF_HALO_MAT = 6,      // halo-staged, D from the material table
     AF_RING_KNP = 7,      // ring-staged KNP, material table (apply_ring.hip)
     AF_P2 = 8,            // matrix-free P2 (apply_p2.hip)
-    AF_P2_ASSEMBLED = 9,  // assembled P2 blocks (tab_dg.hip)
+    AF_P2_ASSEMBLED = 9,  // assembled P2 blocks (tab_assembled.hip)
     AF_RING_U = 10        // ring-staged without geometry classes (apply_ring_u.hip)
 };
 

@@ -132,8 +132,7 @@ template <> __device__ __forceinline__ void gradients<2>(const double (*X)[2], C
     K.vol = fabs(det) * 0.5;
 }
 
-template <int D> __device__ __forceinline__ void cell_geometry_from(const double (*X)[D], CellGeom<D>& K) {
-    gradients<D>(X, K);
+template <int D> __device__ __forceinline__ void gram_matrix(CellGeom<D>& K) {
 #pragma unroll
     for (int a = 0; a <= D; ++a)
 #pragma unroll
@@ -144,11 +143,31 @@ template <int D> __device__ __forceinline__ void cell_geometry_from(const double
         }
 }
 
-template <int D> __device__ __forceinline__ void load_cell_geometry(const MeshDev& m, const int* verts, CellGeom<D>& K) {
+template <int D> __device__ __forceinline__ void cell_geometry_from(const double (*X)[D], CellGeom<D>& K) {
+    gradients<D>(X, K);
+    gram_matrix<D>(K);
+}
+
+// gradients + volume of the cell with vertex ids verts[] / of cell c (the tabulated DG-p kernels need no Gram matrix)
+template <int D> __device__ __forceinline__ void load_cell_gradients(const MeshDev& m, const int* verts, CellGeom<D>& K) {
     double X[D + 1][D];
 #pragma unroll
     for (int a = 0; a <= D; ++a) load_vertex<D>(m.coords, verts[a], X[a]);
-    cell_geometry_from<D>(X, K);
+    gradients<D>(X, K);
+}
+template <int D> __device__ __forceinline__ void load_cell_gradients(const MeshDev& m, int64_t c, CellGeom<D>& K) {
+    int v[D + 1];
+    load_cell_ints<D>(m.cells, c, v);
+    load_cell_gradients<D>(m, v, K);
+}
+
+template <int D> __device__ __forceinline__ void load_cell_geometry(const MeshDev& m, const int* verts, CellGeom<D>& K) {
+    load_cell_gradients<D>(m, verts, K);
+    gram_matrix<D>(K);
+}
+template <int D> __device__ __forceinline__ void load_cell_geometry(const MeshDev& m, int64_t c, CellGeom<D>& K) {
+    load_cell_gradients<D>(m, c, K);
+    gram_matrix<D>(K);
 }
 
 // Workgroup-local staging of what facet neighbours need from a cell (x, coefficient, diameter, vertex

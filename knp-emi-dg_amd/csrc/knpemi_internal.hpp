@@ -71,7 +71,7 @@ struct Params {
     int splitting = 1;
 };
 
-// one quadrature rule with the reference basis tabulated at its points (DG-p path, tab_dg.hip); device pointers
+// one quadrature rule with the reference basis tabulated at its points (DG-p path, tab_rhs.hip / tab_assembled.hip); device pointers
 struct TabRule {
     int nq = 0;
     const double* w = nullptr;     // [nq], sums to 1
@@ -153,7 +153,7 @@ struct knp_ctx {
     double* extra_emi = nullptr;   // [nc*nd]
     double* extra_knp = nullptr;   // [n_sys][nc*nd]
     SourceState* src = nullptr;    // device-evaluated ion sources writing rows of extra_knp (source.hip; created by the first call that needs it)
-    // DG-p (p >= 2) path: tabulated rules + assembled cell blocks [nc][dim+2][nd][nd] (tab_dg.hip)
+    // DG-p (p >= 2) path: tabulated rules + assembled cell blocks [nc][dim+2][nd][nd] (tab_rhs.hip, tab_assembled.hip)
     TabRule tab[KNP_TAB_COUNT];
     double* tab_mem[KNP_TAB_COUNT] = {nullptr};
     double* blk_emi = nullptr;
@@ -300,18 +300,31 @@ int launch_step_updates(knp_ctx* c, const double* cc, double* celim, const doubl
                         double* phiM, double* E);
 int launch_facet_trace(knp_ctx* c, const double* nodal, int side, double* out);
 
-// DG-p path (tab_dg.hip)
+// DG-p path, p >= 2: what every step needs (tab_rhs.hip: nodal coefficient fields, right-hand sides, membrane-facet updates over the
+// tabulated rules of knp_set_tabulation) ...
 int tab_kappa(knp_ctx* c, const double* cc, const double* celim, double* kappa);
-int tab_assemble_knp(knp_ctx* c, const double* phi);
-int tab_apply(knp_ctx* c, int which, const double* x, double* y);
-int tab_block_inverse(knp_ctx* c, int which, bjreal* binv);
 int tab_emi_rhs(knp_ctx* c, const double* cc, const double* celim, const double* phiM, const double* Ich, double* b);
 int tab_knp_rhs(knp_ctx* c, const double* cc, const double* cprev, const double* celim, const double* phi, const double* phiM,
                 const double* Ich, double* b);
 int tab_step_updates(knp_ctx* c, const double* cc, double* celim, const double* phi, double* phiM, double* E, bool do_celim);
 int tab_facet_trace(knp_ctx* c, const double* nodal, int side, double* out);
-void tab_free(knp_ctx* c);
+void tab_free(knp_ctx* c);                              // the rules, and the blocks below
+// ... and the assembled operator blocks of KNP_P2_ASSEMBLED=1 (tab_assembled.hip: A/B runs against the matrix-free applies only)
 inline bool p2_assembled(const knp_ctx* c) { return c->p2_assembled; }   // KNP_P2_ASSEMBLED=1: round-1 path (quadrature-assembled cell blocks) instead of the matrix-free applies
+int tab_assemble_emi(knp_ctx* c, const double* kappa);
+int tab_assemble_knp(knp_ctx* c, const double* phi);
+int tab_apply(knp_ctx* c, int which, const double* x, double* y);
+int tab_block_inverse(knp_ctx* c, int which, bjreal* binv);
+void tab_free_blocks(knp_ctx* c);
+
+// what a P2 KNP operator kernel, matrix-free or assembling, takes from the parameters: one record, one filler
+struct KnpOpArgs { double inv_dt, psi, tau; double z[KNP_MAX_SYS]; };
+inline KnpOpArgs knp_op_args(const knp_ctx* c) {
+    KnpOpArgs ka;
+    ka.inv_dt = 1.0 / c->p.dt; ka.psi = c->p.psi; ka.tau = c->p.tau_knp;
+    for (int k = 0; k < KNP_MAX_SYS; ++k) ka.z[k] = k < c->p.n_sys ? c->p.z[k] : 0.0;
+    return ka;
+}
 
 // ring-staged P1 applies on structured 3D meshes (apply_ring.hip): loader wave + LDS-DMA ring + consumer waves
 bool ring_usable(const knp_ctx* c, int which);       // which: 0 EMI, 1 KNP
@@ -323,7 +336,7 @@ int ring_u_knp_apply(knp_ctx* c, const MeshDev& m, const double* x, const double
 int ring_emi_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* kappa, double* y, int reserve_cus);
 int ring_knp_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* gphi, double* y, const KnpArgs& ka, int reserve_cus);
 
-// matrix-free DG-P2 applies (apply_p2.hip)
+// matrix-free DG-P2 applies and their cell-diagonal block inverses (apply_p2.hip; its device pieces: p2_frame.hpp)
 int p2_emi_apply(knp_ctx* c, const double* x, const double* kappa, double* y);
 int p2_knp_apply(knp_ctx* c, const double* x, const double* phi, double* y);
 int p2_block_inverse(knp_ctx* c, int which, const double* coef, bjreal* binv);

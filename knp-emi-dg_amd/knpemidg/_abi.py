@@ -513,7 +513,7 @@ class Device:
         self._tmp_slot = -1                # rotating scratch slot of facet_trace results
         self._tmp_gen = [0] * FACET_TMP_SLOTS
         if degree != 1:
-            # DG-p path: the device integrates the forms with host-tabulated rules (csrc/tab_dg.hip)
+            # DG-p path: the device integrates the forms with host-tabulated rules (csrc/tab_rhs.hip)
             from knpemidg import dgtab
             for slot, (nloc, nq, w, B, dB) in dgtab.tables(self.dim, degree).items():
                 self._chk(self.lib.knp_set_tabulation(self.ctx, slot, nloc, nq, _p(w, _f64p), _p(B, _f64p), _p(dB, _f64p)),

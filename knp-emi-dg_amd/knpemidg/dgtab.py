@@ -1,4 +1,4 @@
-"""Reference-basis tabulations for the device's DG-p path (csrc/tab_dg.hip, knp_set_tabulation).
+"""Reference-basis tabulations for the device's DG-p path (csrc/tab_rhs.hip, csrc/tab_assembled.hip; knp_set_tabulation).
 
 Lagrange P2 on simplices in barycentric coordinates; local dof order: the dim+1 vertices, then the edge midpoints
 (a, b), a < b, in lexicographic order.  The quadrature degree of every integral class is the one UFL estimates for the

@@ -1,5 +1,5 @@
 """Two small UNSTRUCTURED meshes on which every ordered pair (own local facet I, neighbour's local facet j) occurs, and the helper
-that counts the pairs.  The DG-P2 kernels (csrc/apply_p2.hip, csrc/tab_dg.hip) and the 2D coordinate kernels treat a facet by
+that counts the pairs.  The DG-P2 kernels (csrc/apply_p2.hip, csrc/tab_rhs.hip, csrc/tab_assembled.hip) and the 2D coordinate kernels treat a facet by
 that index pair: I is a template parameter, j picks the permutation the neighbour's dofs are gathered through, so each pair is
 its own piece of arithmetic -- 16 in 3D, 9 in 2D.  Box meshes and their refinements carry 4 of 16 (5 of 9) on SIPG facets and
 2 (1) on membrane facets; these two carry all of them, on every facet class.  Data selection only, no arithmetic of either path.

@@ -454,7 +454,7 @@ def test_stale_projection_result_raises(hip_lib):
 
 
 def test_fp64_mfma_probe_matches_fma_chain(hip_lib):
-    """The DG-P2 facet-quadrature contraction as v_mfma_f64_16x16x4_f64 tiles (diagnostic variant, csrc/apply_p2.hip) gives
+    """The DG-P2 facet-quadrature contraction as v_mfma_f64_16x16x4_f64 tiles (diagnostic variant, csrc/p2_probe.hip) gives
     the same numbers as the per-thread FMA chain of the product kernels -- and as the numpy formula -- on random inputs,
     including a ragged column count (partial last tile)."""
     import p2_formulation as pf

@@ -1,4 +1,4 @@
-"""The DG-P2 kernels (csrc/apply_p2.hip, csrc/tab_dg.hip) and the 2D coordinate kernels against the CPU oracle on meshes that carry
+"""The DG-P2 kernels (csrc/apply_p2.hip, csrc/tab_rhs.hip, csrc/tab_assembled.hip) and the 2D coordinate kernels against the CPU oracle on meshes that carry
 EVERY ordered pair (own local facet I, neighbour's local facet j) -- tests/p2_meshes.py; the box meshes of the other comparisons
 carry 4 of 16 (5 of 9) -- through the C ABI, on seeded inputs.  Also the first runs of: the 3D coordinate-geometry P2 instantiations on
 more than two cells, the assembled-blocks switch KNP_P2_ASSEMBLED=1, P2 with rho != 0, D per subdomain / per cell and one / three

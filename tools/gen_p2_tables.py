@@ -1,5 +1,5 @@
 """Generates knp-emi-dg_amd/csrc/p2_tables.hpp: reference-element constants of the matrix-free DG-P2 operator applies
-(csrc/apply_p2.hip).  Everything here is geometry independent:
+(csrc/apply_p2.hip, csrc/p2_frame.hpp).  Everything here is geometry independent:
 
   M3[b][vv']   int phi_b lambda_v lambda_v'   (reference measure 1)  -- exact cell integrals of  coef(P2) * P1 * P1
   MASS[a][b]   int phi_a phi_b
