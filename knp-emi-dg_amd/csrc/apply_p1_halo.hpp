@@ -3,7 +3,6 @@
 #pragma once
 #include "cell_geom.hpp"
 #include <algorithm>
-#include <map>
 
 // ---- halo-staged persistent variants (3D P1, structured meshes) -------------------------------------------------------
 // Measured on the staged kernels above (tools/pmc_apply.sh, profiles/r02_pmc_apply_halo.md): 60 % of the wave cycles are
@@ -269,16 +268,12 @@ static int* halo_counters(knp_ctx* c, int which, int* flip_nq) {
 // reserve_cus: with an active communicator the interior launch runs next to the halo exchange (pack kernel + RCCL's send / receive
 // kernels on the high-priority halo stream, comm.hip): a persistent grid that occupies every CU would leave them nothing to run on
 // until its first workgroups retire, so it is sized for (CUs - reserve_cus).
-template <typename KernelT> static dim3 halo_grid(const MeshDev& m, int device, KernelT kernel, size_t lds, int reserve_cus) {
+template <typename KernelT> static dim3 halo_grid(knp_ctx* c, const MeshDev& m, KernelT kernel, size_t lds, int reserve_cus) {
     const int64_t nb = (m.c_end - 1) / KNP_HALO_BLK - m.c_begin / KNP_HALO_BLK + 1;
-    static int ncu = 0;
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        ncu = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
+    const int ncu = c->ncu;
     int per_cu = env_int("KNP_HALO_WG_PER_CU", 0);
     if (per_cu <= 0) {
-        static std::map<std::pair<const void*, size_t>, int> cache;            // one occupancy query per kernel instance and LDS size
+        auto& cache = c->halo_wg_per_cu;                                       // one occupancy query per context, kernel instance and LDS size
         const auto key = std::make_pair((const void*)kernel, lds);
         auto it = cache.find(key);
         if (it == cache.end()) {
@@ -317,7 +312,7 @@ static int knp_halo_launch(knp_ctx* c, const MeshDev& m, const double* x, const 
     int* ctr = halo_counters(c, 1, &flip_nq);
     auto launch = [&](auto ns, auto mat) {
         const auto kernel = k_knp_apply_halo<decltype(ns)::value, decltype(mat)::value>;
-        hipLaunchKernelGGL(kernel, halo_grid(m, c->device, kernel, lds, reserve_cus), dim3(KNP_HALO_BLK), lds, c->stream, m, x, gphi, c->D, y, ka,
+        hipLaunchKernelGGL(kernel, halo_grid(c, m, kernel, lds, reserve_cus), dim3(KNP_HALO_BLK), lds, c->stream, m, x, gphi, c->D, y, ka,
                            ent, (const uint8_t*)c->mat, (const uint8_t*)c->nmat4, (const double*)c->dtab, ctr, flip_nq);
         return 0;
     };

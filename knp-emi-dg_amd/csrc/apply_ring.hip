@@ -320,8 +320,8 @@ bool ring_usable(const knp_ctx* c, int which) {
 
 int ring_emi_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* kappa, double* y, int reserve_cus) {
     const size_t lds = ring_lds_bytes(c, 0);
-    if (!grant_lds(k_emi_apply_ring, lds)) { c->err = "hipFuncSetAttribute(k_emi_apply_ring) failed"; return -2; }
-    hipLaunchKernelGGL(k_emi_apply_ring, ring_grid(m, c->device, reserve_cus), dim3(2 * RB + 64 * RLOADERS), lds, c->stream, m, x, kappa, y, c->p.C_phi, c->p.tau_emi);
+    if (!grant_lds(c, k_emi_apply_ring, lds)) { c->err = "hipFuncSetAttribute(k_emi_apply_ring) failed"; return -2; }
+    hipLaunchKernelGGL(k_emi_apply_ring, ring_grid(c, m, reserve_cus), dim3(2 * RB + 64 * RLOADERS), lds, c->stream, m, x, kappa, y, c->p.C_phi, c->p.tau_emi);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -329,11 +329,11 @@ int ring_emi_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* 
 int ring_knp_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* gphi, double* y, const KnpArgs& ka, int reserve_cus) {
     const int ns = c->p.n_sys;
     const size_t lds = ring_lds_bytes(c, 1);
-    const dim3 g = ring_grid(m, c->device, reserve_cus);
+    const dim3 g = ring_grid(c, m, reserve_cus);
     const bool split = ns == 2 && env_int("KNP_RING_SPLIT", 0) != 0;       // two consumer groups, one species each (measured equal to one group: 47.6 vs 46.3 us)
 #define RING_KNP_LAUNCH(NS_, NG_)                                                                                                     \
     do {                                                                                                                              \
-        if (!grant_lds(k_knp_apply_ring<NS_, NG_>, lds)) { c->err = "hipFuncSetAttribute(k_knp_apply_ring) failed"; return -2; }  \
+        if (!grant_lds(c, k_knp_apply_ring<NS_, NG_>, lds)) { c->err = "hipFuncSetAttribute(k_knp_apply_ring) failed"; return -2; }  \
         hipLaunchKernelGGL((k_knp_apply_ring<NS_, NG_>), g, dim3(RB * NG_ + 64 * RLOADERS), lds, c->stream, m, x, gphi, y, ka, (const uint8_t*)c->mat,  \
                            (const uint8_t*)c->nmat4, (const double*)c->dtab, env_int("KNP_RING_DEBUG", 0));                     \
     } while (0)

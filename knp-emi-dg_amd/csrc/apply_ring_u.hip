@@ -17,13 +17,14 @@
 //
 // Streaming a precomputed per-cell geometry record instead (Gram matrix + per-facet coefficients: 248-344 B per cell) would triple the
 // bytes of a 137-byte operator; recomputing costs FP64 issue slots, which the loaders' stream leaves free.
+//
+// The per-block tables of a context are its RingUState (knp_ctx::ring_u): built by the first ring_u_cells, read by the launchers without
+// a look-up or a lock, freed by ring_u_free.  The CU count and the LDS grants of the launches are the context's too (ring_common.hpp).
 #include "cell_geom.hpp"
 #include "ring_common.hpp"
 #include "ring_facet.hpp"
 #include <algorithm>
 #include <cstdlib>
-#include <map>
-#include <mutex>
 #include <vector>
 
 namespace {
@@ -291,10 +292,15 @@ __global__ __launch_bounds__(RB + 64 * ULOADERS) void k_knp_apply_ring_u(MeshDev
     }
 }
 
+}  // namespace
+
+// knp_ctx::ring_u: created by the first ring_u_cells that gets as far as the tables, freed by ring_u_free
 struct RingUState {
     RingUTables T;
-    bool tried = false, usable = false;
+    bool usable = false;
 };
+
+namespace {
 
 template <typename Tp> int up_u(knp_ctx* c, Tp** dst, const std::vector<Tp>& src) {
     const size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(Tp);
@@ -374,31 +380,14 @@ int build_tables_u(knp_ctx* c, RingUState& S) {
     return 0;
 }
 
-// per-context tables.  The map is guarded (contexts may live on different host threads; std::map keeps references to other entries
-// valid across insert / erase), a context's own entry is only touched by the thread that drives that context.
-std::mutex g_states_mu;
-std::map<const knp_ctx*, RingUState>& states_locked() {
-    static std::map<const knp_ctx*, RingUState> s;
-    return s;
-}
-RingUState& state_u(const knp_ctx* c) {
-    std::lock_guard<std::mutex> lock(g_states_mu);
-    return states_locked()[c];
-}
-
 }  // namespace
 
 void ring_u_free(knp_ctx* c) {
-    RingUTables T;
-    {
-        std::lock_guard<std::mutex> lock(g_states_mu);
-        auto& st = states_locked();
-        auto it = st.find(c);
-        if (it == st.end()) return;
-        T = it->second.T;
-        st.erase(it);
-    }
+    if (!c->ring_u) return;
+    const RingUTables& T = c->ring_u->T;
     hipFree(T.hb_src); hipFree(T.hb_loc); hipFree(T.vb_src); hipFree(T.vloc); hipFree(T.hinv4);
+    delete c->ring_u;
+    c->ring_u = nullptr;
 }
 
 static size_t ring_u_lds(const knp_ctx* c, int which) {
@@ -415,31 +404,33 @@ int64_t ring_u_cells(knp_ctx* c, int which) {
     if (env_int("KNP_APPLY_RING_U", 1) == 0 || env_int("KNP_APPLY_RING", 1) == 0) return 0;
     if (which == 1 && !(c->nmat > 0 && c->p.n_sys <= 2 && env_int("KNP_APPLY_MAT", 1) != 0)) return 0;
     if (ring_u_lds(c, which) > RING_MAX_LDS) return 0;
-    RingUState& S = state_u(c);
-    if (!S.tried) {
-        S.tried = true;
-        if (build_tables_u(c, S)) { S.usable = false; return 0; }
+    if (!c->ring_u) {                                                  // one attempt per context: the state exists from here on, usable or not
+        c->ring_u = new RingUState();
+        if (build_tables_u(c, *c->ring_u)) { c->ring_u->usable = false; return 0; }
     }
+    const RingUState& S = *c->ring_u;
     return S.usable ? std::min<int64_t>(S.T.long0 * RB, c->m.nc_owned) : 0;
 }
 
 int ring_u_emi_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* kappa, double* y, int reserve_cus) {
-    const RingUTables& T = state_u(c).T;
+    if (!c->ring_u || !c->ring_u->usable) { c->err = "unstructured ring: no tables (ring_u_cells was not asked, or said no)"; return -1; }
+    const RingUTables& T = c->ring_u->T;
     const size_t lds = ring_u_lds(c, 0);
-    if (!grant_lds(k_emi_apply_ring_u, lds)) { c->err = "hipFuncSetAttribute(k_emi_apply_ring_u) failed"; return -2; }
-    hipLaunchKernelGGL(k_emi_apply_ring_u, ring_grid(m, c->device, reserve_cus), dim3(RB + 64 * ULOADERS), lds, c->stream, m, T, x, kappa, y, c->p.C_phi,
+    if (!grant_lds(c, k_emi_apply_ring_u, lds)) { c->err = "hipFuncSetAttribute(k_emi_apply_ring_u) failed"; return -2; }
+    hipLaunchKernelGGL(k_emi_apply_ring_u, ring_grid(c, m, reserve_cus), dim3(RB + 64 * ULOADERS), lds, c->stream, m, T, x, kappa, y, c->p.C_phi,
                        c->p.tau_emi);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
 
 int ring_u_knp_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* gphi, double* y, const KnpArgs& ka, int reserve_cus) {
-    const RingUTables& T = state_u(c).T;
+    if (!c->ring_u || !c->ring_u->usable) { c->err = "unstructured ring: no tables (ring_u_cells was not asked, or said no)"; return -1; }
+    const RingUTables& T = c->ring_u->T;
     const size_t lds = ring_u_lds(c, 1);
-    const dim3 g = ring_grid(m, c->device, reserve_cus);
+    const dim3 g = ring_grid(c, m, reserve_cus);
     return dispatch_nsys<2>(c->p.n_sys, [&](auto ns) {               // ring_u_cells admits one or two solved species
         const auto kernel = k_knp_apply_ring_u<decltype(ns)::value>;
-        if (!grant_lds(kernel, lds)) { c->err = "hipFuncSetAttribute(k_knp_apply_ring_u) failed"; return -2; }
+        if (!grant_lds(c, kernel, lds)) { c->err = "hipFuncSetAttribute(k_knp_apply_ring_u) failed"; return -2; }
         hipLaunchKernelGGL(kernel, g, dim3(RB + 64 * ULOADERS), lds, c->stream, m, T, x, gphi, y, ka, (const uint8_t*)c->mat,
                            (const uint8_t*)c->nmat4, (const double*)c->dtab);
         HIPCHK(c, hipGetLastError());

@@ -143,6 +143,8 @@ int knp_ctx_create(knp_ctx** out, int device, int dim, int degree, int n_ions, i
     if (hipStreamCreate(&c->stream) != hipSuccess) { g_err = "hipStreamCreate failed"; delete c; return -5; }
     hipEventCreate(&c->ev0);
     hipEventCreate(&c->ev1);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->ncu = prop.multiProcessorCount;
     stamp("HIP runtime, stream");
 
     const MeshIn in{dim, NV, nv, nc, nc_owned, nf, coords, cells, cell_tags, facet_cells, facet_local, facet_tags, n_membrane_tags, membrane_tags};

@@ -22,6 +22,8 @@
 //
 // Frames land in one of two pinned host buffers: kernel, asynchronous copy and an event on the context's stream;
 // knp_grid_fetch waits for that event only.  The grid holds no step-to-step state: it adds no checkpoint block.
+// The grids of a context and its uploaded tag table are its GridState (knp_ctx::grid): created with the first grid, freed by
+// grid_destroy_all, shared with no other context.
 #include "../../include/knpemi_hip.h"
 #include "knpemi_internal.hpp"
 #include <cmath>
@@ -78,11 +80,15 @@ struct Grid {
     size_t frame_bytes() const { return (size_t)planes() * (size_t)npts * (f32 ? 4 : 8); }
 };
 
-struct GridCtx {
+}  // namespace
+
+// knp_ctx::grid: created by the first knp_grid_create that passes validation and allocation, freed by grid_destroy_all
+struct GridState {
     Grid* g[KNP_GRID_MAX] = {nullptr};
     uint32_t* ctag = nullptr;       // device [nc]: the context's subdomain table, uploaded with the first grid
 };
-std::map<knp_ctx*, GridCtx> g_grid;
+
+namespace {
 
 // ---- arithmetic shared by the locate and the weights pass: every product and sum rounded on its own -------------------------------
 __device__ __forceinline__ double g_mul(double a, double b) { return __dmul_rn(a, b); }
@@ -432,23 +438,22 @@ void grid_free(Grid* g) {
 }
 
 Grid* grid_find(knp_ctx* c, int handle, const char* who) {
-    auto it = g_grid.find(c);
-    if (it == g_grid.end() || handle < 0 || handle >= KNP_GRID_MAX || !it->second.g[handle]) {
+    if (!c->grid || handle < 0 || handle >= KNP_GRID_MAX || !c->grid->g[handle]) {
         c->err = std::string(who) + ": no grid with handle " + std::to_string(handle) + " (knp_grid_create)";
         return nullptr;
     }
-    return it->second.g[handle];
+    return c->grid->g[handle];
 }
 
 }  // namespace
 
 void grid_destroy_all(knp_ctx* c) {
-    auto it = g_grid.find(c);
-    if (it == g_grid.end()) return;
+    if (!c->grid) return;
     host_stream_sync(c, c->stream);
-    for (Grid* g : it->second.g) grid_free(g);
-    hipFree(it->second.ctag);
-    g_grid.erase(it);
+    for (Grid* g : c->grid->g) grid_free(g);
+    hipFree(c->grid->ctag);
+    delete c->grid;
+    c->grid = nullptr;
 }
 
 extern "C" {
@@ -503,10 +508,9 @@ int knp_grid_create_derived(knp_ctx* c, const double* lo, const double* h, const
     if (n_derived && !(c->p.dt > 0.0)) { c->err = "knp_grid_create_derived: the parameters were never set (knp_set_params)"; return -1; }
     if (m.nc >= (int64_t)KNP_GRID_NONE) { c->err = "knp_grid_create: too many cells"; return -1; }
     if (c->h_ctag.size() != (size_t)m.nc) { c->err = "knp_grid_create: the context holds no subdomain table"; return -1; }
-    auto found = g_grid.find(c);
     int handle = -1;
     for (int s = 0; s < KNP_GRID_MAX && handle < 0; ++s)
-        if (found == g_grid.end() || !found->second.g[s]) handle = s;
+        if (!c->grid || !c->grid->g[s]) handle = s;
     if (handle < 0) { c->err = "knp_grid_create: at most 8 grids per context"; return -1; }
 
     HIPCHK(c, hipSetDevice(c->device));
@@ -519,7 +523,7 @@ int knp_grid_create_derived(knp_ctx* c, const double* lo, const double* h, const
     T.n = n_tags;
     for (int q = 0; q < KNP_GRID_MAX_TAGS; ++q) T.t[q] = q < n_tags ? tags[q] : 0u;
     const size_t np = (size_t)g->npts;
-    uint32_t* ctag = found == g_grid.end() ? nullptr : found->second.ctag;
+    uint32_t* ctag = c->grid ? c->grid->ctag : nullptr;
     const bool own_ctag = ctag == nullptr;
     bool ok = hipMalloc((void**)&g->owner, 4 * np) == hipSuccess && hipMalloc((void**)&g->cell, 4 * np) == hipSuccess &&
               hipMalloc((void**)&g->tag, 4 * np) == hipSuccess && hipMalloc((void**)&g->lam, 8 * np * (size_t)(d + 1)) == hipSuccess &&
@@ -537,7 +541,8 @@ int knp_grid_create_derived(knp_ctx* c, const double* lo, const double* h, const
         return -2;
     }
     // ---- from here on the context changes ------------------------------------------------------------------------------------------
-    GridCtx& X = g_grid[c];
+    if (!c->grid) c->grid = new GridState();
+    GridState& X = *c->grid;
     X.ctag = ctag;
     X.g[handle] = g;
     int rc = 0;
@@ -645,7 +650,7 @@ int knp_grid_destroy(knp_ctx* c, int grid) {
     if (!g) return -1;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, host_stream_sync(c, c->stream));
-    g_grid[c].g[grid] = nullptr;
+    c->grid->g[grid] = nullptr;
     grid_free(g);
     return 0;
 }

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 #include <map>
 #include "../../include/knpemi_hip.h"
@@ -120,7 +121,14 @@ struct Fields {
     }
 };
 
+// Per-context state of the subsystems, each defined in the file that owns it.  The owner creates its struct at the first call that
+// needs it and frees it (and nulls the pointer) in its destroy function below: the library keeps no per-context state outside the context.
 struct SourceState;                // source.hip: the context's device-evaluated ion sources
+struct OdeState;                   // ode.hip: membrane-model sets and runtime-compiled models
+struct RecState;                   // record.hip: the time-series recorder
+struct GridState;                  // grid.hip: voxel grids and the uploaded tag table
+struct CkptState;                  // state.hip: cell permutation, checkpoint staging, events
+struct RingUState;                 // apply_ring_u.hip: per-block tables of the unstructured ring
 
 struct knp_ctx {
     int device = 0;
@@ -153,6 +161,15 @@ struct knp_ctx {
     double* extra_emi = nullptr;   // [nc*nd]
     double* extra_knp = nullptr;   // [n_sys][nc*nd]
     SourceState* src = nullptr;    // device-evaluated ion sources writing rows of extra_knp (source.hip; created by the first call that needs it)
+    OdeState* ode = nullptr;       // ode.hip (knp_ode_create / knp_ode_register)
+    RecState* rec = nullptr;       // record.hip (knp_rec_create)
+    GridState* grid = nullptr;     // grid.hip (knp_grid_create)
+    CkptState* ckpt = nullptr;     // state.hip (knp_state_cell_order / knp_state_save / knp_state_load)
+    RingUState* ring_u = nullptr;  // apply_ring_u.hip (ring_u_cells)
+    // launch caches of the persistent applies: what the context's device answered, asked once per context
+    int ncu = 256;                 // compute units of the device (knp_ctx_create; 256 when the query fails)
+    std::map<const void*, size_t> lds_granted;                        // kernel -> dynamic LDS granted to it (ring_common.hpp: grant_lds)
+    std::map<std::pair<const void*, size_t>, int> halo_wg_per_cu;     // (kernel, LDS bytes) -> occupancy answer (apply_p1_halo.hpp: halo_grid)
     // DG-p (p >= 2) path: tabulated rules + assembled cell blocks [nc][dim+2][nd][nd] (tab_rhs.hip, tab_assembled.hip)
     TabRule tab[KNP_TAB_COUNT];
     double* tab_mem[KNP_TAB_COUNT] = {nullptr};
@@ -261,6 +278,23 @@ inline double* knp_field_ptr(knp_ctx* c, int field, int64_t* n) {
     if (!c || field < 0 || field >= KNP_F_COUNT) return nullptr;
     if (n) *n = c->fields.n[field];
     return c->fields.f[field];
+}
+
+// A runtime-compiled code object onto the context's current device: its module and the named kernel, or -2 with the module unloaded
+// again (ode.hip: membrane models, source.hip: ion sources; `who` names the caller in the error text)
+inline int rtc_load_kernel(knp_ctx* c, const char* who, const void* code, const char* kernel_name, hipModule_t* mod_out, hipFunction_t* fn_out) {
+    hipModule_t mod = nullptr;
+    hipFunction_t fn = nullptr;
+    HIPCHK(c, hipModuleLoadData(&mod, code));            // reads the ELF's own size
+    const hipError_t e = hipModuleGetFunction(&fn, mod, kernel_name);
+    if (e != hipSuccess) {
+        hipModuleUnload(mod);
+        c->err = std::string(who) + ": kernel " + kernel_name + " not in the code object: " + hipGetErrorString(e);
+        return -2;
+    }
+    *mod_out = mod;
+    *fn_out = fn;
+    return 0;
 }
 
 inline int64_t grid_for(int64_t n) { return (n + KNP_BLOCK - 1) / KNP_BLOCK; }

@@ -6,6 +6,7 @@
 // membrane models of the idealized examples (reference: examples/idealized-geometries/mm_hh.py:118-161).
 // A set may be switched to a second integrator for stiff models (knp_ode_set_method: ode_stiff.hpp, extrapolated linearly implicit
 // Euler); it shares the tables, the stimulus, the step-size carry-over and the failure flag, and adds four step / call counters.
+// The sets and the runtime-compiled models of a context are its OdeState (knp_ctx::ode): nothing here is shared between contexts.
 #include "../../include/knpemi_hip.h"
 #include "knpemi_internal.hpp"
 #include "ode_dp5.hpp"
@@ -36,8 +37,6 @@ struct OdeSet {
     double stim_val[ODE_MAX_STIM] = {0};
 };
 
-static std::map<knp_ctx*, std::vector<OdeSet>> g_ode;
-
 // a model module's HIP_RHS compiled by hipRTC (knpemidg/ode_rtc.py) and loaded on one context's device
 #define ODE_N_METHODS 2
 struct RtcModel {
@@ -45,12 +44,22 @@ struct RtcModel {
     hipFunction_t fn[ODE_N_METHODS] = {nullptr, nullptr};
     int ns = 0, np = 0;
 };
-static std::map<knp_ctx*, std::vector<RtcModel>> g_rtc;
+
+// knp_ctx::ode: created by the first knp_ode_create / knp_ode_register, freed by ode_destroy_all.  A handle is an index into `sets`, a
+// registered model id is ODE_RTC_ID0 + an index into `rtc`; neither vector ever shrinks while the context lives.
+struct OdeState {
+    std::vector<OdeSet> sets;
+    std::vector<RtcModel> rtc;
+};
+
+static OdeState& ode_make(knp_ctx* c) {
+    if (!c->ode) c->ode = new OdeState();
+    return *c->ode;
+}
 
 static const RtcModel* rtc_model(knp_ctx* c, int model) {
-    auto it = g_rtc.find(c);
-    if (it == g_rtc.end() || model < ODE_RTC_ID0 || model - ODE_RTC_ID0 >= (int)it->second.size()) return nullptr;
-    return &it->second[model - ODE_RTC_ID0];
+    if (!c->ode || model < ODE_RTC_ID0 || model - ODE_RTC_ID0 >= (int)c->ode->rtc.size()) return nullptr;
+    return &c->ode->rtc[model - ODE_RTC_ID0];
 }
 
 // Hodgkin-Huxley squid axon + leak + Na/K pump (+ decaying synaptic conductance), SI units.
@@ -276,13 +285,13 @@ int sync_check_ode(knp_ctx* c) {
 }
 
 static OdeSet* get_set(knp_ctx* c, int handle) {
-    auto it = g_ode.find(c);
-    if (it == g_ode.end() || handle < 0 || handle >= (int)it->second.size()) return nullptr;
-    return &it->second[handle];
+    if (!c->ode || handle < 0 || handle >= (int)c->ode->sets.size()) return nullptr;
+    return &c->ode->sets[handle];
 }
 
 // state table of a handle for the recorder's state channels (record.hip): device pointer [n][ns]; false = no such handle.  The
-// pointer stays valid until the context is destroyed (tables are never reallocated).
+// pointer stays valid until the context is destroyed: a later knp_ode_create may move the OdeSet records, never the device tables
+// they point to.
 bool ode_state_table(knp_ctx* c, int handle, const double** states, int64_t* n, int* ns) {
     const OdeSet* S = get_set(c, handle);
     if (!S) return false;
@@ -290,16 +299,17 @@ bool ode_state_table(knp_ctx* c, int handle, const double** states, int64_t* n, 
     return true;
 }
 
-static void rtc_unload_all(knp_ctx* c);
+static void set_free(OdeSet& S) {
+    hipFree(S.facet); hipFree(S.states); hipFree(S.params); hipFree(S.h); hipFree(S.stim_mask); hipFree(S.stats);
+}
 
 // checkpoint (state.hip): per model the state and parameter tables and the last accepted step size of every node, in the node order
 // the model was created with (the caller's).  Block ids 1000 + 8 handle + {0, 1, 2}; the widths carry the model layout, so a snapshot
 // of other models does not load.  The stimulus mask and values are configuration: the host sends them again.
 int ode_state_blocks(knp_ctx* c, std::vector<StateBlk>& out) {
-    auto it = g_ode.find(c);
-    if (it == g_ode.end()) return 0;
-    for (size_t h = 0; h < it->second.size(); ++h) {
-        OdeSet& S = it->second[h];
+    if (!c->ode) return 0;
+    for (size_t h = 0; h < c->ode->sets.size(); ++h) {
+        OdeSet& S = c->ode->sets[h];
         void* dev[3] = {S.states, S.params, S.h};
         const int width[3] = {S.ns, S.np, 1};
         for (int q = 0; q < 3; ++q) {
@@ -312,21 +322,14 @@ int ode_state_blocks(knp_ctx* c, std::vector<StateBlk>& out) {
 }
 
 void ode_destroy_all(knp_ctx* c) {
-    rtc_unload_all(c);
-    auto it = g_ode.find(c);
-    if (it == g_ode.end()) return;
-    for (auto& S : it->second) { hipFree(S.facet); hipFree(S.states); hipFree(S.params); hipFree(S.h); hipFree(S.stim_mask); hipFree(S.stats); }
-    g_ode.erase(it);
-}
-
-static void rtc_unload_all(knp_ctx* c) {
-    auto it = g_rtc.find(c);
-    if (it == g_rtc.end()) return;
-    host_stream_sync(c, c->stream);                // no launch of a registered kernel may still be in flight
-    for (auto& R : it->second)
+    if (!c->ode) return;
+    if (!c->ode->rtc.empty()) host_stream_sync(c, c->stream);   // no launch of a registered kernel may still be in flight
+    for (auto& R : c->ode->rtc)
         for (int q = 0; q < ODE_N_METHODS; ++q)
             if (R.mod[q]) hipModuleUnload(R.mod[q]);
-    g_rtc.erase(it);
+    for (auto& S : c->ode->sets) set_free(S);
+    delete c->ode;
+    c->ode = nullptr;
 }
 
 extern "C" {
@@ -348,23 +351,31 @@ int knp_ode_create(knp_ctx* c, int model, int64_t n, const int32_t* facets, int 
     OdeSet S;
     S.model = model; S.ns = ns; S.np = np; S.n = n;
     const size_t m = (size_t)(n ? n : 1);
-    HIPCHK(c, hipMalloc((void**)&S.facet, m * sizeof(int32_t)));
-    HIPCHK(c, hipMalloc((void**)&S.states, m * ns * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&S.params, m * np * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&S.h, m * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&S.stim_mask, m));
-    HIPCHK(c, hipMemset(S.stim_mask, 0, m));
     S.fail = c->status + KNP_ODE_FAIL_SLOT;
-    HIPCHK(c, hipMemset(S.h, 0, m * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&S.stats, 4 * sizeof(unsigned long long)));
-    HIPCHK(c, hipMemset(S.stats, 0, 4 * sizeof(unsigned long long)));
-    if (n) {
-        HIPCHK(c, host_memcpy(c, S.facet, facets, n * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHK(c, host_memcpy(c, S.states, states, n * ns * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(c, host_memcpy(c, S.params, params, n * np * sizeof(double), hipMemcpyHostToDevice));
+    auto fill = [&]() -> int {
+        HIPCHK(c, hipMalloc((void**)&S.facet, m * sizeof(int32_t)));
+        HIPCHK(c, hipMalloc((void**)&S.states, m * ns * sizeof(double)));
+        HIPCHK(c, hipMalloc((void**)&S.params, m * np * sizeof(double)));
+        HIPCHK(c, hipMalloc((void**)&S.h, m * sizeof(double)));
+        HIPCHK(c, hipMalloc((void**)&S.stim_mask, m));
+        HIPCHK(c, hipMemset(S.stim_mask, 0, m));
+        HIPCHK(c, hipMemset(S.h, 0, m * sizeof(double)));
+        HIPCHK(c, hipMalloc((void**)&S.stats, 4 * sizeof(unsigned long long)));
+        HIPCHK(c, hipMemset(S.stats, 0, 4 * sizeof(unsigned long long)));
+        if (n) {
+            HIPCHK(c, host_memcpy(c, S.facet, facets, n * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIPCHK(c, host_memcpy(c, S.states, states, n * ns * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(c, host_memcpy(c, S.params, params, n * np * sizeof(double), hipMemcpyHostToDevice));
+        }
+        return 0;
+    };
+    if (const int rc = fill()) {                   // a partial set is released again: the context keeps no trace of it
+        set_free(S);
+        return rc;
     }
-    g_ode[c].push_back(S);
-    return (int)g_ode[c].size() - 1;
+    std::vector<OdeSet>& sets = ode_make(c).sets;
+    sets.push_back(S);
+    return (int)sets.size() - 1;
 }
 
 // what: 0 = states, 1 = parameters
@@ -552,14 +563,8 @@ static int rtc_register(knp_ctx* c, int model, int method, const void* code, siz
     HIPCHK(c, hipSetDevice(c->device));
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
-    HIPCHK(c, hipModuleLoadData(&mod, code));
-    const hipError_t e = hipModuleGetFunction(&fn, mod, kernel_name);
-    if (e != hipSuccess) {
-        hipModuleUnload(mod);
-        c->err = std::string("ode_register: kernel ") + kernel_name + " not in the code object: " + hipGetErrorString(e);
-        return -2;
-    }
-    auto& v = g_rtc[c];
+    if (const int rc = rtc_load_kernel(c, "ode_register", code, kernel_name, &mod, &fn)) return rc;
+    auto& v = ode_make(c).rtc;
     if (model < 0) {
         RtcModel R;
         R.ns = ns;

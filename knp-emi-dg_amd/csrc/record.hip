@@ -26,6 +26,8 @@
 // comm.hip: one all-reduce of rows x n_ch doubles on the solver's stream); knp_rec_map_read spreads the rank's map arrays to their
 // global positions in a staging buffer (k_rec_map_spread: exact zeros elsewhere, so an owner's NaN survives), sums that and copies it
 // out once.  Still no floating-point atomics: the shm transport adds in rank order, so every rank reads the same bits.
+//
+// The recorder of a context is its RecState (knp_ctx::rec): created by knp_rec_create, freed by rec_destroy, shared with no other context.
 #include "../../include/knpemi_hip.h"
 #include "knpemi_internal.hpp"
 #include <algorithm>
@@ -37,9 +39,8 @@ bool ode_state_table(knp_ctx* c, int handle, const double** states, int64_t* n, 
 #define KNP_REC_MAX_REGIONS 16
 #define KNP_REC_FINISH_BLOCK 1024
 
-namespace {
-
-struct Recorder {
+// knp_ctx::rec: the context's one recorder, created by knp_rec_create / knp_rec_create_part, freed by rec_destroy
+struct RecState {
     int64_t capacity = 0, n_ch = 0, n_points = 0, n_sets = 0, n_blk = 0;
     int n_regions = 0;
     int64_t rows_host = 0;          // samples enqueued since the last read (the device counter reaches the same number)
@@ -77,7 +78,7 @@ struct Recorder {
     double* map_stage = nullptr;    // [5][n_map_glob] t_act, t_repol, peak, t_peak, n_up as doubles
 };
 
-std::map<knp_ctx*, Recorder> g_rec;
+namespace {
 
 struct RecFields {                  // nodal fields in row order: phi, c_0 .. c_{n_sys-1}, c_elim
     const double* f[KNP_MAX_IONS + 1];
@@ -316,7 +317,7 @@ template <typename T> int rec_upload(knp_ctx* c, T** dst, const T* src, size_t n
     return 0;
 }
 
-void rec_free(Recorder& R) {
+void rec_free(RecState& R) {
     hipFree(R.point_cell); hipFree(R.point_w); hipFree(R.set_ptr); hipFree(R.set_facet); hipFree(R.set_w); hipFree(R.region);
     hipFree(R.vol); hipFree(R.inv_rvol); hipFree(R.partials); hipFree(R.buf); hipFree(R.count);
     hipFree(R.st_ptr); hipFree(R.st_src); hipFree(R.st_w);
@@ -324,10 +325,9 @@ void rec_free(Recorder& R) {
     hipFree(R.map_src); hipFree(R.map_stage);
 }
 
-Recorder* rec_find(knp_ctx* c, const char* who) {
-    auto it = g_rec.find(c);
-    if (it == g_rec.end()) { c->err = std::string(who) + ": no recorder (knp_rec_create)"; return nullptr; }
-    return &it->second;
+RecState* rec_find(knp_ctx* c, const char* who) {
+    if (!c->rec) c->err = std::string(who) + ": no recorder (knp_rec_create)";
+    return c->rec;
 }
 
 }  // namespace
@@ -335,17 +335,15 @@ Recorder* rec_find(knp_ctx* c, const char* who) {
 // checkpoint (state.hip): the row buffer with its times, the device row counter, the map accumulators and the host-side counters.  The
 // sizes carry the configuration (capacity, channels, map facets): a snapshot of another recorder does not load.  Block ids 2000 + q.
 static void rec_apply_host(knp_ctx* c, int, const char* data) {
-    auto it = g_rec.find(c);
-    if (it == g_rec.end()) return;
+    if (!c->rec) return;
     int64_t v[3];
     memcpy(v, data, sizeof(v));
-    it->second.rows_host = v[0]; it->second.map_k = v[1]; it->second.map_armed = v[2] != 0;
+    c->rec->rows_host = v[0]; c->rec->map_k = v[1]; c->rec->map_armed = v[2] != 0;
 }
 
 int rec_state_blocks(knp_ctx* c, std::vector<StateBlk>& out) {
-    auto it = g_rec.find(c);
-    if (it == g_rec.end()) return 0;
-    Recorder& R = it->second;
+    if (!c->rec) return 0;
+    RecState& R = *c->rec;
     auto push = [&](int id, int kind, int type, int ncomp, int64_t count, int64_t width, void* dev) {
         StateBlk b; b.id = id; b.kind = kind; b.type = type; b.ncomp = ncomp; b.count = count; b.width = width; b.dev = dev;
         out.push_back(b);
@@ -366,11 +364,11 @@ int rec_state_blocks(knp_ctx* c, std::vector<StateBlk>& out) {
 }
 
 void rec_destroy(knp_ctx* c) {
-    auto it = g_rec.find(c);
-    if (it == g_rec.end()) return;
+    if (!c->rec) return;
     host_stream_sync(c, c->stream);
-    rec_free(it->second);
-    g_rec.erase(it);
+    rec_free(*c->rec);
+    delete c->rec;
+    c->rec = nullptr;
 }
 
 // knp_rec_create (part = false: validation, uploads and launches as they always were) and knp_rec_create_part
@@ -434,7 +432,7 @@ static int rec_create(knp_ctx* c, int64_t capacity, int64_t n_points, const int3
     HIPCHK(c, hipSetDevice(c->device));
     rec_destroy(c);                                    // one recorder per context: a second create replaces the first
 
-    Recorder R;
+    RecState R;
     R.capacity = capacity; R.n_points = n_points; R.n_sets = n_sets; R.n_regions = n_regions; R.part = part;
     R.n_ch = n_points * (n_ions + 1) + n_sets * (1 + 2 * n_ions) + (int64_t)n_regions * (n_ions + 1);
     R.n_base = R.n_ch;
@@ -459,16 +457,16 @@ static int rec_create(knp_ctx* c, int64_t capacity, int64_t n_points, const int3
         return -2;
     }
     R.host.resize(nbuf);
-    g_rec[c] = R;
+    c->rec = new RecState(R);
     return 0;
 }
 
 static int rec_add_states(knp_ctx* c, int64_t n_channels, const int64_t* chan_ptr, const int32_t* entry_handle, const int64_t* entry_row,
                           const int32_t* entry_col, const double* entry_w, bool part) {
     if (!c) return -1;
-    Recorder* Rp = rec_find(c, "knp_rec_add_states");
+    RecState* Rp = rec_find(c, "knp_rec_add_states");
     if (!Rp) return -1;
-    Recorder& R = *Rp;
+    RecState& R = *Rp;
     if (part != R.part) { c->err = "knp_rec_add_states: the recorder was created in the other mode (knp_rec_create / knp_rec_create_part)"; return -1; }
     // ---- validation, all of it before the first upload: no entry may address anything outside its state table ------------------
     if (R.rows_host) { c->err = "knp_rec_add_states: samples are waiting (call it right after knp_rec_create)"; return -1; }
@@ -537,9 +535,9 @@ static int rec_add_states(knp_ctx* c, int64_t n_channels, const int64_t* chan_pt
 static int rec_add_map(knp_ctx* c, int64_t n_glob, int64_t n, const int32_t* facets, const int64_t* pos, double threshold, double repolarisation,
                        bool part) {
     if (!c) return -1;
-    Recorder* Rp = rec_find(c, "knp_rec_add_map");
+    RecState* Rp = rec_find(c, "knp_rec_add_map");
     if (!Rp) return -1;
-    Recorder& R = *Rp;
+    RecState& R = *Rp;
     if (part != R.part) { c->err = "knp_rec_add_map: the recorder was created in the other mode (knp_rec_create / knp_rec_create_part)"; return -1; }
     if (part ? (n_glob < 1 || n < 0 || n > n_glob || (n && (!facets || !pos))) : (n < 1 || !facets)) { c->err = "knp_rec_add_map: empty facet selection"; return -1; }
     if (n_glob > (int64_t(1) << 30)) { c->err = "knp_rec_add_map: too many facets"; return -1; }
@@ -621,9 +619,9 @@ int knp_rec_add_map_part(knp_ctx* c, int64_t n_global, int64_t n, const int32_t*
 
 int knp_rec_map_arm(knp_ctx* c, double t0) {
     if (!c) return -1;
-    Recorder* Rp = rec_find(c, "knp_rec_map_arm");
+    RecState* Rp = rec_find(c, "knp_rec_map_arm");
     if (!Rp) return -1;
-    Recorder& R = *Rp;
+    RecState& R = *Rp;
     if (!R.n_map_glob) { c->err = "knp_rec_map_arm: no map (knp_rec_add_map)"; return -1; }
     if (!std::isfinite(t0)) { c->err = "knp_rec_map_arm: the time must be finite"; return -1; }
     if (R.n_map)                                       // (partition mode: a rank may own no facet of the map)
@@ -637,9 +635,9 @@ int knp_rec_map_arm(knp_ctx* c, double t0) {
 
 int knp_rec_map_read(knp_ctx* c, int64_t n, double* t_act, double* t_repol, double* peak, double* t_peak, int32_t* n_up) {
     if (!c) return -1;
-    Recorder* Rp = rec_find(c, "knp_rec_map_read");
+    RecState* Rp = rec_find(c, "knp_rec_map_read");
     if (!Rp) return -1;
-    Recorder& R = *Rp;
+    RecState& R = *Rp;
     if (!R.n_map_glob) { c->err = "knp_rec_map_read: no map (knp_rec_add_map)"; return -1; }
     if (!R.map_armed) { c->err = "knp_rec_map_read: the map is not armed (knp_rec_map_arm)"; return -1; }
     if (n != R.n_map_glob || !t_act || !t_repol || !peak || !t_peak || !n_up) { c->err = "knp_rec_map_read: outputs must hold one entry per map facet"; return -1; }
@@ -674,9 +672,9 @@ int knp_rec_map_read(knp_ctx* c, int64_t n, double* t_act, double* t_repol, doub
 
 int knp_rec_sample(knp_ctx* c, double t) {
     if (!c) return -1;
-    auto it = g_rec.find(c);
-    if (it == g_rec.end()) { c->err = "knp_rec_sample: no recorder (knp_rec_create)"; return -1; }
-    Recorder& R = it->second;
+    RecState* Rp = rec_find(c, "knp_rec_sample");
+    if (!Rp) return -1;
+    RecState& R = *Rp;
     if (R.rows_host >= R.capacity) { c->err = "knp_rec_sample: buffer full (knp_rec_read empties it)"; return -5; }
     if (R.n_map_glob && !R.map_armed) { c->err = "knp_rec_sample: the membrane map is not armed (knp_rec_map_arm)"; return -1; }
     const MeshDev& m = c->m;
@@ -728,9 +726,9 @@ int knp_rec_sample(knp_ctx* c, double t) {
 
 int knp_rec_read(knp_ctx* c, int64_t* n_rows, double* t_out, double* rows_out) {
     if (!c || !n_rows) return -1;
-    auto it = g_rec.find(c);
-    if (it == g_rec.end()) { c->err = "knp_rec_read: no recorder (knp_rec_create)"; return -1; }
-    Recorder& R = it->second;
+    RecState* Rp = rec_find(c, "knp_rec_read");
+    if (!Rp) return -1;
+    RecState& R = *Rp;
     *n_rows = 0;
     if (R.rows_host > 0 && (!t_out || !rows_out)) { c->err = "knp_rec_read: null output"; return -1; }
     HIPCHK(c, host_stream_sync(c, c->stream));
@@ -755,8 +753,7 @@ int knp_rec_read(knp_ctx* c, int64_t* n_rows, double* t_out, double* rows_out) {
 
 int64_t knp_rec_channels(knp_ctx* c) {
     if (!c) return -1;
-    auto it = g_rec.find(c);
-    return it == g_rec.end() ? -1 : it->second.n_ch;
+    return c->rec ? c->rec->n_ch : -1;
 }
 
 int knp_rec_destroy(knp_ctx* c) {

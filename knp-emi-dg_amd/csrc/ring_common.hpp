@@ -4,7 +4,6 @@
 #pragma once
 #include "cell_geom.hpp"
 #include <algorithm>
-#include <map>
 
 namespace ring {
 
@@ -142,29 +141,19 @@ __device__ __forceinline__ int64_t list_cell(const lds_int* L, int e, int hs) {
 
 // ---- host side of the launches ----
 constexpr size_t RING_MAX_LDS = 160 * 1024;   // LDS per workgroup: the CU's 160 KB
-inline int device_cus(int device) {
-    static int ncu = 0;
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        ncu = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return ncu;
-}
-
-// more than 64 KB of dynamic LDS per workgroup has to be granted per kernel, once
-template <typename KernelT> bool grant_lds(KernelT kernel, size_t lds) {
-    static std::map<const void*, size_t> granted;
-    auto it = granted.find((const void*)kernel);
-    if (it != granted.end() && it->second >= lds) return true;
+// more than 64 KB of dynamic LDS per workgroup has to be granted per kernel and device: once per context (knp_ctx::lds_granted)
+template <typename KernelT> bool grant_lds(knp_ctx* c, KernelT kernel, size_t lds) {
+    auto it = c->lds_granted.find((const void*)kernel);
+    if (it != c->lds_granted.end() && it->second >= lds) return true;
     if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-    granted[(const void*)kernel] = lds;
+    c->lds_granted[(const void*)kernel] = lds;
     return true;
 }
 
 // one workgroup per CU (the ring takes most of a CU's LDS), a multiple of 8, not more than 8 per 8 blocks
-inline dim3 ring_grid(const MeshDev& m, int device, int reserve_cus) {
+inline dim3 ring_grid(const knp_ctx* c, const MeshDev& m, int reserve_cus) {
     const int64_t nblk = (m.c_end - 1) / RB - m.c_begin / RB + 1;
-    const int cus = std::max(device_cus(device) - std::max(reserve_cus, 0), 8);
+    const int cus = std::max(c->ncu - std::max(reserve_cus, 0), 8);
     int64_t per_xcd = std::max<int64_t>(1, std::min<int64_t>(cus / 8, (nblk + 7) / 8));
     // tests only: KNP_RING_WG = workgroups of the launch (rounded down to a multiple of 8), so that small oracle-sized meshes put many
     // blocks on a workgroup (slot reuse, list-buffer wrap, counted vmcnt with two blocks in flight: the steady state of the r=2 runs)

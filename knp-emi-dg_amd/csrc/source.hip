@@ -108,13 +108,7 @@ int knp_source_register(knp_ctx* c, int species, const void* code, size_t size, 
     }
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
-    HIPCHK(c, hipModuleLoadData(&mod, code));            // reads the ELF's own size
-    const hipError_t e = hipModuleGetFunction(&fn, mod, kernel_name);
-    if (e != hipSuccess) {
-        hipModuleUnload(mod);
-        c->err = std::string("source_register: kernel ") + kernel_name + " not in the code object: " + hipGetErrorString(e);
-        return -2;
-    }
+    if (int rc = rtc_load_kernel(c, "source_register", code, kernel_name, &mod, &fn)) return rc;
     drop_kernel(c, S.k[species]);
     S.k[species].mod = mod;
     S.k[species].fn = fn;

@@ -9,13 +9,14 @@
 // The pack kernels are plain streams: one element per thread, consecutive threads on consecutive elements of the caller-ordered
 // side (8 bytes per lane for the fp64 blocks), 64-bit indices, a guarded tail.  The permuted side is read or written in runs of one
 // cell's `width` values (32 to 400 bytes), so it moves whole cache lines too once the neighbouring lanes are counted.
+//
+// The cell permutation, the staging buffers and the timing events of a context are its CkptState (knp_ctx::ckpt), freed by state_destroy.
 #include "../../include/knpemi_hip.h"
 #include "knpemi_internal.hpp"
 #include <cstring>
 
-namespace {
-
-struct StateCtx {
+// knp_ctx::ckpt: created by the first knp_state_cell_order / knp_state_save / knp_state_load, freed by state_destroy
+struct CkptState {
     int32_t* rank = nullptr;          // device [nc]: caller's cell id -> device cell (null: identity)
     void* staging = nullptr;          // device
     void* pinned = nullptr;           // host
@@ -23,7 +24,13 @@ struct StateCtx {
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     float pack_ms = 0.f, copy_ms = 0.f;
 };
-std::map<knp_ctx*, StateCtx> g_state;
+
+namespace {
+
+CkptState& ckpt_make(knp_ctx* c) {
+    if (!c->ckpt) c->ckpt = new CkptState();
+    return *c->ckpt;
+}
 
 const unsigned char MAGIC[8] = {'K', 'N', 'P', 'S', 'T', 'A', 'T', 'E'};
 const int32_t VERSION = 1;
@@ -105,7 +112,7 @@ int refuse_ranks(knp_ctx* c, const char* who) {
     return 0;
 }
 
-int ensure_buffers(knp_ctx* c, StateCtx& S, size_t bytes) {
+int ensure_buffers(knp_ctx* c, CkptState& S, size_t bytes) {
     for (auto& e : S.ev)
         if (!e) HIPCHK(c, hipEventCreate(&e));
     if (bytes <= S.cap) return 0;
@@ -119,7 +126,7 @@ int ensure_buffers(knp_ctx* c, StateCtx& S, size_t bytes) {
     return 0;
 }
 
-void pack_all(knp_ctx* c, const Layout& L, StateCtx& S, bool save) {
+void pack_all(knp_ctx* c, const Layout& L, CkptState& S, bool save) {
     for (size_t i = 0; i < L.blocks.size(); ++i) {
         const StateBlk& b = L.blocks[i];
         if (!b.dev) continue;
@@ -132,20 +139,19 @@ void pack_all(knp_ctx* c, const Layout& L, StateCtx& S, bool save) {
 }  // namespace
 
 void state_destroy(knp_ctx* c) {
-    auto it = g_state.find(c);
-    if (it == g_state.end()) return;
-    StateCtx& S = it->second;
+    if (!c->ckpt) return;
+    CkptState& S = *c->ckpt;
     hipFree(S.rank);
     hipFree(S.staging);
     if (S.pinned) hipHostFree(S.pinned);
     for (auto e : S.ev)
         if (e) hipEventDestroy(e);
-    g_state.erase(it);
+    delete c->ckpt;
+    c->ckpt = nullptr;
 }
 
 const int32_t* state_cell_rank(knp_ctx* c) {
-    auto it = g_state.find(c);
-    return it == g_state.end() ? nullptr : it->second.rank;
+    return c->ckpt ? c->ckpt->rank : nullptr;
 }
 
 extern "C" {
@@ -153,7 +159,7 @@ extern "C" {
 int knp_state_cell_order(knp_ctx* c, const int64_t* order) {
     if (!c) return -1;
     HIPCHK(c, hipSetDevice(c->device));
-    StateCtx& S = g_state[c];
+    CkptState& S = ckpt_make(c);
     HIPCHK(c, host_stream_sync(c, c->stream));
     hipFree(S.rank);
     S.rank = nullptr;
@@ -189,7 +195,7 @@ int knp_state_save(knp_ctx* c, void* host_buf, size_t bytes) {
     Layout L;
     if ((rc = build_layout(c, L))) return rc;
     if (bytes != L.total) { c->err = "knp_state_save: the buffer must hold exactly the bytes knp_state_describe reports"; return -1; }
-    StateCtx& S = g_state[c];
+    CkptState& S = ckpt_make(c);
     if ((rc = ensure_buffers(c, S, L.dev_bytes ? L.dev_bytes : 256))) return rc;
     HIPCHK(c, hipMemsetAsync(S.staging, 0, L.dev_bytes, c->stream));          // the padding between blocks: same bytes in every snapshot
     HIPCHK(c, hipEventRecord(S.ev[0], c->stream));
@@ -247,7 +253,7 @@ int knp_state_load(knp_ctx* c, const void* host_buf, size_t bytes) {
         }
     }
     // ---- from here on the context changes ------------------------------------------------------------------------------------------
-    StateCtx& S = g_state[c];
+    CkptState& S = ckpt_make(c);
     if ((rc = ensure_buffers(c, S, L.dev_bytes ? L.dev_bytes : 256))) return rc;
     if ((rc = fields_state_prepare_load(c))) return rc;
     memcpy(S.pinned, in + L.header, L.dev_bytes);
@@ -267,9 +273,8 @@ int knp_state_load(knp_ctx* c, const void* host_buf, size_t bytes) {
 
 int knp_state_timing(knp_ctx* c, float* pack_ms, float* copy_ms) {
     if (!c || !pack_ms || !copy_ms) return -1;
-    auto it = g_state.find(c);
-    *pack_ms = it == g_state.end() ? 0.f : it->second.pack_ms;
-    *copy_ms = it == g_state.end() ? 0.f : it->second.copy_ms;
+    *pack_ms = c->ckpt ? c->ckpt->pack_ms : 0.f;
+    *copy_ms = c->ckpt ? c->ckpt->copy_ms : 0.f;
     return 0;
 }
 

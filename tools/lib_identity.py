@@ -11,9 +11,11 @@ profiles/amg_split_identity.txt)
     python tools/lib_identity.py compare out 3d_p1:1 dist0_2rank:2
 
 cases: 3d_p1, 3d_p2 (3D r=0 four-axon mesh), 2d_p1 (2D r=2), emix, 3d_p1_unshared (KNP_AMG_SHARED=0: one hierarchy per species on
-forked streams), dist0_2rank (3D r=1 P2 on two ranks over the shared-memory communicator, row-distributed level 0: start both ranks
-at once, `run dist0_2rank OUT_r<rank>.npz <rank> 2 /shm_name`; state_save() refuses a partitioned context, so c, phi and the iteration
-counts alone are compared there)."""
+forked streams), 3d_p1_live (3d_p1 with everything a context may own alive: a runtime-compiled membrane model on tag 1, a recorder
+with probes, sets, regions and state channels, a voxel grid; the recorder's rows and a frame per step are compared too),
+dist0_2rank (3D r=1 P2 on two ranks over the shared-memory communicator, row-distributed level 0: start both ranks at once,
+`run dist0_2rank OUT_r<rank>.npz <rank> 2 /shm_name`; state_save() refuses a partitioned context, so c, phi and the iteration counts
+alone are compared there)."""
 import os
 import sys
 
@@ -41,6 +43,12 @@ def run(case, out, rank=0, world=1, shm=None):
         from knpemidg.partition import make_distributed_solver
         S = make_distributed_solver(dim=3, resolution=1, rank=rank, world=world, local_rank=0, dist=None, degree=2)
         sp = solver_parameters(3, 1)
+    elif case == "3d_p1_live":
+        sys.path.insert(0, os.path.join(ROOT, "examples", "custom_membrane_model"))
+        import mm_hh_q10
+        from knpemidg.models import mm_hh_no_stim
+        S = make_solver(dim=3, resolution=0, ode_models={1: mm_hh_q10, 2: mm_hh_no_stim})
+        sp = solver_parameters(3, 0)
     elif case == "2d_p1":
         S = make_solver(dim=2, resolution=2)
         sp = solver_parameters(2, 2)
@@ -52,10 +60,27 @@ def run(case, out, rank=0, world=1, shm=None):
     S.splitting_scheme = True
     S.setup_varform_emi(); S.setup_varform_knp(); S.setup_solver_emi(); S.setup_solver_knp()
     t = Constant(0.0)
+    extra = {}
+    if case == "3d_p1_live":
+        from knpemidg import recorder as R
+        assert all(mm['ode'].on_device for mm in S.mem_models)
+        mid, tags = S.mesh.cell_midpoints(), np.asarray(S.subdomains.array())
+        mem = R.membrane_facets(S.mesh, S.surfaces.array(), [1])
+        rec = S.record(points=[mid[np.nonzero(tags == 0)[0][3]], mid[np.nonzero(tags == 1)[0][3]]], membrane_sets=[mem[:65]], regions=True,
+                       capacity=8, membrane_states=("n", "m", "h"))
+        lo, hi = S.mesh.coords.min(axis=0), S.mesh.coords.max(axis=0)
+        grid = S.record_grid(lo + 0.11 * (hi - lo), hi - 0.11 * (hi - lo), (13, 7, 5), fields=("phi", "K"))
+        frames = []
     for k in range(4):
         S.step_membrane_models(k); S.solve_for_time_step(k, t)
+        if case == "3d_p1_live":
+            f = grid.sample()
+            frames.append(np.stack([f["phi"], f["K"]]))
     S.dev.sync()
-    np.savez(out, snapshot=S.dev.state_save() if world == 1 else np.zeros(0, dtype=np.uint8),   # (state_save: one rank only)
+    if case == "3d_p1_live":
+        extra = dict(rec_t=np.asarray(rec.t), rec_rows=np.asarray(rec.rows), frames=np.stack(frames))
+        assert extra["rec_rows"].shape[0] == 4 and np.isfinite(extra["frames"]).all()
+    np.savez(out, **extra, snapshot=S.dev.state_save() if world == 1 else np.zeros(0, dtype=np.uint8),   # (state_save: one rank only)
              c=np.asarray(S.c.array()), phi=np.asarray(S.phi.array()),
              emi=np.asarray(S.emi_niter, dtype=np.int64).ravel(), knp=np.asarray(S.knp_niter, dtype=np.int64).ravel())
     print("case %s rank %d lib %s done: emi %s knp %s" % (case, rank, os.environ.get("KNP_LIB_PATH", "in-tree"), list(S.emi_niter), [list(n) for n in S.knp_niter]), flush=True)
@@ -78,13 +103,16 @@ def compare(d, specs):
                 return {"c": np.array_equal(L[a]["c"], L[b]["c"]), "phi": np.array_equal(L[a]["phi"], L[b]["phi"]),
                         "emi": np.array_equal(L[a]["emi"], L[b]["emi"]), "knp": np.array_equal(L[a]["knp"], L[b]["knp"]),
                         "blocks": [np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(blocks[a], blocks[b])],
-                        "table": tab[a].tobytes() == tab[b].tobytes(), "bytes": np.array_equal(L[a]["snapshot"], L[b]["snapshot"])}
+                        "table": tab[a].tobytes() == tab[b].tobytes(), "bytes": np.array_equal(L[a]["snapshot"], L[b]["snapshot"]),
+                        "extra": all(np.array_equal(L[a][k], L[b][k]) for k in ("rec_t", "rec_rows", "frames") if k in L[a].files)}
             pp, pn = same("parent", "parent2"), same("parent", "new")
-            yard = all(pp[k] for k in ("c", "phi", "emi", "knp", "table", "bytes")) and all(pp["blocks"])
+            yard = all(pp[k] for k in ("c", "phi", "emi", "knp", "table", "bytes", "extra")) and all(pp["blocks"])
             line = "%-15s rank %d  parent==parent' %s | new==parent: c %s phi %s, %d of %d snapshot blocks equal (whole snapshot %s, %d bytes), iteration counts emi %s knp %s (emi %s knp %s)" % (
                 case, r, yard, pn["c"], pn["phi"], sum(pn["blocks"]), len(pn["blocks"]), pn["bytes"], L["new"]["snapshot"].size, pn["emi"], pn["knp"],
                 L["new"]["emi"].tolist(), L["new"]["knp"].tolist())
-            ok = all(pn[k] for k in ("c", "phi", "emi", "knp", "table", "bytes")) and all(pn["blocks"])
+            ok = all(pn[k] for k in ("c", "phi", "emi", "knp", "table", "bytes", "extra")) and all(pn["blocks"])
+            if "frames" in L["new"].files:
+                line += ", recorder rows and grid frames %s" % pn["extra"]
             if not yard:                                    # fall-back: within four times the parent's own run-to-run difference
                 ok = True
                 for f in ("c", "phi"):
