@@ -162,7 +162,23 @@ enum knp_debug_table_id {
     KNP_DT_HB_SRC = 5,  /* int32  [nblk][hs]   halo- / ring-staged applies: per 256-cell block, 4 * cell + local facet of every
                                                coupled (SIPG or membrane) neighbour outside the block, in (cell, facet) order, -1 padded (0 bytes if unused) */
     KNP_DT_HB_LOC = 6,  /* uint16 [nc_owned][4] LDS entry of the neighbour behind facet i: < 256 in-block, else 256 + list position */
-    KNP_DT_META = 7     /* int64  [8]          nc, nc_owned, nf, nmf, hb_stride, hb_long0, n_interior, dim                     */
+    KNP_DT_META = 7,    /* int64  [8]          nc, nc_owned, nf, nmf, hb_stride, hb_long0, n_interior, dim                     */
+    /* The per-block tables of the unstructured ring-staged applies (3D P1 meshes without geometry classes, csrc/apply_ring_u.hip).
+     * Asking for one builds them as the first apply would; every one has 0 bytes when the context has no usable unstructured ring
+     * (classes present, first block over a limit, KNP_APPLY_RING_U=0, ...).  nblk = ceil(nc_owned / 256).  Blocks [0, long0) fit the
+     * staging limits (320 list entries, 256 vertices); rows of later blocks and of their cells are unspecified. */
+    KNP_DT_RU_META = 8,   /* int64  [4]          long0, hs (longest list of a covered block, at least 1), nblk, covered cells
+                                                 min(long0 * 256, nc_owned): what apply variant 10 runs, the rest goes to the tail kernel */
+    KNP_DT_RU_HB_SRC = 9, /* int32  [nblk][320]  per block, 4 * cell + the neighbour's local facet of every coupled (SIPG or membrane)
+                                                 neighbour that is outside the block OR not owned, in (cell, facet) order, -1 padded   */
+    KNP_DT_RU_HB_LOC = 10,/* uint16 [nc_owned][4] LDS entry of the neighbour behind facet i: < 256 in-block, else 256 + list position
+                                                 (0 where the facet couples nothing)                                                  */
+    KNP_DT_RU_VB_SRC = 11,/* int32  [nblk][256]  per block, the vertex (storage) ids it stages: the vertices of its cells in (cell,
+                                                 local vertex) order of first appearance, then the apex vertices of the coupled
+                                                 neighbours (in-block ones included) in (cell, facet) order; 0 padded                  */
+    KNP_DT_RU_VLOC = 12,  /* uint8  [nc_owned][8] positions in the block's vertex list: the cell's own vertices (0..3) and the apex
+                                                 vertex of the neighbour behind facet i (4 + i; 0 where the facet couples nothing)     */
+    KNP_DT_RU_HINV4 = 13  /* double [nc_owned][4] 2 / (h + h') of the cell and the neighbour behind facet i (0 where it couples nothing) */
 };
 int64_t knp_debug_table_size(knp_ctx* ctx, int which);
 int knp_debug_table(knp_ctx* ctx, int which, void* out, int64_t nbytes);

@@ -401,6 +401,7 @@ static size_t ring_u_lds(const knp_ctx* c, int which) {
 // usable); KNP_APPLY_RING_U=0 selects the thread-per-cell coordinate kernels (A/B runs).  Builds the tables at the first call.
 int64_t ring_u_cells(knp_ctx* c, int which) {
     if (c->degree != 1 || c->m.dim != 3 || c->m.cls || c->m.nc_owned < RB || c->m.nv >= (int64_t(1) << 31)) return 0;
+    if (c->m.nc >= (int64_t(1) << 29)) return 0;                       // hb_src holds 4 * cell + facet as int32 (as the structured lists: upload_halo_lists)
     if (env_int("KNP_APPLY_RING_U", 1) == 0 || env_int("KNP_APPLY_RING", 1) == 0) return 0;
     if (which == 1 && !(c->nmat > 0 && c->p.n_sys <= 2 && env_int("KNP_APPLY_MAT", 1) != 0)) return 0;
     if (ring_u_lds(c, which) > RING_MAX_LDS) return 0;
@@ -410,6 +411,28 @@ int64_t ring_u_cells(knp_ctx* c, int which) {
     }
     const RingUState& S = *c->ring_u;
     return S.usable ? std::min<int64_t>(S.T.long0 * RB, c->m.nc_owned) : 0;
+}
+
+// knp_debug_table (context.hip): table `which` (KNP_DT_RU_*) of the unstructured ring as a device pointer and its size in bytes; the
+// meta table goes to meta[4] instead.  Asks ring_u_cells for the EMI operator first, so the tables are built as the first apply would
+// build them; 0 bytes when the context has no usable unstructured ring.
+int64_t ring_u_debug_table(knp_ctx* c, int which, const void** p, int64_t meta[4]) {
+    *p = nullptr;
+    ring_u_cells(c, 0);
+    if (!c->ring_u || !c->ring_u->usable) return 0;
+    const RingUTables& T = c->ring_u->T;
+    const int64_t no = c->m.nc_owned, nblk = (no + RB - 1) / RB;
+    switch (which) {
+        case KNP_DT_RU_META:
+            if (meta) { meta[0] = T.long0; meta[1] = T.hs; meta[2] = nblk; meta[3] = std::min<int64_t>(T.long0 * RB, no); }
+            return 4 * 8;
+        case KNP_DT_RU_HB_SRC: *p = T.hb_src; return nblk * UH * 4;
+        case KNP_DT_RU_HB_LOC: *p = T.hb_loc; return no * 4 * 2;
+        case KNP_DT_RU_VB_SRC: *p = T.vb_src; return nblk * UV * 4;
+        case KNP_DT_RU_VLOC: *p = T.vloc; return no * 8;
+        case KNP_DT_RU_HINV4: *p = T.hinv4; return no * 4 * 8;
+        default: return -1;
+    }
 }
 
 int ring_u_emi_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* kappa, double* y, int reserve_cus) {

@@ -364,6 +364,8 @@ static int64_t debug_table_ptr(knp_ctx* c, int which, const void** p) {
         case KNP_DT_HB_SRC: *p = m.hb_src; return m.hb_src ? nblk * m.hb_stride * 4 : 0;
         case KNP_DT_HB_LOC: *p = m.hb_loc; return m.hb_loc ? m.nc_owned * 4 * 2 : 0;
         case KNP_DT_META: *p = nullptr; return 8 * 8;
+        case KNP_DT_RU_META: case KNP_DT_RU_HB_SRC: case KNP_DT_RU_HB_LOC: case KNP_DT_RU_VB_SRC: case KNP_DT_RU_VLOC: case KNP_DT_RU_HINV4:
+            return ring_u_debug_table(c, which, p, nullptr);
         default: return -1;
     }
 }
@@ -379,6 +381,12 @@ int knp_debug_table(knp_ctx* c, int which, void* out, int64_t nbytes) {
     if (which == KNP_DT_META) {
         const int64_t meta[8] = {c->m.nc, c->m.nc_owned, c->m.nf, c->m.nmf, c->m.hb_stride, c->m.hb_long0, c->m.n_interior, c->m.dim};
         memcpy(out, meta, sizeof(meta));
+        return 0;
+    }
+    if (which == KNP_DT_RU_META) {
+        int64_t meta[4] = {0, 0, 0, 0};
+        if (n) ring_u_debug_table(c, which, &p, meta);
+        if (n) memcpy(out, meta, sizeof(meta));
         return 0;
     }
     if (n) HIPCHK(c, host_memcpy(c, out, p, (size_t)n, hipMemcpyDeviceToHost));

@@ -365,6 +365,7 @@ bool ring_usable(const knp_ctx* c, int which);       // which: 0 EMI, 1 KNP
 // apply_ring_u.hip: the ring-staged applies for 3D P1 meshes WITHOUT geometry classes (geometry from staged vertex coordinates)
 int64_t ring_u_cells(knp_ctx* c, int which);         // leading owned cells the unstructured ring covers (0: not usable); builds its tables once
 void ring_u_free(knp_ctx* c);
+int64_t ring_u_debug_table(knp_ctx* c, int which, const void** p, int64_t meta[4]);   // KNP_DT_RU_*: bytes (0: no usable ring), device pointer or meta
 int ring_u_emi_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* kappa, double* y, int reserve_cus);
 int ring_u_knp_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* gphi, double* y, const KnpArgs& ka, int reserve_cus);
 int ring_emi_apply(knp_ctx* c, const MeshDev& m, const double* x, const double* kappa, double* y, int reserve_cus);

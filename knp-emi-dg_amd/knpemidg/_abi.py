@@ -21,6 +21,7 @@ FACET_TMP_SLOTS = 4        # KNP_FACET_TMP_SLOTS (include/knpemi_hip.h)
 GD_EFIELD, GD_FLUX, GD_FLUX_DIFFUSIVE, GD_CURRENT = range(4)
 # knp_debug_table_id (include/knpemi_hip.h)
 DT_CELLS, DT_NBR, DT_FLAG, DT_CFACET, DT_MF, DT_HB_SRC, DT_HB_LOC, DT_META = range(8)
+DT_RU_META, DT_RU_HB_SRC, DT_RU_HB_LOC, DT_RU_VB_SRC, DT_RU_VLOC, DT_RU_HINV4 = range(8, 14)      # the unstructured ring's tables
 
 _f64p = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
@@ -417,6 +418,51 @@ def _geometry_classes_native(mesh, order, nb, nj, max_classes, tol):
     return np.ascontiguousarray(cls[order].astype(np.uint16)), np.ascontiguousarray(_class_table(mesh, first, nb, nj))
 
 
+def _device_cell_order(mesh, n_own, reorder):
+    """device_cell_order, and the per-axis cell extent the curve was scaled with (None without reordering): the vertex storage order
+    of Device follows the same curve."""
+    nc = mesh.cells.shape[0]
+    # device cell numbering: owned cells along a Morton curve, ghosts keep their (peer-grouped) places
+    order = np.arange(nc, dtype=np.int64)
+    scale = None
+    n_interior = n_own
+    if reorder and nc:
+        native = nc >= 50000 and mesh.gdim <= 3 and os.environ.get("KNP_SETUP_NATIVE_MORTON", "1") != "0"
+        co = o = None
+        if native:
+            # median cell extent and the curve over the cell midpoints in the library (same numbers, same order): 0.43 -> 0.05 s at 10^6 tets
+            co = np.ascontiguousarray(mesh.coords, dtype=np.float64)
+            cl = np.ascontiguousarray(mesh.cells, dtype=np.int32)
+            scale = np.empty(mesh.gdim)
+            if load().knp_host_cell_extent_median(nc, cl.shape[1], mesh.gdim, _p(co, _f64p), _p(cl, _i32p), _p(scale, _f64p)) == 0:
+                scale = np.maximum(scale, 1e-300)
+                o = _morton_native(co, cl[:n_own], scale)
+        if o is None:
+            xc = mesh.coords[mesh.cells]
+            scale = np.maximum(np.median(xc.max(axis=1) - xc.min(axis=1), axis=0), 1e-300)
+            o = morton_order(mesh.cell_midpoints()[:n_own], scale)
+        order[:n_own] = o
+        if n_own < nc:
+            # a partition: owned cells without a ghost neighbour first (their part of an apply runs while the halo
+            # exchange is in flight), the cells on the cut after them; both groups along the Morton curve
+            fcs = np.asarray(mesh.facet_cells)
+            cut = fcs[(fcs[:, 1] >= 0) & ((fcs[:, 0] >= n_own) != (fcs[:, 1] >= n_own))]
+            on_cut = np.zeros(nc, dtype=bool)
+            on_cut[cut.ravel()] = True
+            o = order[:n_own]
+            order[:n_own] = np.concatenate([o[~on_cut[o]], o[on_cut[o]]])
+            n_interior = int((~on_cut[:n_own]).sum())
+    return order, n_interior, scale
+
+
+def device_cell_order(mesh, n_own, reorder):
+    """(order, n_interior) of a context over `mesh` whose first n_own cells are owned: order[d] = the caller's cell behind device cell
+    d -- the owned cells along a Morton curve of their midpoints, on a partition those without a ghost neighbour first (n_interior of
+    them) and the cells on the cut after them; ghosts keep their places.  reorder False (KNP_NO_REORDER=1): the caller's order.  What
+    Device numbers its cells by; needs no device."""
+    return _device_cell_order(mesh, int(n_own), reorder)[:2]
+
+
 class Device:
     """One context = one GPU = one partition of the mesh."""
 
@@ -429,36 +475,7 @@ class Device:
         n_own = nc if nc_owned is None else int(nc_owned)
         if reorder is None:
             reorder = os.environ.get("KNP_NO_REORDER", "0") != "1"
-        # device cell numbering: owned cells along a Morton curve, ghosts keep their (peer-grouped) places
-        order = np.arange(nc, dtype=np.int64)
-        scale = None
-        self.n_interior = n_own
-        if reorder and nc:
-            native = nc >= 50000 and mesh.gdim <= 3 and os.environ.get("KNP_SETUP_NATIVE_MORTON", "1") != "0"
-            co = o = None
-            if native:
-                # median cell extent and the curve over the cell midpoints in the library (same numbers, same order): 0.43 -> 0.05 s at 10^6 tets
-                co = np.ascontiguousarray(mesh.coords, dtype=np.float64)
-                cl = np.ascontiguousarray(mesh.cells, dtype=np.int32)
-                scale = np.empty(mesh.gdim)
-                if self.lib.knp_host_cell_extent_median(nc, cl.shape[1], mesh.gdim, _p(co, _f64p), _p(cl, _i32p), _p(scale, _f64p)) == 0:
-                    scale = np.maximum(scale, 1e-300)
-                    o = _morton_native(co, cl[:n_own], scale)
-            if o is None:
-                xc = mesh.coords[mesh.cells]
-                scale = np.maximum(np.median(xc.max(axis=1) - xc.min(axis=1), axis=0), 1e-300)
-                o = morton_order(mesh.cell_midpoints()[:n_own], scale)
-            order[:n_own] = o
-            if n_own < nc:
-                # a partition: owned cells without a ghost neighbour first (their part of an apply runs while the halo
-                # exchange is in flight), the cells on the cut after them; both groups along the Morton curve
-                fcs = np.asarray(mesh.facet_cells)
-                cut = fcs[(fcs[:, 1] >= 0) & ((fcs[:, 0] >= n_own) != (fcs[:, 1] >= n_own))]
-                on_cut = np.zeros(nc, dtype=bool)
-                on_cut[cut.ravel()] = True
-                o = order[:n_own]
-                order[:n_own] = np.concatenate([o[~on_cut[o]], o[on_cut[o]]])
-                self.n_interior = int((~on_cut[:n_own]).sum())
+        order, self.n_interior, scale = _device_cell_order(mesh, n_own, reorder)
         rank = np.empty(nc, dtype=np.int64)
         rank[order] = np.arange(nc)
         self.cell_order, self.cell_rank = order, rank            # device -> caller, caller -> device
@@ -641,7 +658,8 @@ class Device:
             out = np.ascontiguousarray(out.reshape(nb, self.nc, self.nd)[:, self.cell_rank]).ravel()
         return out
 
-    _DT_DTYPE = {0: np.int32, 1: np.int32, 2: np.uint32, 3: np.int32, 4: np.int32, 5: np.int32, 6: np.uint16, 7: np.int64}
+    _DT_DTYPE = {0: np.int32, 1: np.int32, 2: np.uint32, 3: np.int32, 4: np.int32, 5: np.int32, 6: np.uint16, 7: np.int64,
+                 8: np.int64, 9: np.int32, 10: np.uint16, 11: np.int32, 12: np.uint8, 13: np.float64}
 
     def debug_table(self, which):
         """Connectivity table `which` (include/knpemi_hip.h: knp_debug_table_id) as the library derived it, flat, in DEVICE cell

@@ -119,6 +119,114 @@ def test_device_connectivity_tables_bit_exact(hip_lib, which):
     dev.close()
 
 
+def _expected_ring_u_tables(cells_d, nbr_d, nloc_d, kind_d, nc_owned, nblk_built, B=256, UH=320, UV=256):
+    """Layout contract of KNP_DT_RU_* (include/knpemi_hip.h), restated for the first nblk_built blocks: per block the vertex list (own
+    vertices of all its cells first, in (cell, local vertex) order of first appearance, then the apexes of the coupled neighbours in
+    (cell, facet) order) and the list of coupled neighbours outside the block or not owned."""
+    n = min(nblk_built * B, nc_owned)
+    hb_src = np.full((nblk_built, UH), -1, dtype=np.int32)
+    vb_src = np.zeros((nblk_built, UV), dtype=np.int32)
+    hb_loc = np.zeros((n, 4), dtype=np.uint16)
+    vloc = np.zeros((n, 8), dtype=np.uint8)
+    coupled = np.zeros((n, 4), dtype=bool)
+    nlist, nvert = [], []
+    for b in range(nblk_built):
+        pos, L = {}, []
+        k0, k1 = b * B, min(nc_owned, (b + 1) * B)
+        for k in range(k0, k1):
+            for a in range(4):
+                vloc[k, a] = pos.setdefault(int(cells_d[k, a]), len(pos))
+        for k in range(k0, k1):
+            for a in range(4):
+                q = int(nbr_d[k, a])
+                if kind_d[k, a] not in (oc.K_SIPG, oc.K_MEMBRANE) or q < 0:
+                    continue
+                coupled[k, a] = True
+                j = int(nloc_d[k, a])
+                vloc[k, 4 + a] = pos.setdefault(int(cells_d[q, j]), len(pos))
+                if q // B == b and q < nc_owned:
+                    hb_loc[k, a] = q - k0
+                else:
+                    hb_loc[k, a] = B + len(L)
+                    L.append(4 * q + j)
+        assert len(L) <= UH and len(pos) <= UV
+        hb_src[b, :len(L)] = L
+        vb_src[b, :len(pos)] = list(pos)
+        nlist.append(len(L))
+        nvert.append(len(pos))
+    return hb_src, hb_loc, vb_src, vloc, coupled, np.array(nlist), np.array(nvert)
+
+
+@pytest.mark.parametrize("which", ["emix", "C", "D1", "D6", "E_lists", "E_verts", "slab_of_12x4x4"])
+def test_unstructured_ring_tables_bit_exact(hip_lib, monkeypatch, which):
+    """The per-block tables of the unstructured ring-staged applies (csrc/apply_ring_u.hip: build_tables_u) entry for entry against
+    the restated layout, their block counts against `block_stats` of tests/apply_split_cases.py -- which restates the builder from the
+    MESH alone and is what the CPU test of the cases stands on -- and 2 / (h + h') against the oracle's cell diameters.  On the tissue
+    mesh (every block fits) and on the cases with lists in the second DMA piece (C: 298 / 292 entries, LDS entries >= 512), a head that
+    stops in front of an overflowing block (D1, D6), blocks exactly at and one past a limit (E_lists: 320 / 321 entries, E_verts:
+    256 / 257 vertices) and an owned + ghost context whose ghosts fall into the id range of the last block (the `nbk < no` clause)."""
+    import apply_split_cases as ac
+    import knpemi_oracle as ko
+    no = None
+    if which == "emix":
+        mesh, sub, surf, mtags = _mesh("emix")
+        exp_meta = None
+    elif which == "slab_of_12x4x4":
+        lm, sub, surf = ac.partition_rank((12, 4, 4), "J", 0)[:3]
+        mesh, mtags, no, exp_meta = lm.mesh, (1,), lm.nc_owned, None
+    else:
+        m, s, f = ac.base_mesh("J")
+        mesh, sub, surf = ac.permuted_mesh(m, s, f, ac.case_order(which, m))
+        mtags = (1,)
+        monkeypatch.setenv("KNP_NO_REORDER", "1")
+        exp_meta = ac.EXPECT[("J", which)][0]
+    ctags, ftags = sub.array(), surf.array()
+    dev = A.Device(mesh, ctags, ftags, mtags, 3, nc_owned=no)
+    try:
+        nc = mesh.num_cells()
+        no = nc if no is None else no
+        nblk = (no + 255) // 256
+        order = dev.cell_order
+        st = ac.block_stats(mesh, order, no, ftags, mtags)
+        long0, hs = ac.expected_unstructured(st)
+        assert exp_meta is None or (long0, hs) == exp_meta
+        if which == "emix":
+            assert long0 == nblk                                      # the tissue reconstruction in Morton order: every block fits
+        if which == "slab_of_12x4x4":                                 # ghosts in the id range of the last block are staged through its list
+            assert long0 == nblk == 3 and no == 576 < nc and st["lists_u"][2] > st["lists_s"][2]
+        covered = min(long0 * 256, no)
+        assert dev.n_geometry_classes == 0 and dev.apply_variant(0) == 10
+        assert dev.debug_table(A.DT_RU_META).tolist() == [long0, hs, nblk, covered]
+        nbr_d = dev.debug_table(A.DT_NBR).reshape(nc, 4).astype(np.int64)
+        flag = dev.debug_table(A.DT_FLAG)
+        fb = ((flag[:, None] >> (8 * np.arange(4, dtype=np.uint32))[None, :]) & 0xFF).astype(np.int64)
+        cells_d = dev.debug_table(A.DT_CELLS).reshape(nc, 4)
+        e_src, e_loc, e_vsrc, e_vloc, coupled, nlist, nvert = _expected_ring_u_tables(cells_d, nbr_d, fb & 3, (fb >> 2) & 3, no, long0)
+        assert np.array_equal(nlist, st["lists_u"][:long0]) and np.array_equal(nvert, st["verts"][:long0])
+        if long0 < nblk:
+            assert st["lists_u"][long0] > 320 or st["verts"][long0] > 256
+        src = dev.debug_table(A.DT_RU_HB_SRC).reshape(nblk, 320)
+        loc = dev.debug_table(A.DT_RU_HB_LOC).reshape(no, 4)
+        vsrc = dev.debug_table(A.DT_RU_VB_SRC).reshape(nblk, 256)
+        vloc = dev.debug_table(A.DT_RU_VLOC).reshape(no, 8)
+        hinv = dev.debug_table(A.DT_RU_HINV4).reshape(no, 4)
+        assert np.array_equal(src[:long0], e_src) and np.array_equal(loc[:covered], e_loc)
+        assert np.array_equal(vsrc[:long0], e_vsrc) and np.array_equal(vloc[:covered], e_vloc)
+        if which == "C":
+            assert sorted(np.nonzero(nlist > 256)[0].tolist()) == [5, 6] and (e_loc >= 512).any()
+        if which == "E_verts":
+            assert nvert[3] == 256 and (e_vloc[3 * 256:4 * 256] == 255).any()
+        if which == "slab_of_12x4x4":                                 # a ghost behind an owned cell of the last block: a list entry, not an in-block one
+            q = nbr_d[512:no]
+            ghost = coupled[512:no] & (q >= no) & (q // 256 == 2)
+            assert ghost.any() and (e_loc[512:no][ghost] >= 256).all()
+        h = ko.Geometry(mesh).h[order]
+        e_hinv = np.where(coupled, 2.0 / (h[:covered, None] + h[np.maximum(nbr_d[:covered], 0)]), 0.0)
+        assert (np.abs(hinv[:covered] - e_hinv) <= 1e-15 * e_hinv).all()
+    finally:
+        dev.close()
+
+
 def test_dof_layout_upload_download_bit_exact(hip_lib):
     """DoF layout: dof(c, a) = c * nd + a in the caller's numbering on both sides of the boundary, species-major
     for the KNP fields; the device's Morton order is invisible: what is uploaded comes back bit for bit, and a cell-indexed
