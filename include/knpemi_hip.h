@@ -115,6 +115,22 @@ int knp_source_clear(knp_ctx* ctx, int species);
 int64_t knp_source_cells(knp_ctx* ctx);
 int knp_source_download(knp_ctx* ctx, double* out);
 
+/* Ion sources that read the solution, on any subdomain (knpemidg.FieldExpression): as knp_source_register, with two additions.
+ *  - field_ids[n_fields], distinct, 0 <= n_fields <= 9: 0 is phi, 1 + i is ion i of the ion list -- i < n_sys is row i of
+ *    KNP_F_C_PREV, i == n_sys is KNP_F_C_ELIM (the convention of knp_grid_create).  The kernel's functor receives their values at
+ *    the quadrature point, u(x_q) = sum_a U[a] B[q][a], in this order.  The pointers are looked up at every knp_source_eval, so
+ *    an evaluation in front of a KNP solve sees the concentrations of the previous time level (the same in every Picard iteration
+ *    of a step) and the phi of the EMI solve just done.
+ *  - tags[n_tags], n_tags >= 1: the kernel integrates over its OWN cell list, the cells of the context (owned and ghost, ascending
+ *    device order) whose tag is one of them.  No such cell: the row stays zero and an evaluation launches nothing.  The shared ECS
+ *    list of knp_source_register and knp_source_cells are untouched by this call.
+ * Registering over an existing source of the species, of either kind, first zeroes the species' row on the stream: cells that
+ * left the selection hold exact zeros.  knp_source_eval / _clear serve both kinds; knp_source_clear and knp_ctx_destroy free the
+ * kernel's list.  -1 for everything knp_source_register refuses, for a field id outside [0, n_ions] or listed twice, for n_fields
+ * above 9 and for n_tags < 1. */
+int knp_source_register_fields(knp_ctx* ctx, int species, const void* code, size_t size, const char* kernel_name, int n_params,
+                               int n_fields, const int* field_ids, int n_tags, const int* tags);
+
 /* DG-p path (degree 2): reference-basis tabulation of one integral class.  The operator applies are matrix-free and need
  * no tabulation (csrc/apply_p2.hip); the right-hand sides, facet averages and Nernst projections of step III (the device
  * analogue of assemble(L_emi / L_knp), solver.py:477-479, 730-731, and of pcws_constant_project, utils.py:100-124) are

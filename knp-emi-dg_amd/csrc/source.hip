@@ -2,6 +2,9 @@
 // around the user's expression -- registered per species and launched before every KNP solve.  An evaluation writes the load vector
 // int f v dx(0) of the context's ECS cells (tag 0, owned and ghost) into the species' row of knp_ctx::extra_knp, the buffer the
 // right-hand-side kernels already add to L_knp: one launch on the context's stream, the parameters by value, no copy and no wait.
+// A knpemidg.FieldExpression (knp_source_register_fields) is the same with two additions: the kernel carries its own cell list (the
+// cells whose tag is one of the registered subdomains) and reads phi and level-n concentrations through pointers that are looked
+// up at every evaluation and passed by value as well.
 #include "../../include/knpemi_hip.h"
 #include "knpemi_internal.hpp"
 #include "source_rtc.hpp"
@@ -11,6 +14,11 @@ struct SourceKernel {
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
     int n_params = 0;
+    // knp_source_register_fields only: the kernel's own cell list and the fields it reads
+    int n_fields = -1;             // -1: a plain source over the shared ECS list below
+    int field_ids[KNP_SOURCE_MAX_FIELDS] = {0};      // 0: phi, 1 + i: ion i of the ion list (the eliminated one last)
+    int32_t* sel = nullptr;        // [nsel] cells whose tag is one of the registered ones, device order
+    int64_t nsel = 0;
 };
 
 // knp_ctx::src: owned by the context, so two contexts driven from two host threads share nothing here
@@ -43,7 +51,33 @@ void drop_kernel(knp_ctx* c, SourceKernel& K) {
     if (!K.mod) return;
     host_stream_sync(c, c->stream);
     hipModuleUnload(K.mod);
+    hipFree(K.sel);
     K = SourceKernel();
+}
+
+// a registration over an existing source of the species: the old kernel may have written cells the new one never visits (other
+// subdomains), so its row is zeroed on the stream first; then the kernel goes
+int replace_kernel(knp_ctx* c, SourceKernel& K, int species) {
+    if (!K.fn) return 0;
+    if (c->extra_knp && c->p.splitting != 2)
+        HIPCHK(c, hipMemsetAsync(c->extra_knp + (size_t)species * (size_t)row_len(c), 0, sizeof(double) * (size_t)row_len(c), c->stream));
+    drop_kernel(c, K);
+    return 0;
+}
+
+int ensure_buffer(knp_ctx* c) {
+    if (c->extra_knp) return 0;
+    const size_t bytes = sizeof(double) * (size_t)c->p.n_sys * (size_t)row_len(c);
+    HIPCHK(c, hipMalloc((void**)&c->extra_knp, std::max<size_t>(bytes, 8)));
+    HIPCHK(c, hipMemset(c->extra_knp, 0, std::max<size_t>(bytes, 8)));
+    return 0;
+}
+
+// device copy of a host cell list (at least one element allocated, so that an empty list still owns a pointer)
+int upload_cells(knp_ctx* c, const std::vector<int32_t>& sel, int32_t** out) {
+    HIPCHK(c, hipMalloc((void**)out, std::max<size_t>(sel.size(), 1) * sizeof(int32_t)));
+    if (!sel.empty()) HIPCHK(c, host_memcpy(c, *out, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    return 0;
 }
 
 }  // namespace
@@ -97,22 +131,58 @@ int knp_source_register(knp_ctx* c, int species, const void* code, size_t size, 
         std::vector<int32_t> sel;
         for (int64_t k = 0; k < c->m.nc; ++k)
             if (c->h_ctag[(size_t)k] == 0u) sel.push_back((int32_t)k);
-        HIPCHK(c, hipMalloc((void**)&S.sel, std::max<size_t>(sel.size(), 1) * sizeof(int32_t)));
-        if (!sel.empty()) HIPCHK(c, host_memcpy(c, S.sel, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (int rc = upload_cells(c, sel, &S.sel)) return rc;
         S.nsel = (int64_t)sel.size();
     }
-    if (!c->extra_knp) {
-        const size_t bytes = sizeof(double) * (size_t)c->p.n_sys * (size_t)row_len(c);
-        HIPCHK(c, hipMalloc((void**)&c->extra_knp, std::max<size_t>(bytes, 8)));
-        HIPCHK(c, hipMemset(c->extra_knp, 0, std::max<size_t>(bytes, 8)));
-    }
+    if (int rc = ensure_buffer(c)) return rc;
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
     if (int rc = rtc_load_kernel(c, "source_register", code, kernel_name, &mod, &fn)) return rc;
-    drop_kernel(c, S.k[species]);
+    if (int rc = replace_kernel(c, S.k[species], species)) { hipModuleUnload(mod); return rc; }
     S.k[species].mod = mod;
     S.k[species].fn = fn;
     S.k[species].n_params = n_params;
+    return 0;
+}
+
+int knp_source_register_fields(knp_ctx* c, int species, const void* code, size_t size, const char* kernel_name, int n_params, int n_fields,
+                               const int* field_ids, int n_tags, const int* tags) {
+    if (!c) return -1;
+    if (c->p.splitting == 2) { c->err = "source_register_fields: the manufactured-solution mode sets its own data terms"; return -1; }
+    if (species < 0 || species >= c->p.n_sys) { c->err = "source_register_fields: species outside [0, n_sys)"; return -1; }
+    if (n_params < 0 || n_params > KNP_SOURCE_MAX_PARAMS) { c->err = "source_register_fields: 0..32 parameters"; return -1; }
+    if (!code || !size || !kernel_name) { c->err = "source_register_fields: no code object / kernel name"; return -1; }
+    static_assert(KNP_SOURCE_MAX_FIELDS == KNP_MAX_IONS + 1, "phi and every ion");
+    if (n_fields < 0 || n_fields > KNP_SOURCE_MAX_FIELDS || (n_fields > 0 && !field_ids)) { c->err = "source_register_fields: 0..9 fields (phi and at most 8 ions)"; return -1; }
+    for (int i = 0; i < n_fields; ++i) {
+        if (field_ids[i] < 0 || field_ids[i] > c->p.n_ions) { c->err = "source_register_fields: field id outside [0, n_ions] (0: phi, 1 + i: ion i)"; return -1; }
+        for (int j = 0; j < i; ++j)
+            if (field_ids[j] == field_ids[i]) { c->err = "source_register_fields: a field id is listed twice"; return -1; }
+    }
+    if (n_tags < 1 || !tags) { c->err = "source_register_fields: at least one subdomain tag"; return -1; }
+    SourceState& S = state_make(c);
+    if (!S.nq) { c->err = "source_register_fields: no quadrature rule yet (knp_source_set_rule)"; return -1; }
+    HIPCHK(c, hipSetDevice(c->device));
+    // every cell of the context, owned and ghost, whose tag is one of `tags`: ascending device order
+    std::vector<int32_t> sel;
+    for (int64_t k = 0; k < c->m.nc; ++k)
+        for (int t = 0; t < n_tags; ++t)
+            if (tags[t] >= 0 && c->h_ctag[(size_t)k] == (uint32_t)tags[t]) { sel.push_back((int32_t)k); break; }
+    if (int rc = ensure_buffer(c)) return rc;
+    hipModule_t mod = nullptr;
+    hipFunction_t fn = nullptr;
+    if (int rc = rtc_load_kernel(c, "source_register_fields", code, kernel_name, &mod, &fn)) return rc;
+    int32_t* dsel = nullptr;
+    if (int rc = upload_cells(c, sel, &dsel)) { hipModuleUnload(mod); hipFree(dsel); return rc; }
+    if (int rc = replace_kernel(c, S.k[species], species)) { hipModuleUnload(mod); hipFree(dsel); return rc; }
+    SourceKernel& K = S.k[species];
+    K.mod = mod;
+    K.fn = fn;
+    K.n_params = n_params;
+    K.n_fields = n_fields;
+    for (int i = 0; i < n_fields; ++i) K.field_ids[i] = field_ids[i];
+    K.sel = dsel;
+    K.nsel = (int64_t)sel.size();
     return 0;
 }
 
@@ -123,20 +193,39 @@ int knp_source_eval(knp_ctx* c, int species, const double* params, int n_params)
     if (c->p.splitting == 2) { c->err = "source_eval: the manufactured-solution mode sets its own data terms"; return -1; }
     if (n_params != S->k[species].n_params || (n_params > 0 && !params)) { c->err = "source_eval: parameter count differs from the registered kernel's"; return -1; }
     if (!c->extra_knp) { c->err = "source_eval: the source buffer is gone (knp_set_mms)"; return -1; }
-    if (!S->nsel) return 0;                              // no ECS cell: nothing to launch, the row stays zero
+    const SourceKernel& K = S->k[species];
+    const bool with_fields = K.n_fields >= 0;
+    int64_t n = with_fields ? K.nsel : S->nsel;
+    if (!n) return 0;                                    // no cell in the list: nothing to launch, the row stays zero
     SourceParams p;
     memset(&p, 0, sizeof(p));
     for (int i = 0; i < n_params; ++i) p.v[i] = params[i];
-    int64_t n = S->nsel;
-    const int32_t* sel = S->sel;
+    const int32_t* sel = with_fields ? K.sel : S->sel;
     const double* coords = c->m.coords;
     const int32_t* cells = c->m.cells;
     int nq = S->nq;
     const double *bary = S->bary, *w = S->w, *B = S->B;
     double* out = c->extra_knp + (size_t)species * (size_t)row_len(c);
-    void* args[] = {&n, &sel, &coords, &cells, &nq, &bary, &w, &B, &p, &out};
     const unsigned grid = (unsigned)((n + KNP_SOURCE_BLOCK - 1) / KNP_SOURCE_BLOCK);
-    HIPCHK(c, hipModuleLaunchKernel(S->k[species].fn, grid, 1, 1, KNP_SOURCE_BLOCK, 1, 1, 0, c->stream, args, nullptr));
+    if (with_fields) {
+        // the field pointers as they are now (never cached across steps): phi of this step's EMI solve, level-n concentrations
+        SourceFields fld;
+        memset(&fld, 0, sizeof(fld));
+        for (int i = 0; i < K.n_fields; ++i) {
+            const int id = K.field_ids[i];
+            const bool solved = id >= 1 && id <= c->p.n_sys;
+            const double* f = knp_field_ptr(c, id == 0 ? KNP_F_PHI : solved ? KNP_F_C_PREV : KNP_F_C_ELIM, nullptr);
+            if (!f) { c->err = "source_eval: a field the source reads is not allocated"; return -1; }
+            if (solved) f += (int64_t)(id - 1) * row_len(c);
+            if (c->nd % 2 == 0 && ((uintptr_t)f & 15u)) { c->err = "source_eval: a field the source reads is not 16-byte aligned"; return -1; }
+            fld.v[i] = f;
+        }
+        void* args[] = {&n, &sel, &coords, &cells, &nq, &bary, &w, &B, &fld, &p, &out};
+        HIPCHK(c, hipModuleLaunchKernel(K.fn, grid, 1, 1, KNP_SOURCE_BLOCK, 1, 1, 0, c->stream, args, nullptr));
+        return 0;
+    }
+    void* args[] = {&n, &sel, &coords, &cells, &nq, &bary, &w, &B, &p, &out};
+    HIPCHK(c, hipModuleLaunchKernel(K.fn, grid, 1, 1, KNP_SOURCE_BLOCK, 1, 1, 0, c->stream, args, nullptr));
     return 0;
 }
 

@@ -11,8 +11,8 @@ from knpemidg.utils import (subdomain_marking_foo, interface_normal, plus, minus
                             CellCenterDistance)
 from knpemidg.solver import Solver
 from knpemidg.solver_emi import SolverEMI
-from knpemidg.expression import Expression
+from knpemidg.expression import Expression, FieldExpression
 
-__all__ = ["Solver", "SolverEMI", "Expression", "MembraneModel", "subdomain_marking_foo", "interface_normal", "plus", "minus",
+__all__ = ["Solver", "SolverEMI", "Expression", "FieldExpression", "MembraneModel", "subdomain_marking_foo", "interface_normal", "plus", "minus",
            "pcws_constant_project", "CellCenterDistance", "Mesh", "MeshFunction", "Constant", "RectangleMesh", "BoxMesh",
            "make_mesh_2D", "make_mesh_3D", "make_mesh_MMS"]

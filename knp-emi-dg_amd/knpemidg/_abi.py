@@ -44,6 +44,7 @@ SIGNATURES = {
     "knp_set_source": (C.c_int, [_ctxp, _f64p]),
     "knp_source_set_rule": (C.c_int, [_ctxp, C.c_int, _f64p, _f64p, _f64p]),
     "knp_source_register": (C.c_int, [_ctxp, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_int]),
+    "knp_source_register_fields": (C.c_int, [_ctxp, C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_int, C.c_int, _i32p, C.c_int, _i32p]),
     "knp_source_eval": (C.c_int, [_ctxp, C.c_int, _f64p, C.c_int]),
     "knp_source_clear": (C.c_int, [_ctxp, C.c_int]),
     "knp_source_cells": (C.c_int64, [_ctxp]),
@@ -526,7 +527,9 @@ class Device:
         self._rtc_ids = {}                 # kernel name of a registered HIP_RHS model -> its device model id (knp_ode_register)
         self._rtc_methods = {}             # device model id -> the methods whose kernels are loaded (knp_ode_register_method)
         self._source_rule_set = False      # the rule tables of the device-evaluated sources are uploaded (knp_source_set_rule)
-        self._source_kernels = {}          # species -> kernel name of its registered Expression (knp_source_register)
+        # species -> what is registered: the kernel name of an Expression (knp_source_register), or (kernel name, subdomains, field
+        # ids) of a FieldExpression (knp_source_register_fields)
+        self._source_kernels = {}
         self._tmp_slot = -1                # rotating scratch slot of facet_trace results
         self._tmp_gen = [0] * FACET_TMP_SLOTS
         if degree != 1:
@@ -587,14 +590,19 @@ class Device:
         self._chk(self.lib.knp_set_source(self.ctx, _p(src, _f64p)), "knp_set_source")
 
     # -- device-evaluated ion sources (knpemidg/expression.py builds, csrc/source.hip loads and launches) ---------------------
-    def source_register(self, species, expr):
-        """Make `expr` (a knpemidg.Expression) the source of `species`: compiled once per process for this context's dimension and
-        basis size, loaded on this context; the rule tables go up with the first registration.  A species whose registered kernel
-        is this one already (same code, parameter names, dimension and basis: values travel with every evaluation) is left alone.
-        A compile error raises KnpError with the hipRTC log."""
+    def source_register(self, species, expr, ion_names=None):
+        """Make `expr` (a knpemidg.Expression or FieldExpression) the source of `species`: compiled once per process for this
+        context's dimension and basis size, loaded on this context; the rule tables go up with the first registration.  A species
+        whose registered kernel is this one already (same code, parameter names, dimension and basis: values travel with every
+        evaluation; for a FieldExpression also the same subdomains and fields) is left alone.  A FieldExpression whose subdomains
+        alone changed gets a new cell list without a compile (the code object is memoised).  A compile error raises KnpError with
+        the hipRTC log.  `ion_names`: the solver's ion list in order, which a FieldExpression's "c_<name>" fields are resolved against."""
         from knpemidg import expression
         species = int(species)
-        if self._source_kernels.get(species) == expr.kernel_name(self.dim, self.nd):
+        key = expr.kernel_name(self.dim, self.nd)
+        if isinstance(expr, expression.FieldExpression):
+            key = key, tuple(expr.subdomains), tuple(expr.field_ids(ion_names or ()))
+        if self._source_kernels.get(species) == key:
             return
         kernel, code = expr.compiled(self.dim, self.nd)
         if not self._source_rule_set:
@@ -602,9 +610,15 @@ class Device:
             assert bary.shape == (len(w), self.dim + 1) and B.shape == (len(w), self.nd)
             self._chk(self.lib.knp_source_set_rule(self.ctx, len(w), _p(bary, _f64p), _p(w, _f64p), _p(B, _f64p)), "knp_source_set_rule")
             self._source_rule_set = True
-        self._chk(self.lib.knp_source_register(self.ctx, species, code, len(code), kernel.encode(), len(expr.names)),
-                  "knp_source_register")
-        self._source_kernels[species] = kernel
+        if isinstance(expr, expression.FieldExpression):
+            ids, tags = np.array(key[2], dtype=np.int32), np.array(key[1], dtype=np.int32)
+            self._chk(self.lib.knp_source_register_fields(self.ctx, species, code, len(code), kernel.encode(), len(expr.names),
+                                                          len(ids), _p(ids, _i32p), len(tags), _p(tags, _i32p)),
+                      "knp_source_register_fields")
+        else:
+            self._chk(self.lib.knp_source_register(self.ctx, species, code, len(code), kernel.encode(), len(expr.names)),
+                      "knp_source_register")
+        self._source_kernels[species] = key
 
     def source_eval(self, species, values):
         """Enqueue the evaluation of the species' registered source with these parameter values (no copy, no wait)."""

@@ -11,6 +11,9 @@ with its context (knp_source_register) and launches it before every KNP solve (k
 the ECS cells by the degree-8 rule of the host path (mms_terms.QDEG), written into the species' row of the buffer the right-hand-
 side kernels add to L_knp.  Parameter values are kernel arguments, not source text: a `Constant` is read at every evaluation (so
 `t=t` follows the solver's time constant), and `expr.g_syn = 65.0` takes effect at the next one without a recompile.
+
+`FieldExpression` is an `Expression` that also reads phi and concentrations at the quadrature points and integrates over the cells
+of any listed subdomains (source_load_vector_fields of the same header, knp_source_register_fields).
 """
 import hashlib
 import os
@@ -154,6 +157,130 @@ class Expression:
         th = threading.Thread(target=run, name="knp-source-rtc", daemon=True)
         th.start()
         return th
+
+
+MAX_FIELDS = 9               # KNP_SOURCE_MAX_FIELDS of csrc/source_rtc.hpp: phi and KNP_MAX_IONS concentrations
+FIELD_LINE_FILE = "knpemidg.FieldExpression"
+_FIELDS_ARGUMENT = "knp_fields"              # the functor's argument holding the field values at the quadrature point
+
+
+class FieldExpression(Expression):
+    """FieldExpression(code, fields=(), subdomains=(0,), degree=None, **params): a source term f(x, u(x); params) that reads the
+    solution, integrated over the cells of the listed subdomains.
+
+        ion_K['f_source'] = FieldExpression("-k_up * (c_K - c0)", fields=("c_K",), k_up=50.0, c0=4.0)
+        ion_K['f_source'] = FieldExpression("amp * (t > t0 && t < t1)", subdomains=(1,), amp=..., t0=..., t1=..., t=t)
+
+    `fields` lists distinct names out of "phi" and "c_<name>", <name> an ion['name'] of the solver's ion list (the eliminated ion
+    included); inside `code` each is a double holding that field's value at the quadrature point, u(x_q) = sum_a U[a] B[q][a] with
+    the cell's nodal values U.  The names are resolved against the ion list when the solver registers the source
+    (Solver.setup_varform_knp); an unknown one raises ValueError there.  `subdomains` is a non-empty tuple of distinct cell tags:
+    the load vector is int f v dx over the cells carrying one of them, (0,) -- the ECS -- by default.  A tag no cell carries is
+    allowed: the row is zero and nothing is launched.  Parameters, `degree` and the refusals are those of `Expression`; in addition
+    ValueError for a parameter named like a listed field, `phi` or `knp_fields`, for `fields` / `subdomains` that are no tuple or
+    list of str / int, and for duplicates in either.  Subdomains and parameter values are data: `expr.subdomains = (0, 1)` and
+    `expr.k_up = 80.0` need no recompile.
+
+    Time level.  The source is evaluated before every KNP solve.  Concentrations, the eliminated ion's included, are those of the
+    previous time level n (KNP_F_C_PREV, KNP_F_C_ELIM), phi is the one of this step's EMI solve, just done.  The reaction is
+    therefore explicit in a step whose diffusion is implicit: a rate with k * dt of order one or more is unstable, and nothing
+    guards against it, nor against injecting net charge.  In the Picard variant every iteration of a step sees the same level-n
+    concentrations of the solved species (the eliminated ion's field is recomputed from the iterate, as it always is there).  A
+    manufactured solution (mms) refuses a FieldExpression as it refuses an Expression."""
+
+    def __init__(self, code, fields=(), subdomains=(0,), degree=None, **params):
+        if not isinstance(fields, (tuple, list)) or not all(isinstance(f, str) for f in fields):
+            raise ValueError("FieldExpression: fields must be a tuple or list of names (\"phi\", \"c_<ion name>\")")
+        fields = tuple(fields)
+        if len(set(fields)) != len(fields):
+            raise ValueError("FieldExpression: a field is listed twice in %r" % (fields,))
+        if len(fields) > MAX_FIELDS:
+            raise ValueError("FieldExpression: %d fields; the device kernel takes at most %d (phi and every ion)" % (len(fields), MAX_FIELDS))
+        for f in fields:
+            if f != "phi" and not (f.startswith("c_") and len(f) > 2 and ode_rtc._IDENT.match(f)):
+                raise ValueError("FieldExpression: field %r is neither \"phi\" nor \"c_<ion name>\"" % f)
+        subdomains = self._checked_subdomains(subdomains)
+        for name in params:
+            if name in fields or name == "phi":
+                raise ValueError("FieldExpression: parameter name %r collides with a field the expression reads (or phi)" % name)
+            if name == _FIELDS_ARGUMENT:
+                raise ValueError("FieldExpression: parameter name %r collides with a name of the generated C++ (the functor's argument)" % name)
+            if name in ("_fields", "_subdomains"):
+                raise ValueError("FieldExpression: parameter name %r collides with an attribute of the Expression object itself" % name)
+        object.__setattr__(self, "_fields", fields)
+        object.__setattr__(self, "_subdomains", subdomains)
+        Expression.__init__(self, code, degree=degree, **params)
+
+    @staticmethod
+    def _checked_subdomains(subdomains):
+        ok = isinstance(subdomains, (tuple, list)) and all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) for s in subdomains)
+        if not ok or not len(subdomains) or min(subdomains) < 0:
+            raise ValueError("FieldExpression: subdomains must be a non-empty tuple or list of cell tags (non-negative ints)")
+        subdomains = tuple(int(s) for s in subdomains)
+        if len(set(subdomains)) != len(subdomains):
+            raise ValueError("FieldExpression: a subdomain is listed twice in %r" % (subdomains,))
+        return subdomains
+
+    def __setattr__(self, name, value):
+        if name == "subdomains":
+            object.__setattr__(self, "_subdomains", self._checked_subdomains(value))
+        else:
+            Expression.__setattr__(self, name, value)
+
+    @property
+    def fields(self):
+        return self._fields
+
+    @property
+    def subdomains(self):
+        return self._subdomains
+
+    def field_ids(self, ion_names):
+        """The fields as the ids of knp_source_register_fields: 0 for phi, 1 + i for "c_<name>" with <name> the i-th of
+        `ion_names` (the solver's ion list in order, the eliminated ion last).  ValueError for a name that is not among them."""
+        known = ["phi"] + ["c_%s" % n for n in ion_names]
+        missing = [f for f in self._fields if f not in known]
+        if missing:
+            raise ValueError("FieldExpression: no field named %s; the fields of this solver are %s"
+                             % (", ".join(repr(f) for f in missing), ", ".join(known)))
+        return [known.index(f) for f in self._fields]
+
+    def kernel_name(self, dim, nd):
+        """A function of (code, parameter names, field names, dim, nd) -- not of the subdomains or the parameter values."""
+        parts = (self._code,) + self._names + ("fields",) + self._fields + (str(int(dim)), str(int(nd)))
+        return "k_fsource_%dd_%d_%s" % (int(dim), int(nd), hashlib.sha256("\0".join(parts).encode()).hexdigest()[:12])
+
+    def source(self, dim, nd):
+        """(translation unit, kernel name) for a mesh of dimension `dim` with `nd` basis functions per cell."""
+        dim, nd = int(dim), int(nd)
+        if dim not in (2, 3) or nd not in {2: (3, 6), 3: (4, 10)}[dim]:
+            raise ValueError("Expression: no DG-P1 / P2 basis with %d functions per cell in %dD" % (nd, dim))
+        kernel = self.kernel_name(dim, nd)
+        enum = "enum : int { %s };\n" % ", ".join("P_%s = %d" % (n, i) for i, n in enumerate(self._names)) if self._names else ""
+        head = ("// %s: ion source over x[0..%d], %d fields and %d parameters, generated by knpemidg/expression.py\n"
+                "typedef long int64_t;\n"
+                "typedef int int32_t;\n" % (kernel, dim - 1, len(self._fields), len(self._names))) + enum + \
+            "struct UserSource {\n" \
+            "    __device__ __forceinline__ double operator()(const double* x, const double* knp_fields, const double* knp_params) const {\n" \
+            "        const double pi = 3.14159265358979323846;\n" + \
+            "".join("        const double %s = knp_fields[%d];\n" % (f, i) for i, f in enumerate(self._fields)) + \
+            "".join("        const double %s = knp_params[P_%s];\n" % (n, n) for n in self._names) + \
+            "        return (\n" \
+            "#line 1 \"%s\"\n" % FIELD_LINE_FILE
+        with open(HEADER) as fh:
+            header = fh.read()
+        tail_line = head.count("\n") + self._code.count("\n") + 3      # the line after the #line directive below
+        tail = ("\n#line %d \"%s.cpp\"\n" % (tail_line, kernel)) + \
+            "        );\n" \
+            "    }\n" \
+            "};\n" + header + \
+            ("\nextern \"C\" __global__ __launch_bounds__(KNP_SOURCE_BLOCK) void %s(int64_t n, const int32_t* __restrict__ sel,\n"
+             "        const double* __restrict__ coords, const int32_t* __restrict__ cells, int nq, const double* __restrict__ bary,\n"
+             "        const double* __restrict__ w, const double* __restrict__ B, SourceFields fld, SourceParams p,\n"
+             "        double* __restrict__ out) {\n"
+             "    source_load_vector_fields<%d, %d, %d>(UserSource(), n, sel, coords, cells, nq, bary, w, B, fld, p, out);\n"
+             "}\n" % (kernel, dim, nd, len(self._fields)))
+        return head + self._code + tail, kernel
 
 
 def rule_tables(dim, degree):

@@ -393,23 +393,24 @@ class Solver:
         # ion['f_source'] v dx(0) (solver.py:599): a number / Constant or a per-cell array travels as a DG0 coefficient on the ECS
         # cells; a callable f(x) or f(x, t) (the reference accepts any UFL coefficient, e.g. the box-and-time-window Expression
         # of run_tortuosity.py:180-200) is integrated on the host before every KNP solve (_update_sources); a knpemidg.Expression
-        # is compiled for the device and integrated there (csrc/source_rtc.hpp), with no host pass and no upload
+        # is compiled for the device and integrated there (csrc/source_rtc.hpp), with no host pass and no upload.  A FieldExpression
+        # (an Expression that also reads phi and concentrations, on any subdomain) is a device source too.  Both kinds are
+        # registered in one place, _register_device_sources, behind the parameter upload
         from knpemidg.expression import Expression
         fsrc = None
         nc = self.mesh.num_cells()
         ecs = (self.subdomains.array() == 0).astype(np.float64)
         rows, self._callable_sources = [], {}
-        before, self._device_sources = getattr(self, "_device_sources", {}), {}
         exprs = {k: ion['f_source'] for k, ion in enumerate(self.ion_list[:-1]) if isinstance(ion.get('f_source', 0.0), Expression)}
         if exprs and splitting == 2:
             raise ValueError("an Expression source cannot be combined with a manufactured solution (mms), which sets its own data terms")
         for k, f in exprs.items():                       # a source whose kernel the context holds already is left alone (Device.source_register)
-            if self.dev._source_kernels.get(k) != f.kernel_name(self.mesh.gdim, self.nd):
+            known = self.dev._source_kernels.get(k)
+            if (known[0] if isinstance(known, tuple) else known) != f.kernel_name(self.mesh.gdim, self.nd):
                 f.prefetch(self.mesh.gdim, self.nd)      # the compiles overlap each other and the parameter upload below
         for k, ion in enumerate(self.ion_list[:-1]):
             f = ion.get('f_source', 0.0)
             if k in exprs:
-                self._device_sources[k] = f
                 rows.append(np.zeros(nc))
             elif callable(f) and not hasattr(f, '__float__'):
                 self._callable_sources[k] = f
@@ -424,11 +425,7 @@ class Solver:
             fsrc = np.stack(rows)
         self.dev.set_params(_f(self.C_M), _f(self.dt), _f(self.F), _f(self.R), _f(self.temperature), _f(self.C_phi),
                             _f(self.tau_emi), _f(self.tau_knp), z, D, rho=self.rho, fsrc=fsrc, splitting=splitting)
-        for k in before:
-            if k not in self._device_sources:
-                self.dev.source_clear(k)
-        for k, f in self._device_sources.items():
-            self.dev.source_register(k, f)
+        self._register_device_sources()
 
     # ------------------------------------------------------------------ forms / solvers (solver.py:270-468, 534-721)
     def setup_varform_emi(self):
@@ -446,13 +443,40 @@ class Solver:
         return
 
     def setup_varform_knp(self):
+        """Field names of `FieldExpression` sources are resolved and a manufactured solution refuses them here, with or without a
+        device; with one, the device sources are registered (again: what the context holds already is left alone)."""
+        self._register_device_sources()
         return
+
+    def _register_device_sources(self):
+        """The one place where the ion sources that are `Expression`s or `FieldExpression`s reach the device.  "phi" / "c_<name>" of
+        a FieldExpression are resolved against the ion list (the eliminated ion included; ValueError for an unknown name, listing
+        the ones that exist) and a manufactured solution refuses either kind before anything is loaded; then species that lost their
+        device source are cleared and every device source is registered (Device.source_register compiles and loads only what the
+        context does not hold already).  Without a device yet, only the checks run: setup_varform_emi comes back here."""
+        from knpemidg.expression import Expression, FieldExpression
+        found = {k: ion['f_source'] for k, ion in enumerate(self.ion_list[:-1]) if isinstance(ion.get('f_source', 0.0), Expression)}
+        if found and self.mms is not None:
+            raise ValueError("an Expression source cannot be combined with a manufactured solution (mms), which sets its own data terms")
+        names = [ion.get('name', str(k)) for k, ion in enumerate(self.ion_list)]
+        for f in found.values():
+            if isinstance(f, FieldExpression):
+                f.field_ids(names)
+        if self.dev is None:
+            return
+        before, self._device_sources = getattr(self, "_device_sources", {}), found
+        for k in before:
+            if k not in found:
+                self.dev.source_clear(k)
+        for k, f in found.items():
+            self.dev.source_register(k, f, ion_names=names)
 
     def _update_sources(self, t):
         """Load vector of the callable ion sources at time t: int f_k(x, t) v dx(0) by a degree-8 rule per ECS cell (the reference
         interpolates its Expression to the declared degree and integrates that: run_tortuosity.py:180-200, solver.py:599).
-        Host callables are integrated here and uploaded first; the sources that are `Expression`s are then evaluated on the device
-        with their current parameter values (same rule, same stream, no host pass, no copy, no wait) and overwrite their rows."""
+        Host callables are integrated here and uploaded first; the sources that are `Expression`s or `FieldExpression`s are then
+        evaluated on the device with their current parameter values (same rule, same stream, no host pass, no copy, no wait) and
+        overwrite their rows."""
         if self.mms is not None:
             return
         self._update_host_sources(t)
