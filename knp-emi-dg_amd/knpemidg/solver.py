@@ -13,14 +13,22 @@ reference (reference: src/knpemidg/solver.py:62-1258); what changed is what sits
 
 dolfin objects are replaced by the array stand-ins of `knpemidg.mesh` / `knpemidg.functions`.
 There is no CPU fallback: without libknpemi_hip.so and a visible GPU, setup raises.
+
+Who owns what: `Solver` keeps the reference's setup calls and time loops, the device bring-up, the ion sources and the checkpoint of its
+own state, and declares everything it holds in `__init__`.  `resolve_settings` (below) turns solver_params and the KNP_* variables into
+the effective tolerances and Krylov options.  knpemidg/precond.py owns the preconditioners' host side: `Solver.emi_smoother`
+(SmootherChoice: the EMI DG-level smoother, measured on the first solve) and `Solver.amg` (AmgSetup: helper processes, hierarchy builds
+and uploads, refresh policy and its counters).  knpemidg/recorder.py, grid.py and checkpoint.py own time series, voxel grids and the
+checkpoint file.
 """
 import os
 import sys
 import time
+from typing import NamedTuple
 
 import numpy as np
 
-from knpemidg import _abi, ode_rtc
+from knpemidg import _abi, ode_rtc, precond
 from knpemidg.functions import FacetSpace, FacetFunction, DeviceFacetFunction, DeviceFunction
 from knpemidg.membrane import MembraneModel
 from knpemidg.mesh import Constant
@@ -29,7 +37,7 @@ from knpemidg.utils import interface_normal, plus, minus, pcws_constant_project
 JUMP = lambda f, n: ("JUMP", f, n)   # symbolic marker; the device evaluates minus - plus
 
 
-# factor theta of the residual half of the error-controlled EMI stop (Solver._read_solver_params): the solve ends when the TRUE residual,
+# factor theta of the residual half of the error-controlled EMI stop (resolve_settings): the solve ends when the TRUE residual,
 # in the order-8 norm of its density, is below theta / p^2 * 0.1 rtol_emi * F min|z_k| ||b_knp / vol||_8 (p = polynomial degree: the
 # error behind a given residual density grows with the degree, round 2's "DG-P2 needs a 4x tighter potential"; no mesh quantity enters).
 # Measured against runs converged to 1e-11 / 1e-13 with BOTH DG-level smoothers of the EMI preconditioner (tools/stop_sweep_r04.py,
@@ -61,6 +69,103 @@ def _names(ode, what):
     if isinstance(table, dict):
         return [str(x) for x in sorted(table, key=table.get)]
     return int(len(ode.init_state_values() if what == "state" else ode.init_parameter_values()))
+
+
+class Settings(NamedTuple):
+    """Effective tolerances and Krylov options of a run (resolve_settings)."""
+    max_it_emi: int
+    max_it_knp: int
+    rtol_emi: float
+    atol_emi: float
+    emi_target: object           # factor of the error-controlled EMI stop, or None: the relative test with rtol_emi alone
+    rtol_knp: float
+    atol_knp: float
+    knp_krylov: str
+    gmres_restart: int
+    knp_min_it: int
+    knp_early: float
+
+
+def _setting(sp, field, environ, variable, default, falsy_is_unset=False):
+    """Field `field` of solver_params, else the variable, else the default -- as found: the caller converts."""
+    v = getattr(sp, field, None)
+    if v is None or (falsy_is_unset and not v):
+        v = environ.get(variable) if variable is not None else None
+    return default if v is None else v
+
+
+def resolve_settings(sp, *, degree_emi, rtol_emi, atol_emi, rtol_knp, atol_knp, direct_emi, direct_knp, environ=os.environ,
+                     max_it_emi=50000, max_it_knp=5000):
+    """The `Settings` a run solves with: every option is the field of solver_params `sp` if that is set, else its KNP_* variable (where
+    it has one), else the default.  "Set" means `is not None` for emi_rtol_scale, knp_rtol_scale and knp_early_stop (0 switches the
+    early stop off).  For c_tol, emi_target_safety, emi_energy_factor, knp_krylov, knp_min_it and gmres_restart a FALSY field (0, 0.0,
+    "") counts as unset and falls through to the variable: that is how these were always read, and it is kept.  rtol_* / atol_* are the
+    nominal tolerances of solver_params (unused, and possibly None, for a direct solve); max_it_* the caps without a field."""
+    # Krylov caps: the reference sets ksp_max_it 1000 behind BoomerAMG (solver.py:429,687); the cap is a solver_params option.
+    max_it_emi = int(_setting(sp, "max_it_emi", environ, None, max_it_emi))
+    max_it_knp = int(_setting(sp, "max_it_knp", environ, None, max_it_knp))
+    # direct solvers (MUMPS, solver.py:412-422, 671-681) have no device counterpart: emulate with a tight
+    # iterative tolerance
+    rtol_direct = float(_setting(sp, "rtol_direct", environ, None, 1e-10))
+    # PETSc tests ||M^-1 r|| <= rtol ||M^-1 b|| with M = BoomerAMG (solver.py:425-444); with this build's preconditioner the
+    # same nominal rtol 1e-5 leaves mean-free phi accurate to 1e-4 of its maximum but the concentrations only to 3e-5
+    # (they inherit the RELATIVE error of phi through the drift and membrane terms), measured against direct solves
+    # through an action potential (tests/test_gpu_trajectory.py, tools/tolerance_sweep.py).  The nominal tolerance is
+    # therefore scaled so that the stated parity bounds (c <= 1e-6, phi <= 1e-4) hold at every step.
+    # DG-P2 needs a 4x tighter potential for the same bound on c (configs[2], r=1, 40 steps: worst c 1.8e-6 / 1.1e-6 / 6.2e-7
+    # at scale 2e-3 / 1e-3 / 5e-4; a tighter KNP tolerance changes nothing): profiles/r02_tolerance_p2_r1.txt
+    # The factor is a property of (mesh family, degree), not a constant: the weaker the preconditioner on a mesh, the larger
+    # the error behind a given residual (EMIx reconstruction, 13-36 EMI iterations per solve: worst c 7.1e-6 at the idealized
+    # mesh's settings; there the KNP residual test needs tightening too).  `emi_rtol_scale` / `knp_rtol_scale` in
+    # solver_params set the factors per configuration (examples/emix_simulations: 1e-4 / 0.03, profiles/r02_tolerance_emix.txt);
+    # tools/tolerance_sweep.py / tools/tolerance_emix.py measure them.
+    # ROUND 3: the per-mesh factors above are replaced by an error-controlled stop.  The EMI solve stops when its residual, in the
+    # cell-volume-weighted norm, is small enough for the concentration accuracy wanted (knp_emi_residual_target,
+    # csrc/solve.hip): r_abs = theta * c_tol * F * min_k |z_k| ||b_knp,k||_w with c_tol = 0.1 * rtol_emi (the reference pairs
+    # rtol_emi 1e-5 with concentrations good to 1e-6) and ONE safety factor theta for every mesh family and degree
+    # (EMI_TARGET_SAFETY above; measured: profiles/r03_error_controlled_stop.txt).  `emi_rtol_scale` in solver_params (or
+    # KNP_EMI_RTOL_SCALE, tools only) selects the old preconditioned-norm test with that factor instead.
+    scale = _setting(sp, "emi_rtol_scale", environ, "KNP_EMI_RTOL_SCALE", None)
+    rt = float(rtol_emi) if not direct_emi else 0.0
+    emi_target = None
+    if direct_emi:
+        rtol_e = rtol_direct
+    elif scale is not None:
+        rtol_e = max(rt * float(scale), min(rt, 1.0e-11))
+    else:
+        c_tol = float(_setting(sp, "c_tol", environ, None, 0.1 * rt, falsy_is_unset=True))
+        theta = float(_setting(sp, "emi_target_safety", environ, "KNP_EMI_TARGET_SAFETY", EMI_TARGET_SAFETY / degree_emi ** 2, falsy_is_unset=True))
+        emi_target = theta * c_tol
+        # Second half of the stop (csrc/krylov.hip: cg_converged): the energy-norm error of the iterate, estimated from the CG
+        # coefficients, relative to ||phi||_A.  Round 3 tested the preconditioned norm ||M^-1 r|| here, which under-reports the
+        # error by a factor that depends on M (a better preconditioner met it with MORE error left); the Hestenes-Stiefel estimate
+        # measures the error itself and holds for any SPD preconditioner.
+        rtol_e = float(_setting(sp, "emi_energy_factor", environ, "KNP_EMI_ENERGY_FACTOR", PHI_ENERGY_FACTOR, falsy_is_unset=True)) * rt
+    kscale = float(_setting(sp, "knp_rtol_scale", environ, "KNP_KNP_RTOL_SCALE", 1.0))
+    rk = float(rtol_knp) if not direct_knp else 0.0
+    # direct_knp (MUMPS in the reference) is emulated by a tightly converged solve: rtol_direct is meant for the residual itself, so the
+    # factor 20 the device puts on the order-8 density test (csrc/solve.hip: KNP_D8_FACTOR) is divided out here (ADVICE r3)
+    rtol_k = rtol_direct / 20.0 if direct_knp else max(rk * kscale, min(rk, 1.0e-13))
+    # KNP Krylov method: the device default is BiCGStab; `knp_krylov = "gmres"` (+ `gmres_restart`, default 30) in solver_params,
+    # or KNP_KNP_KRYLOV=gmres, selects the reference's restarted GMRES (ksp_type gmres / ksp_gmres_restart 30, solver.py:684-701)
+    meth = _setting(sp, "knp_krylov", environ, "KNP_KNP_KRYLOV", "bicgstab", falsy_is_unset=True)
+    restart = int(_setting(sp, "gmres_restart", environ, "KNP_GMRES_RESTART", 30, falsy_is_unset=True))
+    # ksp_min_it 5 of the reference's GMRES (solver.py:686) = at least five operator + preconditioner applications.  A BiCGStab
+    # iteration makes two of each, so three iterations (six applications) would honour it; rounds 1-3 forced five iterations = ten
+    # applications, and the solves of the quiet phases of a run stopped at exactly that floor.  FOUR is the measured optimum: the
+    # forced iterations of the quiet steps are what keeps the per-step errors from adding up over a run (r=1, 40 steps, worst c
+    # against tight solves: min_it 3: 9.0e-7 at 3.95 iterations per step, 4: 2.2e-7 at 4.47, 5: 2.1e-7 at 5.12; tightening the
+    # residual test instead buys less per iteration: factor 10 at min_it 3: 5.8e-7 at 4.70; profiles/r04_min_it.txt,
+    # r04_stop_sweep.txt).  KNP_KNP_MIN_IT / solver_params.knp_min_it change it.
+    min_it = int(_setting(sp, "knp_min_it", environ, "KNP_KNP_MIN_IT", 5 if meth == "gmres" else 4, falsy_is_unset=True))
+    # The floor is there for the quiet phases; a solve whose residual is already 100x UNDER the tolerance needs no forced iterations
+    # for that purpose (knp_knp_early_stop).  Over the reference's 200-step run at r=2: 4.20 -> 3.54 KNP iterations per step, KNP time
+    # -16 %, worst c / phi over 100 steps unchanged to three digits at r=1 and r=2 (2.31e-7 / 2.15e-7: they come from the action
+    # potential, where the floor does not bind); a factor 0.1 instead of 0.01: 2.57 iterations but c 7.2e-7 at r=1
+    # (profiles/r04_early_stop_sweep.txt).  solver_params.knp_early_stop / KNP_KNP_EARLY set the factor, 0 switches it off.
+    early = 0.0 if direct_knp else float(_setting(sp, "knp_early_stop", environ, "KNP_KNP_EARLY", 0.01))
+    return Settings(max_it_emi, max_it_knp, rtol_e, 1e-40 if direct_emi else float(atol_emi), emi_target, rtol_k,
+                    1e-40 if direct_knp else float(atol_knp), meth, restart, min_it, early)
 
 
 class Solver:
@@ -98,6 +203,56 @@ class Solver:
         self.max_it_knp = 5000
         self.recorder = None             # time-series recorder (Solver.record), sampled after step III of every time step
         self.grids = None                # voxel-grid samplers (Solver.record_grid); None = off: the time loops test this once per step
+        # a partition of a global mesh: partition.distribute_solver sets these before setup_domain
+        self.nc_owned = self.local_mesh = self.global_mesh_tuple = None
+        # what the setup_* calls fill in, in the reference's order
+        self.mesh = self.subdomains = self.surfaces = self.n_g = self.gdim = self.tau_emi = self.tau_knp = self.lm_tags = None
+        self.C_phi = self.C_M = self.dt = self.F = self.R = self.temperature = self.psi = self.phi_M_init_type = self.rho = None
+        self.nd = self.Q = self._init_c = self._init_c_elim = self._init_phi_M = None
+        self.membrane_tags = self.phi = self.c = self.c_prev_k = self.c_prev_n = self.phi_M_prev_PDE = self.I_ch = None
+        self.amg = None                  # precond.AmgSetup, from _ensure_device on
+        self.emi_smoother = None         # precond.SmootherChoice, from setup_solver_emi on (with the AMG preconditioner)
+        self._device_sources, self._callable_sources, self._src_geom = {}, {}, None
+        # solver_params as unpacked by _unpack_solver_params, and what resolve_settings makes of them (_read_solver_params)
+        self.solver_params = None
+        self.direct_emi = self.direct_knp = False
+        self.rtol_emi = self.atol_emi = self.threshold_emi = self.rtol_knp = self.atol_knp = self.threshold_knp = None
+        self.settings = None
+        self._rtol_emi = self._atol_emi = self._emi_target = self._rtol_knp = self._atol_knp = self._knp_min_it = self._knp_early = None
+        self._knp_krylov = "bicgstab"    # the method the device runs (its default until set_knp_krylov)
+        # run state
+        self.filename, self.save_fields, self.save_solver_stats, self.splitting_scheme = None, False, False, True
+        self._t_now = 0.0                # time-dependent sources see the t of the current step
+        self._knp_bnorm = None           # load norms of the last KNP solve (_knp_load_norm)
+        self.knp_residuals = None
+        self.picard_iters = []
+        self._picard = False
+        self._k_done, self._t_done = 0, 0.0                  # what a checkpoint written now continues from
+        self._resume_header, self._resume_k = None, 0
+        self.h5_file = self.h5_path = None
+        self.h5_idx = 0
+        self.file_emi_solve = self.file_emi_assem = self.file_emi_niter = None
+        self.file_knp_solve = self.file_knp_assem = self.file_knp_niter = None
+
+    @property
+    def emi_dg_chebyshev_measured(self):
+        """None until the smoother trial has run, then its figures (precond.SmootherChoice.measured)."""
+        return None if self.emi_smoother is None else self.emi_smoother.measured
+
+    # read-only views of `amg` and `emi_smoother` under the names tests and the rank workers read
+    _emi_helper = property(lambda self: None if self.amg is None else self.amg.emi_helper)
+    _knp_helper = property(lambda self: None if self.amg is None else self.amg.knp_helper)
+    amg_refreshes = property(lambda self: 0 if self.amg is None else self.amg.refreshes)
+    amg_dist0 = property(lambda self: 0 if self.amg is None else self.amg.dist0_uploads)
+    _emi_trial = property(lambda self: True if self.emi_smoother is not None and self.emi_smoother.pending else None)
+    _emi_cheb_chosen = property(lambda self: None if self.emi_smoother is None else self.emi_smoother.chosen)
+
+    @property
+    def _cspace(self):
+        """The conforming space, an attribute only once it has been built in this process (the helper processes build their own)."""
+        if self.amg is None or self.amg.cspace is None:
+            raise AttributeError("_cspace")
+        return self.amg.cspace
 
     # ------------------------------------------------------------------ setup_domain (solver.py:85-121)
     def setup_domain(self, mesh, subdomains, surfaces):
@@ -251,13 +406,18 @@ class Solver:
         self.membrane_tags = list(membrane_tags)
         nc = self.mesh.num_cells()
         _abi._stamp("solver: _ensure_device")
+        self.amg = precond.AmgSetup(precond.AmgInputs(
+            mesh=self.mesh, subdomains=self.subdomains, surfaces=self.surfaces, global_mesh_tuple=self.global_mesh_tuple,
+            local_mesh=self.local_mesh, degree=self.degree_knp, nd=self.nd, ion_list=self.ion_list, dt=_f(self.dt), F=_f(self.F),
+            psi=self.psi, C_phi=_f(self.C_phi), membrane_tags=self.membrane_tags, init_c=self._init_c, init_c_elim=self._init_c_elim,
+            verbose=self.verbose))
         if self.mms is None:
-            self._start_knp_helper()
-            self._start_emi_helper()
+            if self.use_amg:                 # the helper processes build while the device context is being created
+                self.amg.start_knp_helper()
+                self.amg.start_emi_helper()
             _abi._stamp("solver: helper jobs handed over")
         self.dev = _abi.Device(self.mesh, self.subdomains.array(), self.surfaces.array(), self.membrane_tags,
-                               len(self.ion_list), degree=self.degree_knp, device=self.device_index,
-                               nc_owned=getattr(self, "nc_owned", None))
+                               len(self.ion_list), degree=self.degree_knp, device=self.device_index, nc_owned=self.nc_owned)
         A = _abi
         dev = self.dev
         self.phi = DeviceFunction(dev, A.F_PHI, nc, self.nd)
@@ -311,11 +471,11 @@ class Solver:
         if membrane_states and not self.use_device_ode:
             raise _abi.KnpError("Solver.record: membrane_states read the ODE state tables on the device; with KNP_HOST_ODE=1 they "
                                 "live on the host")
-        loc, gmt = getattr(self, "local_mesh", None), getattr(self, "global_mesh_tuple", None)
-        if (loc is None or gmt is None) and (loc is not None or getattr(self, "nc_owned", None) is not None):
+        loc, gmt = self.local_mesh, self.global_mesh_tuple
+        if (loc is None or gmt is None) and (loc is not None or self.nc_owned is not None):
             raise _abi.KnpError("Solver.record: a partitioned solver needs its LocalMesh and the global mesh (local_mesh, "
                                 "global_mesh_tuple: partition.distribute_solver sets them)")
-        if getattr(self, "mesh", None) is None:
+        if self.mesh is None:
             raise _abi.KnpError("Solver.record: call setup_domain first")
         mtags = self.membrane_tags if self.dev is not None else None
         mesh, sub, surf = (self.mesh, self.subdomains, self.surfaces) if loc is None else gmt
@@ -349,10 +509,9 @@ class Solver:
         {field: array [nz, ny, nx]} ([ny, nx] in 2D) of the fields as they are now; `sampler.cells` / `sampler.tags` are the owner and
         subdomain volumes.  Without a call nothing is allocated or launched.  Partitioned solvers are not supported."""
         from knpemidg.grid import GridSpec, GridSampler, resolve_fields
-        if getattr(self, "local_mesh", None) is not None or getattr(self, "nc_owned", None) is not None or \
-                (self.dev is not None and self.dev.nranks > 1):
+        if self.local_mesh is not None or self.nc_owned is not None or (self.dev is not None and self.dev.nranks > 1):
             raise _abi.KnpError("record_grid: not supported with several ranks (sample the grid in a one-GPU run)")
-        if getattr(self, "mesh", None) is None:
+        if self.mesh is None:
             raise _abi.KnpError("Solver.record_grid: call setup_domain first")
         try:
             spec = GridSpec(self.mesh.gdim, lo, hi, shape, tol=tol, tags=tags)
@@ -464,7 +623,7 @@ class Solver:
                 f.field_ids(names)
         if self.dev is None:
             return
-        before, self._device_sources = getattr(self, "_device_sources", {}), found
+        before, self._device_sources = self._device_sources, found
         for k in before:
             if k not in found:
                 self.dev.source_clear(k)
@@ -480,16 +639,16 @@ class Solver:
         if self.mms is not None:
             return
         self._update_host_sources(t)
-        for k, f in getattr(self, "_device_sources", {}).items():
+        for k, f in self._device_sources.items():
             self.dev.source_eval(k, f.values())
 
     def _update_host_sources(self, t):
-        srcs = getattr(self, "_callable_sources", None)
+        srcs = self._callable_sources
         if not srcs:
             return
         import inspect
         from knpemidg.mms_terms import _cell_source, _geometry
-        if not hasattr(self, "_src_geom"):
+        if self._src_geom is None:
             self._src_geom = (_geometry(self.mesh)[0], np.nonzero(self.subdomains.array() == 0)[0])
         vol, sel = self._src_geom
         out = np.zeros((self.N_ions, self.mesh.num_cells(), self.nd))
@@ -504,392 +663,38 @@ class Solver:
         # block-Jacobi preconditioner: it stays SPD to rounding for any coefficient contrast (the MMS problem couples
         # the membrane with C_phi = 1e10), which a V-cycle does not
         if self.use_amg and not self.direct_emi:
-            self.dev.set_emi_dg_smoother(self._emi_dg_chebyshev())
-            # the KNP helper usually finishes first (no membrane term, one hierarchy for both species): while the EMI helper is still
-            # running, its result is uploaded here instead of in setup_solver_knp (0.2 s of upload hidden behind the wait)
-            eh, kh = getattr(self, "_emi_helper", None), getattr(self, "_knp_helper", None)
-            if (eh is not None and kh is not None and not self.direct_knp and eh[0]["thread"].is_alive() and not kh[0]["thread"].is_alive()):
-                self._setup_amg_knp()
-                self._knp_amg_uploaded_early = True
-            self._setup_amg_emi()
+            self.emi_smoother = precond.SmootherChoice(self.dev, getattr(self.solver_params, "emi_dg_chebyshev", None),
+                                                       (self._resume_header or {}).get("emi_dg_chebyshev"), self.verbose)
+            self.dev.set_emi_dg_smoother(self.emi_smoother.chosen)
+            if not self.direct_knp:
+                self.amg.upload_knp_if_ready(self.dev)
+            self.amg.setup_emi(self.dev)
         else:
-            self._drop_emi_helper()
+            self.amg.drop_emi_helper()
         return
-
-    def _emi_dg_chebyshev(self):
-        """DG-level smoother of the EMI preconditioner at setup time: the two-step Chebyshev block-Jacobi (one more operator apply per PCG
-        iteration, fewer iterations) unless `emi_dg_chebyshev` in solver_params decides explicitly.  Whether the extra apply pays depends
-        on where the run sits between the launch-latency and the bandwidth regime and on the mesh quality (r=2: 4.25 -> 4.7 iterations
-        without it for a quarter less work per iteration; EMIx reconstruction: 9.2 -> 13.5 iterations), so it is MEASURED on the first
-        EMI system of the run itself (_emi_smoother_trial) instead of being read off mesh-size thresholds (round 3)."""
-        sp = getattr(self, "solver_params", None)
-        explicit = getattr(sp, "emi_dg_chebyshev", None)
-        if explicit is None and os.environ.get("KNP_EMI_CHEB") is not None:
-            explicit = int(os.environ["KNP_EMI_CHEB"]) != 0                # the device reads the same variable as an override (csrc/solve.hip)
-        self._emi_trial = None if explicit is not None else True
-        recorded = (getattr(self, "_resume_header", None) or {}).get("emi_dg_chebyshev")
-        if explicit is None and recorded is not None:
-            self._emi_trial = None                                         # a resumed run keeps the choice its first part measured
-            explicit = bool(recorded)
-        self._emi_cheb_chosen = True if explicit is None else bool(explicit)
-        return self._emi_cheb_chosen
-
-    def _emi_smoother_trial(self, solve):
-        """Measured choice of the EMI DG-level smoother, on the FIRST EMI system of the run: the same right-hand side is solved from the
-        same initial guess with the Chebyshev step and with plain block-Jacobi (one untimed solve each first: eigenvalue estimate, graph
-        capture, code-object loads), each charged its wall time per decade of TRUE-residual reduction; the times are summed over the
-        ranks of a partitioned run (one all-reduce: every rank takes the same decision and keeps ONE symmetric preconditioner).  The
-        step stays unless dropping it is at least 3 % cheaper.  The time stepping itself never changes preconditioner: a trial spread
-        over the first steps of the run (tried first) perturbed the extrapolated initial guesses of the steps behind it (r=2: EMI 4.6 ->
-        5.2, KNP 5.1 -> 5.4 iterations per step over the next 20 steps, profiles/r04_smoother_trial.txt).  Both variants meet the same
-        stopping test, which does not depend on the preconditioner (csrc/krylov.hip: cg_converged), so the last solve's result IS the
-        step's solution.  solve() -> (seconds, niter, res) runs one EMI solve on the current device state."""
-        dev = self.dev
-        phi0 = dev.download(_abi.F_PHI)
-        cost = {}
-        out = None
-        for timed in (False, True):
-            for cheb in (True, False):
-                dev.set_emi_dg_smoother(cheb)
-                dev.upload(_abi.F_PHI, phi0)                       # same initial guess; a caller-supplied state is no history point
-                sec, niter, res = solve()
-                if timed:
-                    decades = max(np.log10(max(float(res[0]), 1e-300) / max(float(res[1]), 1e-300)), 0.25)
-                    cost[cheb] = sec / decades
-                out = (sec, niter, res)
-        on, off = self.dev.allreduce_sum([cost[True], cost[False]])
-        keep = not (off < 0.97 * on)
-        self.emi_dg_chebyshev_measured = {"chebyshev_s_per_decade": float(on), "plain_s_per_decade": float(off), "chosen": bool(keep)}
-        if self.verbose:
-            print(" EMI DG-level smoother: Chebyshev step %.3f ms / decade, plain block-Jacobi %.3f ms / decade -> %s"
-                  % (1e3 * on, 1e3 * off, "Chebyshev" if keep else "plain"))
-        self._emi_trial = None
-        self._emi_cheb_chosen = bool(keep)
-        if keep:                                                   # the last solve ran without the step: redo with the chosen one
-            dev.set_emi_dg_smoother(True)
-            dev.upload(_abi.F_PHI, phi0)
-            out = solve()
-        return out
-
-    def _host_initial_kappa(self):
-        """kappa = F psi sum_k z_k^2 D_k c_k of the initial state, nodal [nc, nd] (what k_kappa computes on the device)."""
-        nc = self.mesh.num_cells()
-        kappa = np.zeros((nc, self.nd))
-        for idx, ion in enumerate(self.ion_list):
-            c = self._init_c_elim if idx == len(self.ion_list) - 1 else self._init_c[idx]
-            kappa += _f(self.F) * float(ion['z']) ** 2 * self.psi * np.asarray(ion['D'], dtype=np.float64)[:, None] * c
-        return kappa
-
-    def _start_emi_helper(self):
-        """First EMI hierarchy (from the initial state) in a helper process, next to the KNP one (knpemidg/setup_worker.py).
-        Not for partitions (their hierarchy is the global one) and not for manufactured solutions (direct_emi)."""
-        if (not self.use_amg or os.environ.get("KNP_AMG_SERIAL_SETUP", "0") == "1" or getattr(self, "_emi_helper", None) is not None
-                or getattr(self, "global_mesh_tuple", None) is not None or not hasattr(self, "_init_c")):
-            return
-        from knpemidg import setup_worker
-        kappa = self._host_initial_kappa()
-        job = setup_worker.emi_job(self.mesh, self.surfaces.array(), self.membrane_tags, self.degree_knp, kappa, _f(self.params.C_phi))
-        self._emi_helper = (setup_worker.start(job), kappa)
-
-    def _drop_emi_helper(self):
-        helper = getattr(self, "_emi_helper", None)
-        if helper is not None:
-            from knpemidg import setup_worker
-            self._emi_helper = None
-            setup_worker.cancel(helper[0])
-
-    def _setup_amg_emi(self):
-        """Preconditioner setup (the reference builds BoomerAMG from BB_emi, solver.py:433, 505): conforming
-        P1 operator from the current kappa + smoothed-aggregation hierarchy, built on the host once and reused
-        across time steps."""
-        from knpemidg import amg
-        ts = time.perf_counter()
-        dev = self.dev
-        levels = dg2cg = None
-        helper = getattr(self, "_emi_helper", None)
-        if helper is not None:
-            # first build: collected from the helper process if the device state still is the initial state it was given
-            from knpemidg import setup_worker
-            self._emi_helper = None
-            handle, kappa_h = helper
-            dev.update_kappa()
-            kappa = dev.download(_abi.F_KAPPA).reshape(self.mesh.num_cells(), self.nd)
-            if np.allclose(kappa, kappa_h, rtol=1e-8, atol=0.0):
-                _abi._stamp("solver: waiting for the EMI helper")
-                res = setup_worker.collect(handle)
-                _abi._stamp("solver: EMI hierarchy collected")
-                if res is not None:
-                    levels, dg2cg = res["levels"], res["dof"]
-                    self._amg_kappa0 = kappa.ravel().copy()
-                    self._dg2cg_helper = dg2cg
-            else:
-                setup_worker.cancel(handle)
-        if levels is None:
-            gmesh, gsub, gsurf = self._amg_global()
-            if gmesh is self.mesh:
-                dev.update_kappa()
-                kappa = dev.download(_abi.F_KAPPA).reshape(self.mesh.num_cells(), self.nd)
-                self._amg_kappa0 = kappa.ravel().copy()          # what the hierarchy was built from (refresh policy)
-            else:
-                # distributed: every rank builds the SAME global hierarchy from the tag-wise initial state (no
-                # communication; the preconditioner is lagged anyway)
-                kappa = np.zeros(gmesh.num_cells())
-                for ion in self.ion_list:
-                    if ion['c_init_sub_type'] != 'constant':
-                        raise NotImplementedError("distributed AMG setup needs tag-wise constant initial concentrations")
-                    D = self._by_tag(ion['D_sub'], gsub)
-                    c0 = self._by_tag(ion['c_init_sub'], gsub)
-                    kappa += _f(self.F) * float(ion['z']) ** 2 * self.psi * D * c0
-            levels = amg.build_emi_levels(self._cspace, self._cspace2 if self.degree_knp != 1 else None, gsurf.array(),
-                                          self.membrane_tags, kappa, _f(self.C_phi))
-            dg2cg = self._local_dg2cg()
-            d0 = self._dist0()
-            if d0 is not None:                      # partitioned run: this rank's rows of the finest conforming level
-                local = d0.localize(levels)
-                if local is not None:
-                    dev.amg_upload(0, d0.local_dg2cg(self.local_mesh.cells_global), local, dist0=True)
-                    self.amg_dist0 = getattr(self, "amg_dist0", 0) + 1          # hierarchies uploaded in the row-distributed form
-                    levels = None
-        if levels is not None:
-            dev.amg_upload(0, dg2cg, levels)
-            _abi._stamp("solver: EMI hierarchy uploaded")
-            nlev = [lv.A.shape[0] for lv in levels]
-        else:
-            nlev = [lv.A.shape[0] for lv in local]
-        self.amg_setup_timer = time.perf_counter() - ts
-        if self.verbose:
-            print(" AMG(EMI) levels:", nlev, "setup %.2f s" % self.amg_setup_timer)
-
-    def _maybe_refresh_amg_emi(self, niter):
-        """Refresh policy of the lagged EMI hierarchy.  The reference rebuilds BoomerAMG from the freshly assembled B_emi at
-        EVERY solve (solver.py:479, 505); here the hierarchy is built from kappa at setup time and rebuilt when it has gone
-        stale: (a) kappa has moved by more than KNP_AMG_REFRESH_KAPPA (default 25 %) anywhere since the last build (checked
-        every KNP_AMG_REFRESH_EVERY = 50 solves), or (b) the PCG iteration count has stayed above 3x its post-build level for 10 consecutive solves.
-        (The KNP hierarchies depend on the mesh, D_k and dt only -- nothing to refresh.)  A partitioned run keeps the hierarchy
-        of the initial state (every rank would have to gather kappa to rebuild the replicated levels): the Krylov solves still
-        converge to their tolerance, only the iteration count can grow."""
-        if not (self.use_amg and not self.direct_emi) or getattr(self, "local_mesh", None) is not None:
-            return
-        st = self.__dict__.setdefault("_amg_refresh", {"solves": 0, "ref": None, "high": 0})
-        st["solves"] += 1
-        if st["ref"] is None and st["solves"] >= 3:
-            st["ref"] = max(1, min(self.emi_niter[-2:]))
-        stale = False
-        if st["ref"] is not None:
-            st["high"] = st["high"] + 1 if niter > 3 * st["ref"] + 2 else 0
-            stale = st["high"] >= 10
-        if st["solves"] % int(os.environ.get("KNP_AMG_REFRESH_EVERY", 50)) == 0:
-            kap, k0 = self.dev.download(_abi.F_KAPPA), self._amg_kappa0
-            lim = float(os.environ.get("KNP_AMG_REFRESH_KAPPA", 0.25))
-            floor = 1e-12 * max(float(np.abs(k0).max()), 1e-300)                # a zero entry of kappa must not force a rebuild
-            drift = np.abs(kap - k0) / np.maximum(np.abs(k0), floor)
-            stale = stale or bool(np.nanmax(drift) > lim) or not bool(np.isfinite(kap).all())
-        if stale:
-            if self.verbose:
-                print(" AMG(EMI): hierarchy refreshed (kappa drift / iteration count)")
-            self._setup_amg_emi()
-            self.amg_refreshes = getattr(self, "amg_refreshes", 0) + 1
-            self._amg_refresh = {"solves": 0, "ref": None, "high": 0}
 
     def setup_solver_knp(self):
         if self.use_amg and not self.direct_knp:
-            if self.__dict__.pop("_knp_amg_uploaded_early", False):
-                return
-            self._setup_amg_knp()
+            self.amg.setup_knp(self.dev)
         else:
-            self._drop_knp_helper()
+            self.amg.drop_knp_helper()
         return
 
-    def _drop_knp_helper(self):
-        helper = getattr(self, "_knp_helper", None)
-        if helper is not None:
-            from knpemidg import setup_worker
-            self._knp_helper = None
-            setup_worker.cancel(helper[0])
-
-    def _amg_global(self):
-        """(mesh, subdomains, surfaces) the conforming hierarchy is built on: the global mesh when this solver
-        holds one partition of it (make_distributed_solver), else its own mesh."""
-        from knpemidg import amg
-        g = getattr(self, "global_mesh_tuple", None) or (self.mesh, self.subdomains, self.surfaces)
-        if not hasattr(self, "_cspace"):
-            self._cspace = amg.ConformingSpace(g[0], g[2].array(), self.membrane_tags)
-            if self.degree_knp != 1:
-                self._cspace2 = amg.ConformingSpaceP2(self._cspace)
-        return g
-
-    def _dist0(self):
-        """Row distribution of the finest conforming level over the ranks of a partitioned run (amg.Dist0Space; the reference's BoomerAMG
-        is row-distributed by PETSc, solver.py:433, 688), with the shared-dof tables handed to the device on the first call; None on one
-        rank and with KNP_AMG_DIST0=0 (replicated level 0 behind an all-reduce of the level-0 residual, rounds 1-2)."""
-        loc = getattr(self, "local_mesh", None)
-        if loc is None or getattr(loc, "part", None) is None or loc.part.world < 2 or os.environ.get("KNP_AMG_DIST0", "1") == "0":
-            return None
-        d0 = getattr(self, "_dist0_space", None)
-        if d0 is None:
-            from knpemidg import amg
-            gmesh, gsub, gsurf = self._amg_global()
-            space = self._cspace if self.degree_knp == 1 else self._cspace2
-            mem = np.nonzero((gmesh.facet_cells[:, 1] >= 0) & np.isin(np.asarray(gsurf.array()), list(self.membrane_tags)))[0]
-            d0 = amg.Dist0Space(space, loc.part.owner, mem, loc.rank, loc.part.world)
-            self.dev.amg_interface(d0.n, *d0.interface_tables())
-            self._dist0_space = d0
-        return d0
-
-    def _local_dg2cg(self):
-        loc = getattr(self, "local_mesh", None)
-        if loc is None and not hasattr(self, "_cspace") and getattr(self, "_dg2cg_helper", None) is not None:
-            return self._dg2cg_helper             # spaces built by the helper process only (same deterministic numbering)
-        self._amg_global()
-        dof = self._cspace.dof if self.degree_knp == 1 else self._cspace2.dof
-        return dof if loc is None else dof[loc.cells_global]
-
-    @staticmethod
-    def _by_tag(d, subdomains):
-        tags = subdomains.array()
-        q = np.zeros(len(tags), dtype=np.float64)
-        for key, value in d.items():
-            q[tags == int(key)] = float(value)
-        return q
-
-    def _knp_level0_degree(self):
-        # one Jacobi step on the finest conforming level, on one GPU and on partitions alike.  (With a communicator the hierarchy is
-        # replicated and the restricted residual is all-reduced; a transfer-only finest level would let that happen on level 1 --
-        # 6.5x fewer bytes, no replicated level-0 SpMVs -- but costs 50 % more BiCGStab iterations: 9.9 instead of 6.6 per step in
-        # a 4-rank run of the r=2 mesh, which only pays for itself beyond 8 ranks.)
-        return 1
-
-    def _start_knp_helper(self):
-        """KNP hierarchies depend only on the mesh, D_k and dt: a helper process builds them while this process creates the device
-        context and the EMI hierarchy (knpemidg/setup_worker.py: why a process and not a thread).  KNP_AMG_SERIAL_SETUP=1 or a
-        failure of the helper: built in this process by setup_solver_knp."""
-        if not self.use_amg or os.environ.get("KNP_AMG_SERIAL_SETUP", "0") == "1" or getattr(self, "_knp_helper", None) is not None:
-            return
-        from knpemidg import setup_worker
-        g = getattr(self, "global_mesh_tuple", None) or (self.mesh, self.subdomains, self.surfaces)
-        d0 = self._knp_level0_degree()
-        job = setup_worker.job_from_solver(g[0], g[1].array(), g[2].array(), self.membrane_tags, self.degree_knp,
-                                           [ion['D_sub'] for ion in self.ion_list[:-1]], _f(self.params.dt), d0)
-        self._knp_helper = (setup_worker.start(job), d0)
-
-    def _build_amg_knp(self):
-        """[(members, levels)] of the KNP preconditioner (amg.build_knp_groups), built in this process."""
-        from knpemidg import amg
-        gmesh, gsub, gsurf = self._amg_global()
-        return amg.build_knp_groups(self._cspace, self._cspace2 if self.degree_knp != 1 else None, gsub.array(),
-                                    [ion['D_sub'] for ion in self.ion_list[:-1]], _f(self.dt), self._knp_level0_degree())
-
-    def _setup_amg_knp(self):
-        ts = time.perf_counter()
-        groups = None
-        helper = getattr(self, "_knp_helper", None)
-        if helper is not None:
-            from knpemidg import setup_worker
-            self._knp_helper = None
-            handle, d0 = helper
-            if d0 == self._knp_level0_degree():
-                groups = setup_worker.collect(handle)
-            else:                                   # the helper was started with another guess of the communicator state
-                setup_worker.cancel(handle)
-        if groups is None:
-            groups = self._build_amg_knp()
-        d0 = self._dist0()
-        for members, levels in groups:
-            local = None
-            if d0 is not None:                      # partitioned run: this rank's rows of the finest conforming level
-                local = d0.localize(levels)
-            if local is not None:
-                self.dev.amg_upload(1 + members[0], d0.local_dg2cg(self.local_mesh.cells_global), local, ncol=len(members), dist0=True)
-                self.amg_dist0 = getattr(self, "amg_dist0", 0) + 1
-            else:
-                self.dev.amg_upload(1 + members[0], self._local_dg2cg(), levels, ncol=len(members))
-            for k in members[1:]:
-                self.dev.amg_clear(1 + k)
-            if self.verbose:
-                print(" AMG(KNP %s) levels:" % "+".join(self.ion_list[k]['name'] for k in members), [lv.A.shape[0] for lv in levels])
-        self.amg_setup_timer = getattr(self, "amg_setup_timer", 0.0) + time.perf_counter() - ts
-
     def _read_solver_params(self):
-        sp = getattr(self, "solver_params", None)
-        self.max_it_emi = int(getattr(sp, "max_it_emi", self.max_it_emi))
-        self.max_it_knp = int(getattr(sp, "max_it_knp", self.max_it_knp))
-        # direct solvers (MUMPS, solver.py:412-422, 671-681) have no device counterpart: emulate with a tight
-        # iterative tolerance
-        # PETSc tests ||M^-1 r|| <= rtol ||M^-1 b|| with M = BoomerAMG (solver.py:425-444); with this build's preconditioner the
-        # same nominal rtol 1e-5 leaves mean-free phi accurate to 1e-4 of its maximum but the concentrations only to 3e-5
-        # (they inherit the RELATIVE error of phi through the drift and membrane terms), measured against direct solves
-        # through an action potential (tests/test_gpu_trajectory.py, tools/tolerance_sweep.py).  The nominal tolerance is
-        # therefore scaled so that the stated parity bounds (c <= 1e-6, phi <= 1e-4) hold at every step.
-        # DG-P2 needs a 4x tighter potential for the same bound on c (configs[2], r=1, 40 steps: worst c 1.8e-6 / 1.1e-6 / 6.2e-7
-        # at scale 2e-3 / 1e-3 / 5e-4; a tighter KNP tolerance changes nothing): profiles/r02_tolerance_p2_r1.txt
-        # The factor is a property of (mesh family, degree), not a constant: the weaker the preconditioner on a mesh, the larger
-        # the error behind a given residual (EMIx reconstruction, 13-36 EMI iterations per solve: worst c 7.1e-6 at the idealized
-        # mesh's settings; there the KNP residual test needs tightening too).  `emi_rtol_scale` / `knp_rtol_scale` in
-        # solver_params set the factors per configuration (examples/emix_simulations: 1e-4 / 0.03, profiles/r02_tolerance_emix.txt);
-        # tools/tolerance_sweep.py / tools/tolerance_emix.py measure them.
-        # ROUND 3: the per-mesh factors above are replaced by an error-controlled stop.  The EMI solve stops when its residual, in the
-        # cell-volume-weighted norm, is small enough for the concentration accuracy wanted (knp_emi_residual_target,
-        # csrc/solve.hip): r_abs = theta * c_tol * F * min_k |z_k| ||b_knp,k||_w with c_tol = 0.1 * rtol_emi (the reference pairs
-        # rtol_emi 1e-5 with concentrations good to 1e-6) and ONE safety factor theta for every mesh family and degree
-        # (EMI_TARGET_SAFETY below; measured: profiles/r03_error_controlled_stop.txt).  `emi_rtol_scale` in solver_params (or
-        # KNP_EMI_RTOL_SCALE, tools only) selects the old preconditioned-norm test with that factor instead.
-        dflt = getattr(sp, "emi_rtol_scale", None)
-        if dflt is None and "KNP_EMI_RTOL_SCALE" in os.environ:
-            dflt = float(os.environ["KNP_EMI_RTOL_SCALE"])
-        rt = float(self.rtol_emi) if not self.direct_emi else 0.0
-        self._emi_target = None
-        if self.direct_emi:
-            self._rtol_emi = float(getattr(sp, "rtol_direct", 1e-10))
-        elif dflt is not None:
-            self._rtol_emi = max(rt * float(dflt), min(rt, 1.0e-11))
-        else:
-            c_tol = float(getattr(sp, "c_tol", None) or 0.1 * rt)
-            theta = float(getattr(sp, "emi_target_safety", None) or os.environ.get("KNP_EMI_TARGET_SAFETY", EMI_TARGET_SAFETY / self.degree_emi ** 2))
-            self._emi_target = theta * c_tol
-            # Second half of the stop (csrc/krylov.hip: cg_converged): the energy-norm error of the iterate, estimated from the CG
-            # coefficients, relative to ||phi||_A.  Round 3 tested the preconditioned norm ||M^-1 r|| here, which under-reports the
-            # error by a factor that depends on M (a better preconditioner met it with MORE error left); the Hestenes-Stiefel estimate
-            # measures the error itself and holds for any SPD preconditioner.
-            self._rtol_emi = float(getattr(sp, "emi_energy_factor", None) or os.environ.get("KNP_EMI_ENERGY_FACTOR", PHI_ENERGY_FACTOR)) * rt
-        self._atol_emi = 1e-40 if self.direct_emi else float(self.atol_emi)
-        ks = getattr(sp, "knp_rtol_scale", None)
-        if ks is None and "KNP_KNP_RTOL_SCALE" in os.environ:
-            ks = float(os.environ["KNP_KNP_RTOL_SCALE"])
-        kscale = float(ks) if ks is not None else 1.0
-        rk = float(self.rtol_knp) if not self.direct_knp else 0.0
-        # direct_knp (MUMPS in the reference) is emulated by a tightly converged solve: rtol_direct is meant for the residual itself, so the
-        # factor 20 the device puts on the order-8 density test (csrc/solve.hip: KNP_D8_FACTOR) is divided out here (ADVICE r3)
-        self._rtol_knp = float(getattr(sp, "rtol_direct", 1e-10)) / 20.0 if self.direct_knp else max(rk * kscale, min(rk, 1.0e-13))
+        s = self.settings = resolve_settings(
+            self.solver_params, degree_emi=self.degree_emi, rtol_emi=self.rtol_emi, atol_emi=self.atol_emi, rtol_knp=self.rtol_knp,
+            atol_knp=self.atol_knp, direct_emi=self.direct_emi, direct_knp=self.direct_knp, max_it_emi=self.max_it_emi,
+            max_it_knp=self.max_it_knp)
+        (self.max_it_emi, self.max_it_knp, self._rtol_emi, self._atol_emi, self._emi_target, self._rtol_knp, self._atol_knp, _, _,
+         self._knp_min_it, self._knp_early) = s
         if self.verbose:
             print(" effective tolerances: EMI %s, KNP rtol %.2e (weighted residual norm)" % (
-                ("residual target %.2e x F min|z| ||b_knp||" % self._emi_target) if self._emi_target else "rtol %.2e" % self._rtol_emi,
-                self._rtol_knp))
-        self._atol_knp = 1e-40 if self.direct_knp else float(self.atol_knp)
-        # KNP Krylov method: the device default is BiCGStab; `knp_krylov = "gmres"` (+ `gmres_restart`, default 30) in solver_params,
-        # or KNP_KNP_KRYLOV=gmres, selects the reference's restarted GMRES (ksp_type gmres / ksp_gmres_restart 30, solver.py:684-701)
-        meth = getattr(sp, "knp_krylov", None) or os.environ.get("KNP_KNP_KRYLOV", "bicgstab")
-        # ksp_min_it 5 of the reference's GMRES (solver.py:686) = at least five operator + preconditioner applications.  A BiCGStab
-        # iteration makes two of each, so three iterations (six applications) would honour it; rounds 1-3 forced five iterations = ten
-        # applications, and the solves of the quiet phases of a run stopped at exactly that floor.  FOUR is the measured optimum: the
-        # forced iterations of the quiet steps are what keeps the per-step errors from adding up over a run (r=1, 40 steps, worst c
-        # against tight solves: min_it 3: 9.0e-7 at 3.95 iterations per step, 4: 2.2e-7 at 4.47, 5: 2.1e-7 at 5.12; tightening the
-        # residual test instead buys less per iteration: factor 10 at min_it 3: 5.8e-7 at 4.70; profiles/r04_min_it.txt,
-        # r04_stop_sweep.txt).  KNP_KNP_MIN_IT / solver_params.knp_min_it change it.
-        self._knp_min_it = int(getattr(sp, "knp_min_it", None) or os.environ.get("KNP_KNP_MIN_IT", 5 if meth == "gmres" else 4))
-        # The floor is there for the quiet phases; a solve whose residual is already 100x UNDER the tolerance needs no forced iterations
-        # for that purpose (knp_knp_early_stop).  Over the reference's 200-step run at r=2: 4.20 -> 3.54 KNP iterations per step, KNP time
-        # -16 %, worst c / phi over 100 steps unchanged to three digits at r=1 and r=2 (2.31e-7 / 2.15e-7: they come from the action
-        # potential, where the floor does not bind); a factor 0.1 instead of 0.01: 2.57 iterations but c 7.2e-7 at r=1
-        # (profiles/r04_early_stop_sweep.txt).  solver_params.knp_early_stop / KNP_KNP_EARLY set the factor, 0 switches it off.
-        early = getattr(sp, "knp_early_stop", None)
-        if early is None:
-            early = float(os.environ.get("KNP_KNP_EARLY", 0.01))
-        self._knp_early = 0.0 if self.direct_knp else float(early)
+                ("residual target %.2e x F min|z| ||b_knp||" % s.emi_target) if s.emi_target else "rtol %.2e" % s.rtol_emi, s.rtol_knp))
         if self.dev is not None:
-            self.dev.knp_early_stop(self._knp_early)
-        if self.dev is not None and meth != getattr(self, "_knp_krylov", "bicgstab"):
-            self.dev.set_knp_krylov(meth, int(getattr(sp, "gmres_restart", None) or os.environ.get("KNP_GMRES_RESTART", 30)))
-            self._knp_krylov = meth
+            self.dev.knp_early_stop(s.knp_early)
+        if self.dev is not None and s.knp_krylov != self._knp_krylov:
+            self.dev.set_knp_krylov(s.knp_krylov, s.gmres_restart)
+            self._knp_krylov = s.knp_krylov
 
     def _sync_membrane_to_device(self):
         """phi_M and I_ch_k facet fields produced by the ODE step -> device."""
@@ -927,12 +732,13 @@ class Solver:
             r_abs = self._emi_target * _f(self.F) * self._knp_load_norm()
             self.emi_targets.append(r_abs)            # identical on every rank of a partitioned run (tests/test_gpu_multirank.py)
             dev.emi_residual_target(r_abs)
-        if getattr(self, "_emi_trial", None) is not None and self._emi_target and self.use_amg and not self.direct_emi:
+        amg = self.use_amg and not self.direct_emi
+        if amg and self.emi_smoother.pending and self._emi_target:
             def one_solve():
                 t0 = time.perf_counter()
                 n_, r_ = dev.emi_solve(self._rtol_emi, self._atol_emi, maxit=self.max_it_emi)
                 return time.perf_counter() - t0, n_, r_
-            _, niter, r = self._emi_smoother_trial(one_solve)
+            _, niter, r = self.emi_smoother.run_trial(one_solve)
         else:
             niter, r = dev.emi_solve(self._rtol_emi, self._atol_emi, maxit=self.max_it_emi)
         te = time.perf_counter()
@@ -941,7 +747,8 @@ class Solver:
             print(f"{bcolors.OKGREEN} GPU Execution time PDE solve emi: {res:.4f} seconds ({niter} its) {bcolors.ENDC}")
         self.emi_solve_timer += res
         self.emi_niter.append(niter)
-        self._maybe_refresh_amg_emi(niter)
+        if amg:
+            self.amg.maybe_refresh_emi(dev, self.emi_niter)
         if self.save_solver_stats:
             if not self.direct_emi:
                 self.file_emi_niter.write("niter: %d \n" % niter)
@@ -952,7 +759,7 @@ class Solver:
         """min_k |z_k| ||b_knp,k / vol||_8: size of the KNP load vectors (~ M c_k / dt) in the density norm of order 8 the solvers test
         (csrc/krylov.hip) -- from the previous KNP solve; before the first one, from the right-hand side of the initial state."""
         z = np.abs([float(ion['z']) for ion in self.ion_list[:-1]])
-        bn = getattr(self, "_knp_bnorm", None)
+        bn = self._knp_bnorm
         if bn is None:
             dev = self.dev
             _abi._stamp("first step: EMI right-hand side ready")
@@ -970,7 +777,7 @@ class Solver:
     def solve_knp(self):
         dev = self.dev
         ts = time.perf_counter()
-        self._update_sources(getattr(self, "_t_now", 0.0))
+        self._update_sources(self._t_now)
         dev.update_dnphi()
         dev.knp_rhs()
         dev.sync()
@@ -1049,7 +856,7 @@ class Solver:
         self.dev.step_updates()                             # c_prev_n <- c_prev_k, phi_M, (E_k, c_elim unchanged)
         if self.recorder is not None:
             self.recorder.sample(float(t))
-        self.picard_iters = getattr(self, "picard_iters", []) + [it]
+        self.picard_iters = self.picard_iters + [it]
         self._k_done, self._t_done, self._picard = k + 1, float(t), True
         if self.verbose:
             print(f" Summary Picard: eps = {eps}, #iters = {it}")
@@ -1074,7 +881,7 @@ class Solver:
             sys.exit(0)
         # a resumed run writes a SECOND PART next to the files of the first: results_from<k>.h5 (with /step_offset = k; its vector_0 is the
         # restored state) and solver_from<k>/; timeseries.h5 is written whole, the recorder carries the rows of the first part
-        k0 = int(getattr(self, "_resume_k", 0) or 0)
+        k0 = int(self._resume_k or 0)
         part = "_from%d" % k0 if k0 else ""
         if self.save_fields:
             self.init_h5_savefile(filename + 'results%s.h5' % part)                 # solver.py:978, 1063
@@ -1184,9 +991,9 @@ class Solver:
         return int(every), path
 
     def _checkpoint_mode(self, picard=None):
-        if picard if picard is not None else getattr(self, "_picard", False):
+        if picard if picard is not None else self._picard:
             return "picard"
-        return "splitting" if getattr(self, "splitting_scheme", True) else "passive"
+        return "splitting" if self.splitting_scheme else "passive"
 
     def _checkpoint_header(self, picard=None):
         """The fields a checkpoint is checked against (checkpoint.CHECKED_FIELDS) plus what a reader wants to know about the run."""
@@ -1197,8 +1004,8 @@ class Solver:
         for entry, m in zip(models, self.mem_models):        # only when it is not the default: files from before the choice keep loading
             if m['ode'].ode_method != "dp5":
                 entry["ode_method"] = m['ode'].ode_method
-        sp = getattr(self, "solver_params", None)
-        ref = getattr(self, "_amg_refresh", None) or {}
+        sp = self.solver_params
+        smoother = self.emi_smoother
         return {
             "dt": float(self.dt),
             "ions": [[str(ion['name']), float(ion['z'])] for ion in self.ion_list],
@@ -1210,10 +1017,9 @@ class Solver:
             "rtc_hash": [checkpoint.source_hash(getattr(m['ode'].ode, "HIP_RHS", None)) for m in self.mem_models],
             "solver_params": {k: (v if isinstance(v, (bool, int, float, str, type(None))) else repr(v)) for k, v in sp._asdict().items()}
             if hasattr(sp, "_asdict") else None,
-            "emi_dg_chebyshev": getattr(self, "_emi_cheb_chosen", None) if (self.use_amg and not getattr(self, "direct_emi", False)) else None,
-            "emi_trial_pending": getattr(self, "_emi_trial", None) is not None,
-            "amg_refresh": {"solves": int(ref.get("solves", 0)), "ref": ref.get("ref"), "high": int(ref.get("high", 0)),
-                            "refreshes": int(getattr(self, "amg_refreshes", 0))},
+            "emi_dg_chebyshev": smoother.chosen if (smoother is not None and self.use_amg and not self.direct_emi) else None,
+            "emi_trial_pending": smoother is not None and smoother.pending,
+            "amg_refresh": self.amg.state(),
         }
 
     def save_checkpoint(self, path, t=None, k=None):
@@ -1223,18 +1029,18 @@ class Solver:
         from knpemidg import checkpoint
         if self.dev is None:
             raise _abi.KnpError("save_checkpoint: no device context yet")
-        if getattr(self, "local_mesh", None) is not None or getattr(self, "nc_owned", None) is not None or self.dev.nranks > 1:
+        if self.local_mesh is not None or self.nc_owned is not None or self.dev.nranks > 1:
             raise _abi.KnpError("save_checkpoint: not supported with several ranks (checkpoint a one-GPU run)")
         header = self._checkpoint_header()
-        header["k"] = int(getattr(self, "_k_done", 0) if k is None else k)
-        header["t"] = float(getattr(self, "_t_done", 0.0) if t is None else t)
+        header["k"] = int(self._k_done if k is None else k)
+        header["t"] = float(self._t_done if t is None else t)
         table, arrays = checkpoint.split_snapshot(self.dev.state_save())
         extra = {"emi_niter": np.asarray(self.emi_niter, dtype=np.int64),
                  "knp_niter": np.asarray(self.knp_niter, dtype=np.int64).reshape(len(self.knp_niter), max(self.N_ions, 1)),
                  "emi_targets": np.asarray(self.emi_targets, dtype=np.float64),
-                 "picard_iters": np.asarray(getattr(self, "picard_iters", []), dtype=np.int64),
+                 "picard_iters": np.asarray(self.picard_iters, dtype=np.int64),
                  "model_time": np.asarray([float(m['ode'].time) for m in self.mem_models], dtype=np.float64)}
-        if getattr(self, "_knp_bnorm", None) is not None:
+        if self._knp_bnorm is not None:
             extra["knp_bnorm"] = np.asarray(self._knp_bnorm, dtype=np.float64)
         for i, m in enumerate(self.mem_models):
             extra.update(m['ode'].host_state("model%d_" % i))
@@ -1250,18 +1056,14 @@ class Solver:
         from knpemidg import checkpoint
         if self.dev is None:
             raise _abi.KnpError("load_checkpoint: no device context yet")
-        if getattr(self, "local_mesh", None) is not None or getattr(self, "nc_owned", None) is not None or self.dev.nranks > 1:
+        if self.local_mesh is not None or self.nc_owned is not None or self.dev.nranks > 1:
             raise _abi.KnpError("load_checkpoint: not supported with several ranks (checkpoint a one-GPU run)")
         header, table, arrays, extra = checkpoint.read_checkpoint(path)
         checkpoint.check_header(header, dict(self._checkpoint_header(picard), format_version=checkpoint.FORMAT_VERSION), "checkpoint %s" % path)
         checkpoint.check_table(table, self.dev.state_describe()[0], "checkpoint %s" % path)
-        amg = self.use_amg and not getattr(self, "direct_emi", False)
+        amg = self.use_amg and not self.direct_emi
         if amg and header.get("emi_dg_chebyshev") is not None and not header.get("emi_trial_pending"):
-            explicit = getattr(getattr(self, "solver_params", None), "emi_dg_chebyshev", None)
-            chosen = bool(header["emi_dg_chebyshev"]) if explicit is None else bool(explicit)
-            self.dev.set_emi_dg_smoother(chosen)               # before the state: a change of smoother drops the spectral bound
-            self._emi_cheb_chosen = chosen
-            self._emi_trial = None                             # no trial solves in a resumed run
+            self.emi_smoother.resume(header["emi_dg_chebyshev"])           # before the state: a change of smoother drops the spectral bound
         self.dev.state_load(checkpoint.join_snapshot(table, arrays))
         self.emi_niter = [int(v) for v in extra.get("emi_niter", [])]
         self.knp_niter = [[int(v) for v in row] for row in extra.get("knp_niter", np.zeros((0, self.N_ions)))]
@@ -1274,13 +1076,10 @@ class Solver:
             m['ode'].load_host_state("model%d_" % i, extra)
         if self.recorder is not None:
             self.recorder.load_host_state("recorder_", extra)
-        ref = header.get("amg_refresh") or {}
-        self._amg_refresh = {"solves": int(ref.get("solves", 0)), "ref": ref.get("ref"), "high": int(ref.get("high", 0))}
-        if ref.get("refreshes"):
-            self.amg_refreshes = int(ref["refreshes"])
+        self.amg.restore(header.get("amg_refresh"))
         if amg:
-            self._drop_emi_helper()
-            self._setup_amg_emi()                              # from the restored kappa
+            self.amg.drop_emi_helper()
+            self.amg.setup_emi(self.dev)                       # from the restored kappa
         self._k_done, self._t_done = int(header["k"]), float(header["t"])
         self._resume_k = self._k_done
         if header["mode"] == "picard":
@@ -1353,7 +1152,7 @@ class Solver:
         from knpemidg.h5lite import H5Writer
         self.h5_idx = 0
         os.makedirs(os.path.dirname(filename) or ".", exist_ok=True)
-        loc = getattr(self, "local_mesh", None)
+        loc = self.local_mesh
         rank_sfx = "" if loc is None else "_rank%d" % getattr(self.dev, "rank", loc.rank)
         stem, ext = os.path.splitext(filename)                      # the reference passes the full file name (solver.py:978, 1214)
         self.h5_path = stem + rank_sfx + (ext or ".h5")

@@ -455,63 +455,6 @@ def test_knp_hierarchy_helper_process_matches_in_process(degree):
     assert setup_worker.collect(bad) is None
 
 
-def test_emi_dg_smoother_is_chosen_by_measurement():
-    """knpemidg/solver.py: Solver._emi_dg_chebyshev / _emi_smoother_trial -- round 3 read the DG-level smoother of the EMI preconditioner
-    off mesh-size thresholds; round 4 measures it on the first EMI system of the run: the same system is solved from the same initial
-    guess with and without the Chebyshev step (one untimed solve each first), each charged its time per decade of true-residual
-    reduction, the costs all-reduced (every rank of a partitioned run takes the same decision), the step dropped only if that is
-    >= 3 % cheaper; the step's solution comes from a solve with the chosen variant; solver_params / KNP_EMI_CHEB decide explicitly."""
-    from collections import namedtuple
-    from knpemidg.solver import Solver
-
-    class Dev:
-        def __init__(self):
-            self.calls, self.reduced, self.uploads = [], [], 0
-
-        def set_emi_dg_smoother(self, on):
-            self.calls.append(bool(on))
-
-        def allreduce_sum(self, v):
-            self.reduced.append(list(v))
-            return np.asarray(v, dtype=float) * 3.0          # three ranks with the same timings
-
-        def download(self, field):
-            return np.zeros(4)
-
-        def upload(self, field, a):
-            self.uploads += 1
-
-    def run(cost_on, cost_off, explicit=None):
-        S = Solver.__new__(Solver)
-        S.verbose = False
-        S.dev = Dev()
-        if explicit is not None:
-            S.solver_params = namedtuple("solver_params", ("emi_dg_chebyshev",))(explicit)
-        first = S._emi_dg_chebyshev()
-        if S._emi_trial is None:
-            return first, S.dev.calls, None, None
-
-        def solve():                                         # one decade of reduction: seconds = cost per decade
-            on = S.dev.calls[-1]
-            return (cost_on if on else cost_off), (7 if on else 9), [1.0, 0.1, 0.0]
-        out = S._emi_smoother_trial(solve)
-        assert S._emi_trial is None and len(S.dev.reduced) == 1
-        return first, S.dev.calls, S.emi_dg_chebyshev_measured, out
-
-    first, calls, m, out = run(1.0, 0.8)                      # plain block-Jacobi 20 % cheaper per decade: dropped
-    assert first is True and calls == [True, False, True, False] and m["chosen"] is False and out[1] == 9
-    first, calls, m, out = run(1.0, 0.99)                     # within the 3 % margin: the step stays, the step's solve is redone with it
-    assert calls == [True, False, True, False, True] and m["chosen"] is True and out[1] == 7
-    first, calls, m, out = run(1.0, 1.25)
-    assert calls[-1] is True and abs(m["plain_s_per_decade"] - 3.0 * 1.25) < 1e-12
-    assert run(None, None, explicit=False)[0] is False and run(None, None, explicit=True)[0] is True      # explicit: no trial
-    os.environ["KNP_EMI_CHEB"] = "0"
-    try:
-        assert run(None, None)[0] is False
-    finally:
-        del os.environ["KNP_EMI_CHEB"]
-
-
 def test_native_setup_kernels_match_numpy():
     """Host setup kernels of the library (csrc/host_sparse.cpp, round 4) against the numpy code they replace: facet table (identical
     numbering), geometry classes (same grouping, same records), cell Gram matrices, the CSR pattern of the conforming operators

@@ -1,5 +1,5 @@
 #!/bin/bash
-# DG-level Chebyshev step of the EMI preconditioner: default (decided per mesh by Solver._emi_dg_chebyshev) against forced on / off
+# DG-level Chebyshev step of the EMI preconditioner: default (decided per run by precond.SmootherChoice) against forced on / off
 # -> gpurun_out/r03_emi_dg_smoother.txt (committed as profiles/r03_emi_dg_smoother.txt together with the accuracy runs named there)
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
 o=gpurun_out/r03_emi_dg_smoother.txt
