@@ -446,6 +446,33 @@ int knp_grid_fetch(knp_ctx* ctx, int grid, void* out, size_t bytes);
 int knp_grid_destroy(knp_ctx* ctx, int grid);
 int knp_grid_timing(knp_ctx* ctx, int grid, float* locate_ms, float* weights_ms, float* sample_ms, float* copy_ms);
 
+/* ---- membrane-surface snapshots (csrc/surface.hip) ----------------------------------------
+ * Per selected membrane facet (the caller's facet ids, ascending) a frame [n_fields + n_states][n] of facet quantities, one
+ * thread per facet.  kind[q] / ion[q] of field plane q:
+ *   KNP_SF_PHI_M       PHI_M[f]                       KNP_SF_I_CH_TOTAL  sum_k I_CH[k nf + f], added in ion order
+ *   KNP_SF_E           E[ion nf + f]                  KNP_SF_TRACE_E     facet mean of the trace from cell_e (the `plus` side) ...
+ *   KNP_SF_I_CH        I_CH[ion nf + f]               KNP_SF_TRACE_I     ... and from cell_i (`minus`) of phi (ion -1) or of concentration `ion`
+ * (ion n_ions - 1 is the eliminated one; the facet mean is what knp_facet_trace writes: P1 the mean of the facet's vertex values, P2
+ * the exact mean of the quadratic).  State plane s holds, per facet, column state_col of row state_row of the state table of ODE handle
+ * state_handle -- tables [n_states][n]; handle -1: the facet's model has no such state, the plane holds NaN there.
+ *  knp_surf_create : returns a handle (0 .. 3) or a negative code.  Everything is checked on the host before anything is allocated or
+ *                    uploaded and a failure leaves the context as it was: -7 with several ranks; -1 for facets that are not ascending
+ *                    or not membrane facets of the context, unknown kinds, ions out of range, unknown ODE handles, rows or columns
+ *                    outside their table, parameters never set (E, I_ch), a fifth sampler.  f32 != 0: frames in fp32 (the fp64 value
+ *                    rounded once).
+ *  knp_surf_sample : one frame of the state as it is now: kernel, asynchronous copy into one of two pinned host buffers and an event;
+ *                    -5 when both buffers wait to be fetched
+ *  knp_surf_fetch  : waits for the event of the oldest waiting frame only and copies it to out[bytes], bytes = planes x n x 8 (4)
+ *  knp_surf_timing : device milliseconds of the kernel and the copy of the last fetched frame
+ * A sampler holds no step-to-step state: knp_state_describe is the same with and without one. */
+typedef enum { KNP_SF_PHI_M = 0, KNP_SF_E = 1, KNP_SF_I_CH = 2, KNP_SF_I_CH_TOTAL = 3, KNP_SF_TRACE_E = 4, KNP_SF_TRACE_I = 5 } knp_surf_kind;
+int knp_surf_create(knp_ctx* ctx, int64_t n, const int32_t* facets, int n_fields, const int32_t* kind, const int32_t* ion, int n_states,
+                    const int32_t* state_handle, const int64_t* state_row, const int32_t* state_col, int f32);
+int knp_surf_sample(knp_ctx* ctx, int surf);
+int knp_surf_fetch(knp_ctx* ctx, int surf, void* out, size_t bytes);
+int knp_surf_destroy(knp_ctx* ctx, int surf);
+int knp_surf_timing(knp_ctx* ctx, int surf, float* sample_ms, float* copy_ms);
+
 /* ---- checkpoint of the step-to-step state (csrc/state.hip; DESIGN.md section 4.3 lists every member saved or rebuilt).
  * A snapshot is one host buffer: a 32-byte prologue (magic "KNPSTATE", version, block count, payload bytes), the block table
  * (one knp_state_block per block) and the payloads at the table's offsets.  A block is [ncomp][count][width] elements:

@@ -154,7 +154,11 @@ int knp_ctx_create(knp_ctx** out, int device, int dim, int degree, int n_ions, i
     c->h_fflag = T.fflag;
     c->h_ctag.assign(cell_tags, cell_tags + nc);
     c->h_mf_mask.assign((size_t)nf, 0);
-    for (size_t i = 0; i < T.mf.size(); i += 6) c->h_mf_mask[(size_t)T.mf[i + 4]] = 1;
+    c->h_mf_row.assign((size_t)nf, -1);
+    for (size_t i = 0; i < T.mf.size(); i += 6) {
+        c->h_mf_mask[(size_t)T.mf[i + 4]] = 1;
+        c->h_mf_row[(size_t)T.mf[i + 4]] = (int32_t)(i / 6);
+    }
     MeshDev& m = c->m;
     m.dim = dim; m.nv = nv; m.nc = nc; m.nc_owned = nc_owned; m.nf = nf; m.nmf = (int64_t)T.mf.size() / 6;
     m.c_begin = 0; m.c_end = nc_owned; m.n_interior = nc_owned;
@@ -181,6 +185,7 @@ void knp_ctx_destroy(knp_ctx* c) {
     for (auto st : c->aux_streams) hipStreamDestroy(st);
     for (auto ev : c->aux_events) hipEventDestroy(ev);
     if (c->fork_event) hipEventDestroy(c->fork_event);
+    surf_destroy_all(c);            // before the ODE tables its state addresses point into
     ode_destroy_all(c);
     source_destroy(c);
     rec_destroy(c);

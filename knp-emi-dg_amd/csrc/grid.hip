@@ -21,11 +21,13 @@
 // path reproduces owners and lambda bit for bit.
 //
 // Frames land in one of two pinned host buffers: kernel, asynchronous copy and an event on the context's stream;
-// knp_grid_fetch waits for that event only.  The grid holds no step-to-step state: it adds no checkpoint block.
+// knp_grid_fetch waits for that event only (frame_pipe.hpp, shared with surface.hip).  The grid holds no step-to-step state: it
+// adds no checkpoint block.
 // The grids of a context and its uploaded tag table are its GridState (knp_ctx::grid): created with the first grid, freed by
 // grid_destroy_all, shared with no other context.
 #include "../../include/knpemi_hip.h"
 #include "knpemi_internal.hpp"
+#include "frame_pipe.hpp"
 #include <cmath>
 #include <cstring>
 
@@ -71,11 +73,8 @@ struct Grid {
     int32_t* cell = nullptr;        // [npts] device cell, -1 outside
     int32_t* tag = nullptr;         // [npts] subdomain tag of the owner, -1 outside
     double* lam = nullptr;          // [dim + 1][npts]
-    void* frame = nullptr;          // device [planes()][npts]: the nodal planes, then dim component planes (x first) per derived quantity
-    void* pinned[2] = {nullptr, nullptr};
-    hipEvent_t ev[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};   // per buffer: before the kernel, after it, after the copy
-    int64_t sampled = 0, fetched = 0;   // frames enqueued / handed out; frame n lives in buffer n & 1
-    float locate_ms = 0.f, weights_ms = 0.f, sample_ms = 0.f, copy_ms = 0.f;
+    FramePipe pipe;                 // frame [planes()][npts]: the nodal planes, then dim component planes (x first) per derived quantity
+    float locate_ms = 0.f, weights_ms = 0.f;
     int planes() const { return n_fields + dim * n_derived; }
     size_t frame_bytes() const { return (size_t)planes() * (size_t)npts * (f32 ? 4 : 8); }
 };
@@ -301,7 +300,7 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_grid_sample(int64_t npts, const i
 
 template <int D, int P, typename OUT> void sample_launch(knp_ctx* c, const Grid& g, const GridFields& F) {
     hipLaunchKernelGGL((k_grid_sample<D, P, OUT>), dim3((unsigned)grid_for(g.npts)), dim3(KNP_BLOCK), 0, c->stream, g.npts, g.cell, g.lam, F,
-                       (OUT*)g.frame);
+                       (OUT*)g.pipe.frame);
 }
 template <int D, int P> void sample_type(knp_ctx* c, const Grid& g, const GridFields& F) {
     if (g.f32) sample_launch<D, P, float>(c, g, F);
@@ -419,7 +418,7 @@ __global__ __launch_bounds__(KNP_BLOCK) void k_grid_sample_derived(int64_t npts,
 
 template <int D, int P, typename OUT> void derived_launch(knp_ctx* c, const Grid& g, const GridDerived& Q) {
     hipLaunchKernelGGL((k_grid_sample_derived<D, P, OUT>), dim3((unsigned)grid_for(g.npts)), dim3(KNP_BLOCK), 0, c->stream, g.npts, g.cell, g.lam,
-                       c->m.coords, c->m.cells, Q, (OUT*)g.frame + (int64_t)g.n_fields * g.npts);
+                       c->m.coords, c->m.cells, Q, (OUT*)g.pipe.frame + (int64_t)g.n_fields * g.npts);
 }
 template <int D, int P> void derived_type(knp_ctx* c, const Grid& g, const GridDerived& Q) {
     if (g.f32) derived_launch<D, P, float>(c, g, Q);
@@ -428,12 +427,8 @@ template <int D, int P> void derived_type(knp_ctx* c, const Grid& g, const GridD
 
 void grid_free(Grid* g) {
     if (!g) return;
-    hipFree(g->owner); hipFree(g->cell); hipFree(g->tag); hipFree(g->lam); hipFree(g->frame);
-    for (int b = 0; b < 2; ++b) {
-        if (g->pinned[b]) hipHostFree(g->pinned[b]);
-        for (auto e : g->ev[b])
-            if (e) hipEventDestroy(e);
-    }
+    hipFree(g->owner); hipFree(g->cell); hipFree(g->tag); hipFree(g->lam);
+    g->pipe.release();
     delete g;
 }
 
@@ -526,12 +521,8 @@ int knp_grid_create_derived(knp_ctx* c, const double* lo, const double* h, const
     uint32_t* ctag = c->grid ? c->grid->ctag : nullptr;
     const bool own_ctag = ctag == nullptr;
     bool ok = hipMalloc((void**)&g->owner, 4 * np) == hipSuccess && hipMalloc((void**)&g->cell, 4 * np) == hipSuccess &&
-              hipMalloc((void**)&g->tag, 4 * np) == hipSuccess && hipMalloc((void**)&g->lam, 8 * np * (size_t)(d + 1)) == hipSuccess &&
-              hipMalloc(&g->frame, g->frame_bytes()) == hipSuccess;
-    for (int b = 0; b < 2 && ok; ++b) {
-        ok = hipHostMalloc(&g->pinned[b], g->frame_bytes()) == hipSuccess;
-        for (auto& e : g->ev[b]) ok = ok && hipEventCreate(&e) == hipSuccess;
-    }
+              hipMalloc((void**)&g->tag, 4 * np) == hipSuccess && hipMalloc((void**)&g->lam, 8 * np * (size_t)(d + 1)) == hipSuccess;
+    ok = ok && g->pipe.alloc(g->frame_bytes());
     if (ok && own_ctag) ok = hipMalloc((void**)&ctag, 4 * (size_t)std::max<int64_t>(m.nc, 1)) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
@@ -550,14 +541,14 @@ int knp_grid_create_derived(knp_ctx* c, const double* lo, const double* h, const
         if (own_ctag && m.nc) HIPCHK(c, host_memcpy(c, ctag, c->h_ctag.data(), 4 * (size_t)m.nc, hipMemcpyHostToDevice));
         const int32_t* rank = state_cell_rank(c);
         HIPCHK(c, hipMemsetAsync(g->owner, 0x7f, 4 * np, c->stream));
-        HIPCHK(c, hipEventRecord(g->ev[0][0], c->stream));
+        HIPCHK(c, hipEventRecord(g->pipe.ev[0][0], c->stream));
         if (m.nc) DISPATCH_DIM(c, k_grid_locate, dim3((unsigned)grid_for(m.nc)), m.nc, m.coords, m.cells, rank, ctag, T, g->G, tol, g->owner);
-        HIPCHK(c, hipEventRecord(g->ev[0][1], c->stream));
+        HIPCHK(c, hipEventRecord(g->pipe.ev[0][1], c->stream));
         DISPATCH_DIM(c, k_grid_weights, dim3((unsigned)grid_for(g->npts)), g->npts, m.coords, m.cells, rank, ctag, g->G, g->owner, g->cell, g->tag, g->lam);
-        HIPCHK(c, hipEventRecord(g->ev[0][2], c->stream));
+        HIPCHK(c, hipEventRecord(g->pipe.ev[0][2], c->stream));
         HIPCHK(c, host_stream_sync(c, c->stream));
-        HIPCHK(c, hipEventElapsedTime(&g->locate_ms, g->ev[0][0], g->ev[0][1]));
-        HIPCHK(c, hipEventElapsedTime(&g->weights_ms, g->ev[0][1], g->ev[0][2]));
+        HIPCHK(c, hipEventElapsedTime(&g->locate_ms, g->pipe.ev[0][0], g->pipe.ev[0][1]));
+        HIPCHK(c, hipEventElapsedTime(&g->weights_ms, g->pipe.ev[0][1], g->pipe.ev[0][2]));
         return 0;
     };
     if ((rc = run())) {
@@ -583,7 +574,6 @@ int knp_grid_sample(knp_ctx* c, int grid) {
     Grid* gp = grid_find(c, grid, "knp_grid_sample");
     if (!gp) return -1;
     Grid& g = *gp;
-    if (g.sampled - g.fetched >= 2) { c->err = "knp_grid_sample: both frame buffers wait to be fetched (knp_grid_fetch)"; return -5; }
     const int n_sys = c->p.n_sys;
     const int64_t ndof = c->m.nc * c->nd;
     const double* cc = knp_field_ptr(c, KNP_F_C, nullptr);
@@ -594,9 +584,8 @@ int knp_grid_sample(knp_ctx* c, int grid) {
         const int id = g.field[q];
         F.f[q] = id == 0 ? knp_field_ptr(c, KNP_F_PHI, nullptr) : (id <= n_sys ? cc + (int64_t)(id - 1) * ndof : knp_field_ptr(c, KNP_F_C_ELIM, nullptr));
     }
-    const int b = (int)(g.sampled & 1);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipEventRecord(g.ev[b][0], c->stream));
+    const int b = g.pipe.begin(c, "knp_grid_sample", "knp_grid_fetch");
+    if (b < 0) return b;
     if (g.n_fields) {
         if (g.dim == 3) { if (c->degree == 1) sample_type<3, 1>(c, g, F); else sample_type<3, 2>(c, g, F); }
         else { if (c->degree == 1) sample_type<2, 1>(c, g, F); else sample_type<2, 2>(c, g, F); }
@@ -621,27 +610,14 @@ int knp_grid_sample(knp_ctx* c, int grid) {
         else { if (c->degree == 1) derived_type<2, 1>(c, g, Q); else derived_type<2, 2>(c, g, Q); }
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipEventRecord(g.ev[b][1], c->stream));
-    HIPCHK(c, hipMemcpyAsync(g.pinned[b], g.frame, g.frame_bytes(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(g.ev[b][2], c->stream));
-    ++g.sampled;
-    return 0;
+    return g.pipe.end(c, b);
 }
 
 int knp_grid_fetch(knp_ctx* c, int grid, void* out, size_t bytes) {
     if (!c || !out) return -1;
     Grid* gp = grid_find(c, grid, "knp_grid_fetch");
     if (!gp) return -1;
-    Grid& g = *gp;
-    if (g.fetched >= g.sampled) { c->err = "knp_grid_fetch: no frame waits (knp_grid_sample)"; return -1; }
-    if (bytes != g.frame_bytes()) { c->err = "knp_grid_fetch: the buffer must hold n_fields x points values of the grid's type"; return -1; }
-    const int b = (int)(g.fetched & 1);
-    HIPCHK(c, host_event_sync(c, g.ev[b][2]));
-    HIPCHK(c, hipEventElapsedTime(&g.sample_ms, g.ev[b][0], g.ev[b][1]));
-    HIPCHK(c, hipEventElapsedTime(&g.copy_ms, g.ev[b][1], g.ev[b][2]));
-    memcpy(out, g.pinned[b], bytes);
-    ++g.fetched;
-    return 0;
+    return gp->pipe.fetch(c, "knp_grid_fetch", "knp_grid_sample", "n_fields x points values of the grid's type", out, bytes);
 }
 
 int knp_grid_destroy(knp_ctx* c, int grid) {
@@ -659,7 +635,7 @@ int knp_grid_timing(knp_ctx* c, int grid, float* locate_ms, float* weights_ms, f
     if (!c || !locate_ms || !weights_ms || !sample_ms || !copy_ms) return -1;
     Grid* g = grid_find(c, grid, "knp_grid_timing");
     if (!g) return -1;
-    *locate_ms = g->locate_ms; *weights_ms = g->weights_ms; *sample_ms = g->sample_ms; *copy_ms = g->copy_ms;
+    *locate_ms = g->locate_ms; *weights_ms = g->weights_ms; *sample_ms = g->pipe.sample_ms; *copy_ms = g->pipe.copy_ms;
     return 0;
 }
 

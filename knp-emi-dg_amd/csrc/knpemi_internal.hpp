@@ -127,6 +127,7 @@ struct SourceState;                // source.hip: the context's device-evaluated
 struct OdeState;                   // ode.hip: membrane-model sets and runtime-compiled models
 struct RecState;                   // record.hip: the time-series recorder
 struct GridState;                  // grid.hip: voxel grids and the uploaded tag table
+struct SurfState;                  // surface.hip: membrane-surface samplers
 struct CkptState;                  // state.hip: cell permutation, checkpoint staging, events
 struct RingUState;                 // apply_ring_u.hip: per-block tables of the unstructured ring
 
@@ -152,6 +153,7 @@ struct knp_ctx {
     std::vector<uint32_t> h_fflag;
     std::vector<uint32_t> h_ctag;    // [nc] subdomain tag of every cell, device order: the table the grid sampler's tag filter and tag volume read (grid.hip)
     std::vector<uint8_t> h_mf_mask;  // [nf] 1 on membrane facets: what knp_rec_create checks the caller's facet sets against
+    std::vector<int32_t> h_mf_row;   // [nf] row of the membrane-facet table (MeshDev::mf), -1 off the membrane: what knp_surf_create selects by
     int* halo_ctr = nullptr;       // [KNP_HALO_CTR_INTS] block counters of the persistent halo-staged applies (apply_p1_halo.hpp)
     int halo_flip[2] = {0, 0};
     double* rho = nullptr;         // [nc]
@@ -164,6 +166,7 @@ struct knp_ctx {
     OdeState* ode = nullptr;       // ode.hip (knp_ode_create / knp_ode_register)
     RecState* rec = nullptr;       // record.hip (knp_rec_create)
     GridState* grid = nullptr;     // grid.hip (knp_grid_create)
+    SurfState* surf = nullptr;     // surface.hip (knp_surf_create)
     CkptState* ckpt = nullptr;     // state.hip (knp_state_cell_order / knp_state_save / knp_state_load)
     RingUState* ring_u = nullptr;  // apply_ring_u.hip (ring_u_cells)
     // launch caches of the persistent applies: what the context's device answered, asked once per context
@@ -414,6 +417,7 @@ template <typename T> inline void state_push_host(StateBlk& b, const T* v, int64
 void ode_destroy_all(knp_ctx* c);   // ode.hip: frees the context's membrane models and runtime-compiled kernels
 void rec_destroy(knp_ctx* c);       // record.hip: frees the context's time-series recorder, if any
 void grid_destroy_all(knp_ctx* c);  // grid.hip: frees the context's voxel-grid samplers, if any
+void surf_destroy_all(knp_ctx* c);  // surface.hip: frees the context's membrane-surface samplers, if any
 void source_destroy(knp_ctx* c);    // source.hip: unloads the context's device-evaluated ion sources, frees their cell list and rule
 bool source_registered(knp_ctx* c); // source.hip: some species has a device-evaluated source (knp_source_register)
 int ode_check_failed(knp_ctx* c);   // ode.hip: reads and clears the ODE failure flag (stream idle); sets c->err

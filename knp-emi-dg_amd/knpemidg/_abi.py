@@ -19,6 +19,8 @@ F_PHI, F_C, F_C_PREV, F_C_ELIM, F_PHI_M, F_I_CH, F_E, F_KAPPA, F_DNPHI, F_B_EMI,
 FACET_TMP_SLOTS = 4        # KNP_FACET_TMP_SLOTS (include/knpemi_hip.h)
 # enum knp_grid_derived (include/knpemi_hip.h)
 GD_EFIELD, GD_FLUX, GD_FLUX_DIFFUSIVE, GD_CURRENT = range(4)
+# enum knp_surf_kind (include/knpemi_hip.h)
+SF_PHI_M, SF_E, SF_I_CH, SF_I_CH_TOTAL, SF_TRACE_E, SF_TRACE_I = range(6)
 # knp_debug_table_id (include/knpemi_hip.h)
 DT_CELLS, DT_NBR, DT_FLAG, DT_CFACET, DT_MF, DT_HB_SRC, DT_HB_LOC, DT_META = range(8)
 DT_RU_META, DT_RU_HB_SRC, DT_RU_HB_LOC, DT_RU_VB_SRC, DT_RU_VLOC, DT_RU_HINV4 = range(8, 14)      # the unstructured ring's tables
@@ -151,6 +153,11 @@ SIGNATURES = {
     "knp_grid_fetch": (C.c_int, [_ctxp, C.c_int, C.c_void_p, C.c_size_t]),
     "knp_grid_destroy": (C.c_int, [_ctxp, C.c_int]),
     "knp_grid_timing": (C.c_int, [_ctxp, C.c_int, _f32p, _f32p, _f32p, _f32p]),
+    "knp_surf_create": (C.c_int, [_ctxp, C.c_int64, _i32p, C.c_int, _i32p, _i32p, C.c_int, _i32p, _i64p, _i32p, C.c_int]),
+    "knp_surf_sample": (C.c_int, [_ctxp, C.c_int]),
+    "knp_surf_fetch": (C.c_int, [_ctxp, C.c_int, C.c_void_p, C.c_size_t]),
+    "knp_surf_destroy": (C.c_int, [_ctxp, C.c_int]),
+    "knp_surf_timing": (C.c_int, [_ctxp, C.c_int, _f32p, _f32p]),
     "knp_state_cell_order": (C.c_int, [_ctxp, _i64p]),
     "knp_state_describe": (C.c_int64, [_ctxp, C.c_void_p, C.c_int64, _i64p]),
     "knp_state_save": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t]),
@@ -1137,6 +1144,52 @@ class Device:
         self._chk(self.lib.knp_grid_timing(self.ctx, grid, *[C.byref(x) for x in v]), "knp_grid_timing")
         return tuple(x.value for x in v)
 
+    # -- membrane-surface snapshots (csrc/surface.hip; knpemidg/surface.py holds the host side) ------------------------------
+    def surf_create(self, facets, fields, states=None, f32=False):
+        """A sampler of the membrane facets `facets` (caller's ids, ascending).  fields: (kind, ion) pairs, kind out of SF_PHI_M /
+        SF_E / SF_I_CH / SF_I_CH_TOTAL / SF_TRACE_E / SF_TRACE_I (ion -1: phi, for the traces).  states: (handle, row, col), each
+        [n_states, n]: per state plane and facet the ODE handle (-1: NaN), the row of its state table and the column.  Returns the
+        handle."""
+        f = np.ascontiguousarray(facets, dtype=np.int32)
+        kind = np.ascontiguousarray([k for k, _ in fields], dtype=np.int32)
+        ion = np.ascontiguousarray([i for _, i in fields], dtype=np.int32)
+        if states is None:
+            ns, sh, sr, sc = 0, None, None, None
+        else:
+            sh = np.ascontiguousarray(states[0], dtype=np.int32)
+            sr = np.ascontiguousarray(states[1], dtype=np.int64)
+            sc = np.ascontiguousarray(states[2], dtype=np.int32)
+            if not (sh.ndim == 2 and sh.shape[1] == len(f) and sr.shape == sh.shape and sc.shape == sh.shape):
+                raise KnpError("surf_create: the state tables must be [n_states, n]")
+            ns = sh.shape[0]
+        rc = self.lib.knp_surf_create(self.ctx, len(f), _p(f, _i32p), len(kind), _p(kind, _i32p), _p(ion, _i32p), ns, _p(sh, _i32p),
+                                      _p(sr, _i64p), _p(sc, _i32p), int(bool(f32)))
+        if rc < 0:
+            self._chk(rc, "knp_surf_create")
+        return int(rc)
+
+    def surf_sample(self, surf):
+        """Enqueue one frame of the state as it is now (asynchronous; at most two frames may wait)."""
+        self._chk(self.lib.knp_surf_sample(self.ctx, surf), "knp_surf_sample")
+
+    def surf_fetch(self, surf, n_planes, n, dtype=np.float64, out=None):
+        """The oldest waiting frame, [n_planes, n]; waits for that frame's copy only.  out: a C-contiguous array to fill."""
+        if out is None:
+            out = np.empty((n_planes, n), dtype=dtype)
+        elif out.shape != (n_planes, n) or out.dtype != np.dtype(dtype) or not out.flags.c_contiguous:
+            raise KnpError("surf_fetch: out must be a C-contiguous [n_planes, n] array of the sampler's type")
+        self._chk(self.lib.knp_surf_fetch(self.ctx, surf, out.ctypes.data_as(C.c_void_p), out.nbytes), "knp_surf_fetch")
+        return out
+
+    def surf_destroy(self, surf):
+        self._chk(self.lib.knp_surf_destroy(self.ctx, surf), "knp_surf_destroy")
+
+    def surf_timing(self, surf):
+        """(sample kernel ms, frame copy ms) of the last fetched frame, from HIP events."""
+        a, b = C.c_float(0), C.c_float(0)
+        self._chk(self.lib.knp_surf_timing(self.ctx, surf, C.byref(a), C.byref(b)), "knp_surf_timing")
+        return a.value, b.value
+
     # -- checkpoint of the step-to-step state (csrc/state.hip; knpemidg/checkpoint.py reads and writes the files) ----------
     def state_describe(self):
         """(block table as a structured array of checkpoint.BLOCK_DTYPE, size of a snapshot in bytes)."""
@@ -1184,7 +1237,7 @@ for _name in ("close", "set_params", "set_mms", "upload", "download", "copy_fiel
               "knp_apply", "emi_rhs", "knp_rhs", "emi_solve", "knp_solve", "step_updates", "picard_updates", "max_abs_diff",
               "nernst", "sync", "timer_begin", "timer_end", "bench_apply", "ode_table", "ode_step", "ode_set_stimulus",
               "amg_upload", "amg_interface", "halo_exchange", "knp_load_measure", "apply_timing_read", "comm_init", "set_interior", "rec_sample",
-              "rec_read", "rec_add_states", "rec_map_arm", "rec_map_read", "state_save", "state_load", "grid_sample"):
+              "rec_read", "rec_add_states", "rec_map_arm", "rec_map_read", "state_save", "state_load", "grid_sample", "surf_sample"):
     setattr(Device, _name, _flushing(getattr(Device, _name)))
 
 

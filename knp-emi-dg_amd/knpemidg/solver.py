@@ -203,6 +203,7 @@ class Solver:
         self.max_it_knp = 5000
         self.recorder = None             # time-series recorder (Solver.record), sampled after step III of every time step
         self.grids = None                # voxel-grid samplers (Solver.record_grid); None = off: the time loops test this once per step
+        self.surfaces_rec = None         # membrane-surface samplers (Solver.record_membrane); None = off, tested once per step as well
         # a partition of a global mesh: partition.distribute_solver sets these before setup_domain
         self.nc_owned = self.local_mesh = self.global_mesh_tuple = None
         # what the setup_* calls fill in, in the reference's order
@@ -395,6 +396,7 @@ class Solver:
             self.mem_models.append({'ode': ode_model, 'I_ch_k': I_ch_k})
         if self.recorder is not None:
             self.recorder.attach_states([m['ode'] for m in self.mem_models])     # state channels of a record() call made earlier
+        self._surfaces_attach(with_states=True)                                   # record_membrane calls made earlier
         return
 
     # ------------------------------------------------------------------ device context
@@ -439,6 +441,7 @@ class Solver:
             self.recorder.attach(dev, self.membrane_tags)
         for g in self.grids or ():
             g.attach(dev)
+        self._surfaces_attach(with_states=False)     # samplers with state planes wait for the membrane models (setup_membrane_model)
 
     # ------------------------------------------------------------------ time series (no reference counterpart: knpemidg/recorder.py)
     def record(self, points=None, membrane_sets=None, regions=True, capacity=256, point_tags=None, membrane_states=None,
@@ -541,6 +544,83 @@ class Solver:
     def _grids_finish(self):
         for g in self.grids:
             g.finish()
+
+    # ------------------------------------------------------------------ membrane-surface snapshots (no reference counterpart: knpemidg/surface.py)
+    def record_membrane(self, fields=("phi_M",), states=(), tags=None, facets=None, every=1, dtype=np.float64, name="membrane"):
+        """Sample facet quantities on the membrane on the device (csrc/surface.hip) and write them as cell data of the membrane's
+        surface mesh -- the pictures of the action potential travelling along an axon the reference's figure scripts rebuild from
+        results.h5 with FEniCS (examples/rat-neuron/make_figures_rat_neuron.py, examples/idealized-geometries/make_figures_3D.py).
+        Callable once setup_domain has run; the device tables are created as soon as the device context and, with `states`, the
+        membrane models exist.  Returns the `knpemidg.surface.MembraneSampler`; up to 4 per solver.
+          fields   out of "phi_M"; "E_<ion>" and "I_ch_<ion>" for every ion, the eliminated one included; "I_ch_total" (the sum over
+                   the ions, added in ion order); "phi_e", "phi_i", "c_<ion>_e", "c_<ion>_i": the facet means of the one-sided traces,
+                   `_e` from the side utils.plus gives, `_i` from the side utils.minus gives -- the values of
+                   pcws_constant_project(plus(u, n_g)) / pcws_constant_project(minus(u, n_g))
+          states   gating-variable names as the membrane models declare them (as record(membrane_states=...)): one plane per name,
+                   NaN on the facets whose model has no such state
+          tags     surface tags to select (default: every membrane tag); facets: explicit facet ids instead.  The selection is kept
+                   in ascending facet id
+          every    the time loops write frame 0 for the state they start from, then one frame every `every` steps, to
+                   `<filename><name>.h5` (+ `<name>.xdmf` for ParaView); a resumed run writes `<name>_from<k>.h5`
+          dtype    np.float64 or np.float32 frames
+        Pairing: a frame is taken after step III of a time step, as the recorder's row is: phi_M, E and the traces belong to the new
+        time level, I_ch and the states are those after the ODE step of that splitting step.  `sampler.sample()` returns
+        {plane: array [n]} of the state as it is now; `sampler.facets`, `.points`, `.connectivity` describe the surface.  Without a
+        call nothing is allocated or launched; the sampler holds no step-to-step state (checkpoints do not change).  Partitioned
+        solvers are not supported."""
+        from knpemidg.surface import MembraneSampler, SurfaceSpec, resolve_fields
+        if self.local_mesh is not None or self.nc_owned is not None or (self.dev is not None and self.dev.nranks > 1):
+            raise _abi.KnpError("record_membrane: not supported with several ranks (sample the membrane in a one-GPU run)")
+        if self.mesh is None:
+            raise _abi.KnpError("Solver.record_membrane: call setup_domain first")
+        if states and not self.use_device_ode:
+            raise _abi.KnpError("Solver.record_membrane: states read the ODE state tables on the device; with KNP_HOST_ODE=1 they "
+                                "live on the host")
+        ids = resolve_fields(fields, [ion['name'] for ion in self.ion_list])
+        names = [fields] if isinstance(fields, str) else list(fields)
+        states = [states] if isinstance(states, str) else list(states)
+        if tags is not None and facets is not None:
+            raise ValueError("record_membrane: tags and facets are mutually exclusive")
+        make_spec = lambda mtags: SurfaceSpec(self.mesh, self.surfaces, self.subdomains, mtags, degree=self.degree_knp, tags=tags,
+                                              facets=facets)
+        m = MembraneSampler(make_spec, names, ids, states=states, every=every, dtype=dtype, name=name)
+        if any(o.name == m.name for o in self.surfaces_rec or ()):
+            raise _abi.KnpError("record_membrane: a sampler named %r exists already" % m.name)
+        if len(self.surfaces_rec or ()) >= 4:
+            raise _abi.KnpError("record_membrane: at most 4 surface samplers per solver")
+        if self.membrane_tags is not None:
+            m.resolve(self.membrane_tags)        # a bad selection is refused here, before any device call
+            if m.states:
+                m.spec.state_tables([x['ode'] for x in self.mem_models], m.states)
+        self.surfaces_rec = (self.surfaces_rec or []) + [m]
+        try:
+            self._surfaces_attach(with_states=bool(self.mem_models))
+        except Exception:
+            self.surfaces_rec = self.surfaces_rec[:-1] or None
+            raise
+        return m
+
+    def _surfaces_attach(self, with_states):
+        if self.dev is None:
+            return
+        for m in self.surfaces_rec or ():
+            if not m.attached and (with_states or not m.states):
+                m.attach(self.dev, self.membrane_tags, models=[x['ode'] for x in self.mem_models])
+
+    def _surfaces_begin(self, k0, t):
+        if self.filename is not None:
+            for m in self.surfaces_rec:
+                if not m.attached:
+                    raise _abi.KnpError("record_membrane: sampler %r has state planes but the membrane models were never set up" % m.name)
+                m.begin(self.filename, k0, float(t))
+
+    def _surfaces_step(self, steps_done, t):
+        for m in self.surfaces_rec:
+            m.after_step(steps_done, float(t))
+
+    def _surfaces_finish(self):
+        for m in self.surfaces_rec:
+            m.finish()
 
     def _save_timeseries(self):
         if self.recorder is not None and self.filename is not None:
@@ -910,18 +990,24 @@ class Solver:
             self.recorder.arm(float(t))
         if self.grids is not None:
             self._grids_begin(k0, t)
+        if self.surfaces_rec is not None:
+            self._surfaces_begin(k0, t)
         for k in range(k0, int(round(Tstop / float(self.dt)))):
             self.solve_for_time_step(k, t)
             if (k % self.sf) == 0 and self.save_fields:
                 self.save_h5()
             if self.grids is not None:
                 self._grids_step(k + 1, t)
+            if self.surfaces_rec is not None:
+                self._surfaces_step(k + 1, t)
             if ckpt is not None and (k + 1) % ckpt[0] == 0:
                 self.save_checkpoint(ckpt[1])
         if self.save_fields:
             self.close_h5()
         if self.grids is not None:
             self._grids_finish()
+        if self.surfaces_rec is not None:
+            self._surfaces_finish()
         self._save_timeseries()
         if self.save_solver_stats:
             self.close_solver_stats()
@@ -949,6 +1035,8 @@ class Solver:
         self._check_output_args(filename)
         if self.grids is not None:
             self._grids_begin(k0, t)
+        if self.surfaces_rec is not None:
+            self._surfaces_begin(k0, t)
         for k in range(k0, int(round(Tstop / float(self.dt)))):
             self.step_membrane_models(k)
             if k == 0 and self.recorder is not None:
@@ -960,12 +1048,16 @@ class Solver:
                 self.save_h5()
             if self.grids is not None:
                 self._grids_step(k + 1, t)
+            if self.surfaces_rec is not None:
+                self._surfaces_step(k + 1, t)
             if ckpt is not None and (k + 1) % ckpt[0] == 0:
                 self.save_checkpoint(ckpt[1])
         if self.save_fields:
             self.close_h5()
         if self.grids is not None:
             self._grids_finish()
+        if self.surfaces_rec is not None:
+            self._surfaces_finish()
         self._save_timeseries()
         if self.save_solver_stats:
             self.close_solver_stats()
