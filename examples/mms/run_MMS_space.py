@@ -17,7 +17,9 @@ from knpemidg.quadrature import simplex_rule                     # noqa: E402
 from mms_space import setup_mms                                  # noqa: E402
 
 
-def run(resolution, degree=1, dt=1.0e-10, nsteps=2, verbose=False):
+def make_solver(resolution, degree=1, dt=1.0e-10, verbose=False):
+    """The Solver of the space MMS after setup_domain, setup_parameters and setup_FEM_spaces (no device yet): `run` steps it;
+    the tests take its data terms and its right-hand sides one by one (tests/test_mms_cases_host.py, tests/test_gpu_mms_rhs.py)."""
     names = ('D_a1', 'D_a2', 'D_b1', 'D_b2', 'D_c1', 'D_c2', 'C_a1', 'C_a2', 'C_b1', 'C_b2', 'C_c1', 'C_c2', 'C_phi',
              'z_a', 'z_b', 'z_c', 'dt', 'F', 'C_M', 'phi_M_init', 'R', 'temperature', 'phi_M_init_type', 'rho_sub')
     C_M = 1.0
@@ -41,9 +43,19 @@ def run(resolution, degree=1, dt=1.0e-10, nsteps=2, verbose=False):
     S.setup_domain(mesh, subdomains, surfaces)
     S.setup_parameters()
     S.setup_FEM_spaces()
-    sp = namedtuple('solver_params', ('direct_emi', 'direct_knp', 'resolution', 'rtol_emi', 'rtol_knp', 'atol_emi',
-                                      'atol_knp', 'threshold_emi', 'threshold_knp'))(True, True, resolution, 1e-6, 1e-7,
-                                                                                     1e-40, 1e-40, 0.9, 7.5)
+    return S
+
+
+def direct_solver_params(resolution):
+    """direct_emi = direct_knp = True, as the reference's run_MMS_space.py"""
+    fields = ('direct_emi', 'direct_knp', 'resolution', 'rtol_emi', 'rtol_knp', 'atol_emi', 'atol_knp', 'threshold_emi', 'threshold_knp')
+    return namedtuple('solver_params', fields)(True, True, resolution, 1e-6, 1e-7, 1e-40, 1e-40, 0.9, 7.5)
+
+
+def run(resolution, degree=1, dt=1.0e-10, nsteps=2, verbose=False):
+    S = make_solver(resolution, degree, dt, verbose)
+    mesh, subdomains, sol = S.mesh, S.subdomains, S.mms.solution
+    sp = direct_solver_params(resolution)
     t = Constant(0.0)
     uh, uh_cc = S.solve_system_passive(dt * nsteps, t, sp, None)
     fields = {'a': uh[0].array(), 'b': uh[1].array(), 'c': uh_cc.array(), 'phi': uh[2].array()}

@@ -79,7 +79,9 @@ int knp_set_geometry_classes(knp_ctx* ctx, int ncls, const uint16_t* cls, const 
 /* Manufactured-solution mode (Solver(mms=...), solver.py:349-374, 632-657): splitting = 2 in knp_set_params selects
  * it.  C[n_sys][nc] are the DG0 coupling coefficients ion['C']; extra_emi[nc*nd] / extra_knp[n_sys][nc*nd] are the
  * solution-independent data terms (volume sources, Robin and flux-continuity data, Neumann data) integrated on the
- * host and added to L_emi / L_knp; the solution-dependent term -jump(phi) jump(C v) is evaluated on the device. */
+ * host and added to L_emi / L_knp; the solution-dependent term -jump(phi) jump(C v) is evaluated on the device.
+ * Every call replaces all three tables (a null pointer drops that table).  While splitting == 2 a null C is refused: the
+ * call returns -1 with a message in knp_last_error and leaves the tables of the previous call in place. */
 int knp_set_mms(knp_ctx* ctx, const double* C, const double* extra_emi, const double* extra_knp);
 
 /* Ion sources that are not constants (ion['f_source'] is any UFL coefficient in the reference, solver.py:599; e.g. the box- and

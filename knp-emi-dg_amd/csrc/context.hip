@@ -336,6 +336,8 @@ int knp_set_source(knp_ctx* c, const double* src) {
 
 int knp_set_mms(knp_ctx* c, const double* C, const double* extra_emi, const double* extra_knp) {
     if (!c) return -1;
+    // the MMS branch of the KNP right-hand side reads C for every membrane facet: in that mode the table cannot be taken away
+    if (!C && c->p.splitting == 2) { c->err = "knp_set_mms: C must not be null in MMS mode (splitting == 2); the tables are unchanged"; return -1; }
     const int64_t ndof = c->m.nc * c->nd, ns = c->p.n_sys;
     hipFree(c->mms_C); hipFree(c->extra_emi); hipFree(c->extra_knp);
     c->mms_C = c->extra_emi = c->extra_knp = nullptr;

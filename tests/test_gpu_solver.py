@@ -352,7 +352,8 @@ def test_distributed_setup_path_world1(hip_lib):
 
 def test_mms_space_convergence_on_device(hip_lib):
     """The reference's verification test (tests/run_MMS_space.py) on the HIP path: manufactured solution, 2^r x 2^r
-    meshes, P1, dt = 1e-10, two steps -> L2 order 2 for all concentrations and the (mean-corrected) potential."""
+    meshes, P1, dt = 1e-10, two steps -> L2 order 2 for all concentrations and the (mean-corrected) potential.  At this dt the
+    solution-dependent term of L_knp is invisible in the error norms: tests/test_gpu_mms_rhs.py checks it vector by vector."""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "mms"))
     import run_MMS_space as R
     errs = [R.run(r) for r in (3, 4, 5)]
@@ -371,7 +372,8 @@ def test_mms_space_convergence_on_device(hip_lib):
 
 def test_mms_space_convergence_p2_on_device(hip_lib):
     """The same manufactured solution with `Solver(degree_emi=2, degree_knp=2)` (the reference reaches P2 exactly this
-    way, tests/run_MMS_space.py:194-195): L2 order 3 on the assembled-block P2 path, and the same errors as the oracle."""
+    way, tests/run_MMS_space.py:194-195): L2 order 3 on the assembled-block P2 path, and the same errors as the oracle.  The
+    solution-dependent term of L_knp, which these norms cannot see at dt = 1e-10, is checked in tests/test_gpu_mms_rhs.py."""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "mms"))
     import run_MMS_space as R
     errs = [R.run(r, degree=2) for r in (2, 3, 4)]
@@ -413,7 +415,8 @@ def test_picard_variant(hip_lib):
 
 def test_mms_time_convergence_on_device(hip_lib):
     """The reference's second verification test (tests/run_MMS_time.py) on the HIP path: halving dt halves the
-    concentration errors (first order: backward Euler + splitting with data at the old time level)."""
+    concentration errors (first order: backward Euler + splitting with data at the old time level).  The rates feel the
+    solution-dependent term of L_knp only loosely; tests/test_gpu_mms_rhs.py compares it with the oracle at 1e-11."""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "mms"))
     import run_MMS_time as R
     errs = []
