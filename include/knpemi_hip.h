@@ -475,6 +475,32 @@ int knp_surf_fetch(knp_ctx* ctx, int surf, void* out, size_t bytes);
 int knp_surf_destroy(knp_ctx* ctx, int surf);
 int knp_surf_timing(knp_ctx* ctx, int surf, float* sample_ms, float* copy_ms);
 
+/* ---- volume-field snapshots on the mesh (csrc/fieldmesh.hip) ---------------------------------
+ * Per output node the arithmetic mean of a list of nodal values; a frame is [n_fields][n_nodes].  The lists arrive as CSR: ptr
+ * [n_nodes + 1] and entries [ptr[n_nodes]][2] = (cell in the context's own -- device -- cell order, local dof in the order of
+ * knp_set_tabulation); the library forms the addresses with its own cell stride.  The value of a node is the first listed value, the
+ * further ones added one by one in list order, then one division by the list's length, all in fp64 (a list of length one gives the
+ * nodal value's bits).  kind[q] / ion[q] of plane q: KNP_FM_PHI (ion ignored) or KNP_FM_C with ion 0 .. n_ions - 1 (the last is the
+ * eliminated one).
+ *  knp_fieldmesh_create : writes the handle (0 .. 3) and returns 0, or a negative code.  Everything is checked on the host before
+ *                         anything is allocated or uploaded and a failure leaves the context as it was: -7 with several ranks; -1
+ *                         for a ptr that does not start at 0, is not strictly increasing (an empty list), a cell outside the owned
+ *                         cells, a dof outside 0 .. nd - 1, an unknown kind, an ion out of range, no plane or more than
+ *                         KNP_MAX_IONS + 1, a fifth sampler.  f32 != 0: frames in fp32 (the fp64 value rounded once).
+ *  knp_fieldmesh_sample : one frame of the state as it is now: kernel, asynchronous copy into one of two pinned host buffers and an
+ *                         event; -5 when both buffers wait to be fetched
+ *  knp_fieldmesh_fetch  : waits for the event of the oldest waiting frame only and copies it to out[bytes], bytes = n_fields x
+ *                         n_nodes x 8 (4)
+ *  knp_fieldmesh_timing : device milliseconds of the kernel and the copy of the last fetched frame
+ * A sampler holds no step-to-step state: knp_state_describe is the same with and without one. */
+typedef enum { KNP_FM_PHI = 0, KNP_FM_C = 1 } knp_fieldmesh_kind;
+int knp_fieldmesh_create(knp_ctx* ctx, int64_t n_nodes, const int64_t* ptr, const int32_t* entries, int n_fields, const int32_t* kind,
+                         const int32_t* ion, int f32, int* handle);
+int knp_fieldmesh_sample(knp_ctx* ctx, int fieldmesh);
+int knp_fieldmesh_fetch(knp_ctx* ctx, int fieldmesh, void* out, size_t bytes);
+int knp_fieldmesh_destroy(knp_ctx* ctx, int fieldmesh);
+int knp_fieldmesh_timing(knp_ctx* ctx, int fieldmesh, float* sample_ms, float* copy_ms);
+
 /* ---- checkpoint of the step-to-step state (csrc/state.hip; DESIGN.md section 4.3 lists every member saved or rebuilt).
  * A snapshot is one host buffer: a 32-byte prologue (magic "KNPSTATE", version, block count, payload bytes), the block table
  * (one knp_state_block per block) and the payloads at the table's offsets.  A block is [ncomp][count][width] elements:

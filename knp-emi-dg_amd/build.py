@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "knpemidg", "libknpemi_hip.so")
 HOST_SOURCES = ["host_sparse.cpp"]
-SOURCES = ["abi.hip", "context.hip", "solve.hip", "apply_p1.hip", "rhs_p1.hip", "krylov.hip", "comm.hip", "amg_vcycle.hip", "amg_restrict.hip", "amg_upload.hip", "ode.hip", "tab_rhs.hip", "tab_assembled.hip", "apply_p2.hip", "p2_probe.hip", "apply_ring.hip", "apply_ring_u.hip", "record.hip", "state.hip", "grid.hip", "surface.hip", "source.hip"]
+SOURCES = ["abi.hip", "context.hip", "solve.hip", "apply_p1.hip", "rhs_p1.hip", "krylov.hip", "comm.hip", "amg_vcycle.hip", "amg_restrict.hip", "amg_upload.hip", "ode.hip", "tab_rhs.hip", "tab_assembled.hip", "apply_p2.hip", "p2_probe.hip", "apply_ring.hip", "apply_ring_u.hip", "record.hip", "state.hip", "grid.hip", "surface.hip", "fieldmesh.hip", "source.hip"]
 
 
 def _stale():

@@ -186,6 +186,7 @@ void knp_ctx_destroy(knp_ctx* c) {
     for (auto ev : c->aux_events) hipEventDestroy(ev);
     if (c->fork_event) hipEventDestroy(c->fork_event);
     surf_destroy_all(c);            // before the ODE tables its state addresses point into
+    fieldmesh_destroy_all(c);
     ode_destroy_all(c);
     source_destroy(c);
     rec_destroy(c);

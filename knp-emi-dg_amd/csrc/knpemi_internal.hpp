@@ -128,6 +128,7 @@ struct OdeState;                   // ode.hip: membrane-model sets and runtime-c
 struct RecState;                   // record.hip: the time-series recorder
 struct GridState;                  // grid.hip: voxel grids and the uploaded tag table
 struct SurfState;                  // surface.hip: membrane-surface samplers
+struct FieldMeshState;             // fieldmesh.hip: volume-field samplers on the mesh
 struct CkptState;                  // state.hip: cell permutation, checkpoint staging, events
 struct RingUState;                 // apply_ring_u.hip: per-block tables of the unstructured ring
 
@@ -167,6 +168,7 @@ struct knp_ctx {
     RecState* rec = nullptr;       // record.hip (knp_rec_create)
     GridState* grid = nullptr;     // grid.hip (knp_grid_create)
     SurfState* surf = nullptr;     // surface.hip (knp_surf_create)
+    FieldMeshState* fieldmesh = nullptr;   // fieldmesh.hip (knp_fieldmesh_create)
     CkptState* ckpt = nullptr;     // state.hip (knp_state_cell_order / knp_state_save / knp_state_load)
     RingUState* ring_u = nullptr;  // apply_ring_u.hip (ring_u_cells)
     // launch caches of the persistent applies: what the context's device answered, asked once per context
@@ -418,6 +420,7 @@ void ode_destroy_all(knp_ctx* c);   // ode.hip: frees the context's membrane mod
 void rec_destroy(knp_ctx* c);       // record.hip: frees the context's time-series recorder, if any
 void grid_destroy_all(knp_ctx* c);  // grid.hip: frees the context's voxel-grid samplers, if any
 void surf_destroy_all(knp_ctx* c);  // surface.hip: frees the context's membrane-surface samplers, if any
+void fieldmesh_destroy_all(knp_ctx* c);   // fieldmesh.hip: frees the context's volume-field samplers on the mesh, if any
 void source_destroy(knp_ctx* c);    // source.hip: unloads the context's device-evaluated ion sources, frees their cell list and rule
 bool source_registered(knp_ctx* c); // source.hip: some species has a device-evaluated source (knp_source_register)
 int ode_check_failed(knp_ctx* c);   // ode.hip: reads and clears the ODE failure flag (stream idle); sets c->err

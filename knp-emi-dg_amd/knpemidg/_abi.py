@@ -21,6 +21,8 @@ FACET_TMP_SLOTS = 4        # KNP_FACET_TMP_SLOTS (include/knpemi_hip.h)
 GD_EFIELD, GD_FLUX, GD_FLUX_DIFFUSIVE, GD_CURRENT = range(4)
 # enum knp_surf_kind (include/knpemi_hip.h)
 SF_PHI_M, SF_E, SF_I_CH, SF_I_CH_TOTAL, SF_TRACE_E, SF_TRACE_I = range(6)
+# enum knp_fieldmesh_kind (include/knpemi_hip.h)
+FM_PHI, FM_C = range(2)
 # knp_debug_table_id (include/knpemi_hip.h)
 DT_CELLS, DT_NBR, DT_FLAG, DT_CFACET, DT_MF, DT_HB_SRC, DT_HB_LOC, DT_META = range(8)
 DT_RU_META, DT_RU_HB_SRC, DT_RU_HB_LOC, DT_RU_VB_SRC, DT_RU_VLOC, DT_RU_HINV4 = range(8, 14)      # the unstructured ring's tables
@@ -158,6 +160,11 @@ SIGNATURES = {
     "knp_surf_fetch": (C.c_int, [_ctxp, C.c_int, C.c_void_p, C.c_size_t]),
     "knp_surf_destroy": (C.c_int, [_ctxp, C.c_int]),
     "knp_surf_timing": (C.c_int, [_ctxp, C.c_int, _f32p, _f32p]),
+    "knp_fieldmesh_create": (C.c_int, [_ctxp, C.c_int64, _i64p, _i32p, C.c_int, _i32p, _i32p, C.c_int, C.POINTER(C.c_int)]),
+    "knp_fieldmesh_sample": (C.c_int, [_ctxp, C.c_int]),
+    "knp_fieldmesh_fetch": (C.c_int, [_ctxp, C.c_int, C.c_void_p, C.c_size_t]),
+    "knp_fieldmesh_destroy": (C.c_int, [_ctxp, C.c_int]),
+    "knp_fieldmesh_timing": (C.c_int, [_ctxp, C.c_int, _f32p, _f32p]),
     "knp_state_cell_order": (C.c_int, [_ctxp, _i64p]),
     "knp_state_describe": (C.c_int64, [_ctxp, C.c_void_p, C.c_int64, _i64p]),
     "knp_state_save": (C.c_int, [_ctxp, C.c_void_p, C.c_size_t]),
@@ -1190,6 +1197,50 @@ class Device:
         self._chk(self.lib.knp_surf_timing(self.ctx, surf, C.byref(a), C.byref(b)), "knp_surf_timing")
         return a.value, b.value
 
+    # -- volume-field snapshots on the mesh (csrc/fieldmesh.hip; knpemidg/fieldmesh.py holds the host side) ------------------
+    def fieldmesh_create(self, ptr, cell, dof, fields, f32=False):
+        """A sampler of len(ptr) - 1 output nodes.  Node i is the mean of the nodal values (cell[j], dof[j]), ptr[i] <= j < ptr[i + 1]:
+        caller's cell ids -- translated to the device's cell order here -- and local dofs.  fields: (kind, ion) pairs, kind FM_PHI or
+        FM_C (ion 0 .. n_ions - 1, the eliminated one last).  Returns the handle."""
+        ptr = np.ascontiguousarray(ptr, dtype=np.int64)
+        cell = np.asarray(cell, dtype=np.int64)
+        dof = np.asarray(dof, dtype=np.int64)
+        if ptr.ndim != 1 or len(ptr) < 1 or cell.ndim != 1 or cell.shape != dof.shape:
+            raise KnpError("fieldmesh_create: ptr [n_nodes + 1], cell [nnz] and dof [nnz]")
+        # a cell outside the mesh cannot be translated: it goes through as it is and the library refuses it
+        inside = (cell >= 0) & (cell < self.nc)
+        entries = np.empty((len(cell), 2), dtype=np.int32)
+        entries[:, 0] = np.where(inside, self.cell_rank[np.where(inside, cell, 0)], np.clip(cell, -1, np.iinfo(np.int32).max))
+        entries[:, 1] = np.clip(dof, -1, np.iinfo(np.int32).max)
+        kind = np.ascontiguousarray([k for k, _ in fields], dtype=np.int32)
+        ion = np.ascontiguousarray([i for _, i in fields], dtype=np.int32)
+        handle = C.c_int(-1)
+        self._chk(self.lib.knp_fieldmesh_create(self.ctx, len(ptr) - 1, _p(ptr, _i64p), _p(entries, _i32p), len(kind), _p(kind, _i32p),
+                                                _p(ion, _i32p), int(bool(f32)), C.byref(handle)), "knp_fieldmesh_create")
+        return int(handle.value)
+
+    def fieldmesh_sample(self, fm):
+        """Enqueue one frame of the state as it is now (asynchronous; at most two frames may wait)."""
+        self._chk(self.lib.knp_fieldmesh_sample(self.ctx, fm), "knp_fieldmesh_sample")
+
+    def fieldmesh_fetch(self, fm, n_fields, n_nodes, dtype=np.float64, out=None):
+        """The oldest waiting frame, [n_fields, n_nodes]; waits for that frame's copy only.  out: a C-contiguous array to fill."""
+        if out is None:
+            out = np.empty((n_fields, n_nodes), dtype=dtype)
+        elif out.shape != (n_fields, n_nodes) or out.dtype != np.dtype(dtype) or not out.flags.c_contiguous:
+            raise KnpError("fieldmesh_fetch: out must be a C-contiguous [n_fields, n_nodes] array of the sampler's type")
+        self._chk(self.lib.knp_fieldmesh_fetch(self.ctx, fm, out.ctypes.data_as(C.c_void_p), out.nbytes), "knp_fieldmesh_fetch")
+        return out
+
+    def fieldmesh_destroy(self, fm):
+        self._chk(self.lib.knp_fieldmesh_destroy(self.ctx, fm), "knp_fieldmesh_destroy")
+
+    def fieldmesh_timing(self, fm):
+        """(sample kernel ms, frame copy ms) of the last fetched frame, from HIP events."""
+        a, b = C.c_float(0), C.c_float(0)
+        self._chk(self.lib.knp_fieldmesh_timing(self.ctx, fm, C.byref(a), C.byref(b)), "knp_fieldmesh_timing")
+        return a.value, b.value
+
     # -- checkpoint of the step-to-step state (csrc/state.hip; knpemidg/checkpoint.py reads and writes the files) ----------
     def state_describe(self):
         """(block table as a structured array of checkpoint.BLOCK_DTYPE, size of a snapshot in bytes)."""
@@ -1237,7 +1288,8 @@ for _name in ("close", "set_params", "set_mms", "upload", "download", "copy_fiel
               "knp_apply", "emi_rhs", "knp_rhs", "emi_solve", "knp_solve", "step_updates", "picard_updates", "max_abs_diff",
               "nernst", "sync", "timer_begin", "timer_end", "bench_apply", "ode_table", "ode_step", "ode_set_stimulus",
               "amg_upload", "amg_interface", "halo_exchange", "knp_load_measure", "apply_timing_read", "comm_init", "set_interior", "rec_sample",
-              "rec_read", "rec_add_states", "rec_map_arm", "rec_map_read", "state_save", "state_load", "grid_sample", "surf_sample"):
+              "rec_read", "rec_add_states", "rec_map_arm", "rec_map_read", "state_save", "state_load", "grid_sample", "surf_sample",
+              "fieldmesh_sample"):
     setattr(Device, _name, _flushing(getattr(Device, _name)))
 
 

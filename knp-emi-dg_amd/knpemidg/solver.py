@@ -204,6 +204,7 @@ class Solver:
         self.recorder = None             # time-series recorder (Solver.record), sampled after step III of every time step
         self.grids = None                # voxel-grid samplers (Solver.record_grid); None = off: the time loops test this once per step
         self.surfaces_rec = None         # membrane-surface samplers (Solver.record_membrane); None = off, tested once per step as well
+        self.fieldmeshes = None          # volume-field samplers on the mesh (Solver.record_fields); None = off, tested once per step as well
         # a partition of a global mesh: partition.distribute_solver sets these before setup_domain
         self.nc_owned = self.local_mesh = self.global_mesh_tuple = None
         # what the setup_* calls fill in, in the reference's order
@@ -442,6 +443,8 @@ class Solver:
         for g in self.grids or ():
             g.attach(dev)
         self._surfaces_attach(with_states=False)     # samplers with state planes wait for the membrane models (setup_membrane_model)
+        for m in self.fieldmeshes or ():
+            m.attach(dev, self.membrane_tags)
 
     # ------------------------------------------------------------------ time series (no reference counterpart: knpemidg/recorder.py)
     def record(self, points=None, membrane_sets=None, regions=True, capacity=256, point_tags=None, membrane_states=None,
@@ -621,6 +624,68 @@ class Solver:
     def _surfaces_finish(self):
         for m in self.surfaces_rec:
             m.finish()
+
+    # ------------------------------------------------------------------ volume fields on the mesh (no reference counterpart: knpemidg/fieldmesh.py)
+    def record_fields(self, fields=("phi",), tags=None, continuous=True, every=1, dtype=np.float32, name="fields"):
+        """Sample phi and concentrations on the mesh's own cells on the device (csrc/fieldmesh.hip) and write them as node data of the
+        mesh -- what save_fields holds as full fp64 DG vectors in DOLFIN's layout, in a form ParaView opens and about 24 times smaller
+        on a structured 3D mesh.  Callable once setup_domain has run; the device tables are created as soon as the device context
+        exists.  Returns the `knpemidg.fieldmesh.FieldSampler`; up to 4 per solver.
+          fields      out of "phi" and "c_<ion>" for every ion, the eliminated one included
+          tags        the cell tags whose cells are written (default: every cell), e.g. the ECS alone
+          continuous  True: one node per (mesh entity, cell tag) among the selected cells -- a vertex for P1, a vertex or an edge for
+                      P2 -- holding the arithmetic mean of the nodal values the selected cells of that tag have there.  Cells of
+                      different tags never share a node: the membrane stays a jump.  ValueError when a membrane facet separates two
+                      selected cells of the same tag.  False: one node per (selected cell, local dof) with the exact DG values
+          every       the time loops write frame 0 for the state they start from, then one frame every `every` steps, to
+                      `<filename><name>.h5` (+ `<name>.xdmf` for ParaView); a resumed run writes `<name>_from<k>.h5`; the file is
+                      closed also when the loop raises
+          dtype       np.float32 (the default: this output is for pictures) or np.float64 frames
+        `sampler.sample()` returns {field: array [n_nodes]} of the state as it is now; `sampler.points`, `.connectivity`,
+        `.node_entity`, `.node_tag` and `.cells` describe the output mesh once the device context exists (the nodes are numbered along
+        the device's cell order).  Without a call nothing is allocated or launched; the sampler holds no step-to-step state
+        (checkpoints do not change).  Partitioned solvers are not supported."""
+        from knpemidg.fieldmesh import MAX_SAMPLERS, FieldMeshSpec, FieldSampler, resolve_fields
+        if self.local_mesh is not None or self.nc_owned is not None or (self.dev is not None and self.dev.nranks > 1):
+            raise _abi.KnpError("record_fields: not supported with several ranks (sample the fields in a one-GPU run)")
+        if self.mesh is None:
+            raise _abi.KnpError("Solver.record_fields: call setup_domain first")
+        ids = resolve_fields(fields, [ion['name'] for ion in self.ion_list])
+        names = [fields] if isinstance(fields, str) else list(fields)
+        make_spec = lambda mtags, cell_rank: FieldMeshSpec(self.mesh, self.subdomains, self.surfaces, mtags, self.degree_knp, tags=tags,
+                                                           continuous=continuous, cell_rank=cell_rank)
+        m = FieldSampler(make_spec, names, ids, every=every, dtype=dtype, name=name)
+        if any(o.name == m.name for o in self.fieldmeshes or ()):
+            raise _abi.KnpError("record_fields: a sampler named %r exists already" % m.name)
+        if len(self.fieldmeshes or ()) >= MAX_SAMPLERS:
+            raise _abi.KnpError("record_fields: at most %d field samplers per solver" % MAX_SAMPLERS)
+        if self.dev is not None:
+            m.attach(self.dev, self.membrane_tags)
+        else:
+            make_spec(self.membrane_tags or (), None)      # a bad selection is refused here, not when the device context appears
+        self.fieldmeshes = (self.fieldmeshes or []) + [m]
+        return m
+
+    def _fieldmeshes_begin(self, k0, t):
+        if self.filename is not None:
+            for m in self.fieldmeshes:
+                m.begin(self.filename, k0, float(t))
+
+    def _fieldmeshes_step(self, steps_done, t):
+        for m in self.fieldmeshes:
+            m.after_step(steps_done, float(t))
+
+    def _fieldmeshes_finish(self):
+        """Every sampler closes its file; the first failure is raised unless the loop is already leaving with an exception."""
+        leaving = sys.exc_info()[0] is not None
+        failed = None
+        for m in self.fieldmeshes:
+            try:
+                m.finish()
+            except Exception as e:
+                failed = failed or e
+        if failed is not None and not leaving:
+            raise failed
 
     def _save_timeseries(self):
         if self.recorder is not None and self.filename is not None:
@@ -992,16 +1057,24 @@ class Solver:
             self._grids_begin(k0, t)
         if self.surfaces_rec is not None:
             self._surfaces_begin(k0, t)
-        for k in range(k0, int(round(Tstop / float(self.dt)))):
-            self.solve_for_time_step(k, t)
-            if (k % self.sf) == 0 and self.save_fields:
-                self.save_h5()
-            if self.grids is not None:
-                self._grids_step(k + 1, t)
-            if self.surfaces_rec is not None:
-                self._surfaces_step(k + 1, t)
-            if ckpt is not None and (k + 1) % ckpt[0] == 0:
-                self.save_checkpoint(ckpt[1])
+        try:
+            if self.fieldmeshes is not None:
+                self._fieldmeshes_begin(k0, t)
+            for k in range(k0, int(round(Tstop / float(self.dt)))):
+                self.solve_for_time_step(k, t)
+                if (k % self.sf) == 0 and self.save_fields:
+                    self.save_h5()
+                if self.grids is not None:
+                    self._grids_step(k + 1, t)
+                if self.surfaces_rec is not None:
+                    self._surfaces_step(k + 1, t)
+                if self.fieldmeshes is not None:
+                    self._fieldmeshes_step(k + 1, t)
+                if ckpt is not None and (k + 1) % ckpt[0] == 0:
+                    self.save_checkpoint(ckpt[1])
+        finally:
+            if self.fieldmeshes is not None:
+                self._fieldmeshes_finish()           # also when the loop raises: the frames taken so far are a file
         if self.save_fields:
             self.close_h5()
         if self.grids is not None:
@@ -1037,21 +1110,29 @@ class Solver:
             self._grids_begin(k0, t)
         if self.surfaces_rec is not None:
             self._surfaces_begin(k0, t)
-        for k in range(k0, int(round(Tstop / float(self.dt)))):
-            self.step_membrane_models(k)
-            if k == 0 and self.recorder is not None:
-                # the time loop starts: with phi_M_init_type 'constant' PHI_M holds the membrane potential only from here on (it
-                # comes from the ODE states in the first membrane step), so this is where the map takes its starting values
-                self.recorder.arm(float(t))
-            self.solve_for_time_step(k, t)
-            if (k % self.sf) == 0 and self.save_fields:
-                self.save_h5()
-            if self.grids is not None:
-                self._grids_step(k + 1, t)
-            if self.surfaces_rec is not None:
-                self._surfaces_step(k + 1, t)
-            if ckpt is not None and (k + 1) % ckpt[0] == 0:
-                self.save_checkpoint(ckpt[1])
+        try:
+            if self.fieldmeshes is not None:
+                self._fieldmeshes_begin(k0, t)
+            for k in range(k0, int(round(Tstop / float(self.dt)))):
+                self.step_membrane_models(k)
+                if k == 0 and self.recorder is not None:
+                    # the time loop starts: with phi_M_init_type 'constant' PHI_M holds the membrane potential only from here on (it
+                    # comes from the ODE states in the first membrane step), so this is where the map takes its starting values
+                    self.recorder.arm(float(t))
+                self.solve_for_time_step(k, t)
+                if (k % self.sf) == 0 and self.save_fields:
+                    self.save_h5()
+                if self.grids is not None:
+                    self._grids_step(k + 1, t)
+                if self.surfaces_rec is not None:
+                    self._surfaces_step(k + 1, t)
+                if self.fieldmeshes is not None:
+                    self._fieldmeshes_step(k + 1, t)
+                if ckpt is not None and (k + 1) % ckpt[0] == 0:
+                    self.save_checkpoint(ckpt[1])
+        finally:
+            if self.fieldmeshes is not None:
+                self._fieldmeshes_finish()           # also when the loop raises: the frames taken so far are a file
         if self.save_fields:
             self.close_h5()
         if self.grids is not None:
